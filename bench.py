@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: images/s of DeiT-base/16-224 at bs=512 per GPU, bf16, on N MI355X GPUs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]             (N=1)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N=1)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (its roofline and
+cpu_baseline objects are null); --full adds the per-role roofline and the CPU baseline, which
+take runs of their own after the timed region. --dump-outputs DIR writes what the last timed step
+computed (rank 0: DIR/logits.npy, the [global batch, classes] fp32 logits; a fixed, seeded sample
+of the rows beyond 64 MB); inputs and weights are seeded, so two builds compare output for output.
 
 A step = one forward of the whole batch (patchify -> patch GEMM -> 12 x [LN, QKV GEMM,
 attention, out-proj GEMM + residual, LN, FC1 GEMM + GELU, FC2 GEMM + residual] -> head) through
@@ -18,7 +24,7 @@ Scaling modes (N > 1):
 The process group has a timeout (--dist-timeout): a dead or hung peer ends the run with an error
 instead of a hang (failure detection).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full only):
   roofline      the dominant kernel (the role with the most device time; FC1 GEMM for DeiT-base,
                 M = 512*197, K = 768, N = 3072) timed INSIDE 5 real forwards after the timed region:
                 HIP events around each of its launches on the model's stream (evt_model_profile,
@@ -70,7 +76,7 @@ def kernel_label(model: str, dtype: str, role: str) -> str:
 METRIC = "images/sec DeiT-base/16-224 bs=512 @1/2/4/8 GPU; % bf16 MFMA roofline"
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -80,8 +86,16 @@ def parse():
                     choices=["deit_base", "deit_small", "deit_tiny", "t2t_vit_7", "t2t_vit_10",
                              "t2t_vit_12", "t2t_vit_14", "swin_tiny", "swin_small", "swin_base"])
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget (0 = skip)")
-    ap.add_argument("--no-probe", action="store_true", help="skip the per-kernel probe")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-role "
+                         "roofline (per-kernel probe) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the outputs of the last timed step as DIR/<name>.npy "
+                         "(logits.npy: fp32 [global batch, classes]; at most 64 MB in all)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0,
+                    help="with --full: CPU baseline budget (0 = skip)")
+    ap.add_argument("--no-probe", action="store_true",
+                    help="with --full: skip the per-kernel probe")
     ap.add_argument("--gemm-variant", type=int, default=0, help="evt_set_gemm_variant (tuning A/B)")
     ap.add_argument("--isolated-probe", action="store_true",
                     help="also time FC1 alone, back to back (reported as roofline.isolated_probe_us)")
@@ -98,7 +112,26 @@ def parse():
     ap.add_argument("--dump-logits", default="",
                     help="rank 0 writes the last step's gathered [global batch, classes] fp32 "
                          "logits to this .npy file (the multi-rank parity test)")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname: str, outputs: dict) -> None:
+    """Write each output of the timed path as dirname/<name>.npy in fp32, DUMP_MAX_BYTES in all at
+    the most: an array beyond its share is cut to a fixed (seed 0), sorted sample of its rows."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(outputs), 1)
+    for name, t in outputs.items():
+        a = np.ascontiguousarray(t.detach().float().cpu().numpy(), dtype=np.float32)
+        if a.nbytes > share:
+            rows = max(1, share // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=rows, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def kernel_probe(dtype: str, M: int, K: int, N: int, iters: int = 20) -> float:
@@ -304,12 +337,14 @@ def main():
     ok = bool(torch.isfinite(logits[:B]).all().item())
     if args.dump_logits and rank == 0:
         np.save(args.dump_logits, last["logits"].float().cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": last["logits"]})
 
     gflop_img = model.cfg.gflop_per_image()
     imgs_per_s = G * args.steps / el
     peak = PEAK_BF16_TFLOPS if args.dtype == "bf16" else PEAK_F32_TFLOPS
     roof = None
-    if rank == 0 and not args.no_probe:
+    if rank == 0 and args.full and not args.no_probe:
         # every role's kernels timed INSIDE real forwards (HIP events around each launch on the
         # model's stream, evt_model_profile) with their algorithmic work, after the timed region
         from edgevisiontransformer_amd.profiling import kernel_times, roofline_table
@@ -342,7 +377,7 @@ def main():
             if args.isolated_probe:  # off by default: its launches would mix into a rocprof average
                 roof["isolated_probe_us"] = round(kernel_probe(args.dtype, M, K, N) * 1e6, 1)
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_seconds > 0:
         cpu = cpu_baseline(args.model, args.cpu_seconds)
     if rank == 0:
         coll = "gloo all-gather of logits, ranks sharing GPUs" if gloo else "RCCL all-gather of logits"

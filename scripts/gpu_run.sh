@@ -7,7 +7,7 @@
 # at the first failure (no retries). Bench arguments inside a step are comma-separated.
 #   tests[:<pytest args>]   the GPU suite (default: tests -m gpu), one process
 #   smoke                   __graft_entry__.smoke()
-#   bench:<args>            one bench.py line (e.g. bench:--batch,64,--steps,50)
+#   bench:<args>            one bench.py --full line (e.g. bench:--batch,64,--steps,50)
 #   ab:<args>               alternating A/B of bench.py <args> over the arms in $ARMS, $ROUNDS times;
 #                           an arm is "lib=<path>" (EVT_LIB), "var=<n>" (--gemm-variant) or "base"
 #                           or "env=NAME=VALUE[+NAME=VALUE...]" (environment switches)
@@ -35,10 +35,10 @@ for STEP in "$@"; do
     grep -v amdgpu.ids $O/smoke.log | tail -3 ;;
   bench)
     a=${rest//,/ }; n=$(name_of "bench $a")
-    timeout -k 10 400 python bench.py $a > $O/$n.jsonl 2>&1 || { tail -5 $O/$n.jsonl; exit 1; }
+    timeout -k 10 400 python bench.py $a --full > $O/$n.jsonl 2>&1 || { tail -5 $O/$n.jsonl; exit 1; }
     summ $O/$n.jsonl "$n" ;;
   ab)
-    a=${rest//,/ }; np=--no-probe; [ -n "${PROBE:-}" ] && np=""
+    a=${rest//,/ }; np=--no-probe; [ -n "${PROBE:-}" ] && np=--full
     for i in $(seq $ROUNDS); do
       for arm in ${ARMS:-base}; do
         n=$(name_of "ab $a $arm $i"); extra=""; envl=""
@@ -50,7 +50,7 @@ for STEP in "$@"; do
   kstats)
     a=${rest//,/ }; n=$(name_of "$a")
     timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$n -o run \
-      -- python3 $R/bench.py $a --cpu-seconds 0 > $O/${n}_under_rocprof.jsonl 2>&1 || { tail -5 $O/${n}_under_rocprof.jsonl; exit 1; }
+      -- python3 $R/bench.py $a --full --cpu-seconds 0 > $O/${n}_under_rocprof.jsonl 2>&1 || { tail -5 $O/${n}_under_rocprof.jsonl; exit 1; }
     f=$(find $O/prof_$n -name "*kernel_stats*" | head -1); cp "$f" $O/${n}_kernel_stats.csv
     bs=$(echo " $a " | sed -n 's/.* --batch \([0-9]*\) .*/\1/p'); bs=${bs:-512}
     python3 $R/scripts/kstats.py $O/${n}_kernel_stats.csv $bs > $O/${n}_kstats.txt; head -8 $O/${n}_kstats.txt ;;

@@ -11,7 +11,9 @@ from edgevisiontransformer_amd.modeling.models.vit import decode_prune_encoding
 from edgevisiontransformer_amd.weights import make_images, make_vit_params, vit_config
 from oracle.vit_ref import vit_forward
 
-REF_IMPORTANCE = "/root/reference/are_16_heads/deit_tiny_head_importance.txt"
+# the reference's are_16_heads/deit_tiny_head_importance.txt, stored as a fixture (data only)
+REF_IMPORTANCE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                              "deit_tiny_head_importance.txt")
 
 
 def test_prune_equals_zeroed_full_model():
@@ -61,7 +63,6 @@ def test_heads_from_importance_budget():
     assert pruning.heads_from_importance(np.array([[0.1, 0.2]]), keep_total=0) == [[1]]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_IMPORTANCE), reason="reference not mounted")
 def test_reference_importance_file():
     """The reference's own are_16_heads table loads as [12 layers, 3 heads] (read as data)."""
     imp = pruning.load_head_importance(REF_IMPORTANCE)
