@@ -258,7 +258,11 @@ int validate(const evt_vit_desc* d, Shape* sh) {
   const int np = d->image_size / d->patch_size;
   sh->P = np * np;
   sh->T = sh->P + 1;
-  if (sh->T > 256) return fail(EVT_EINVAL, "at most 255 patches per image are supported");
+  if (sh->T > EVT_ATTN_MAX_TOKENS)
+    return fail(EVT_EINVAL, "at most 4095 patches per image are supported");
+  if (d->dtype == EVT_DTYPE_MX8 && sh->T > 256)
+    return fail(EVT_EINVAL, "EVT_DTYPE_MX8 supports at most 255 patches per image (its attention "
+                            "kernel writes MX8 output for up to 256 tokens only)");
   sh->pd = d->patch_size * d->patch_size * d->in_chans;
   if (sh->pd % PAD_K) return fail(EVT_EINVAL, "patch_size^2 * in_chans must be a multiple of 64");
   if (d->patch_size * d->image_size % 4)
@@ -282,6 +286,19 @@ int validate(const evt_vit_desc* d, Shape* sh) {
     sh->max_ffn_st = std::max<int>(sh->max_ffn_st, (int)round_up(d->ffn[i], PAD_N));
   }
   sh->head_st = (int)round_up(d->mlp_dim, PAD_N);
+  if (sh->T > 256) {
+    // Several kernels form byte offsets into an activation buffer in 32 bits. Up to 256 tokens the
+    // supported batches were measured as they are; past them the create call refuses a max_batch
+    // whose largest buffer (image batch, patch matrix, qkv, FFN hidden) would reach 2^31 bytes.
+    const size_t es = d->dtype == EVT_DTYPE_F32 ? 4 : 2, B = (size_t)d->max_batch;
+    const size_t widest = std::max<size_t>({(size_t)3 * sh->max_inner, (size_t)sh->max_ffn_st,
+                                            (size_t)sh->D});
+    const size_t big = std::max({B * sh->T * widest * es, B * sh->P * sh->pd * es,
+                                 B * d->in_chans * d->image_size * d->image_size * sizeof(float)});
+    if (big >= (size_t)1 << 31)
+      return fail(EVT_EINVAL, "max_batch too large for more than 256 tokens per image: every "
+                              "activation buffer must stay below 2^31 bytes");
+  }
   return EVT_OK;
 }
 
@@ -697,12 +714,24 @@ int validate_t2t(const evt_t2t_desc* d, T2TShape* ts) {
   Shape& sh = ts->enc;
   sh.P = ts->grid[2] * ts->grid[2];
   sh.T = sh.P + 1;
-  if (sh.T > 256) return fail(EVT_EINVAL, "at most 255 patches per image are supported");
+  if (sh.T > EVT_ATTN_MAX_TOKENS)
+    return fail(EVT_EINVAL, "at most 4095 patches per image are supported");
   sh.D = d->dim;
   sh.pd = 9 * 64;
   sh.max_inner = d->dim;  // heads * (dim / heads)
   sh.max_ffn_st = (int)round_up(d->mlp_dim, PAD_N);
   sh.head_st = 0;
+  if (sh.T > 256) {  // as validate(): no buffer of 2^31 bytes or more past 256 tokens
+    const size_t es = d->dtype == EVT_DTYPE_F32 ? 4 : 2, B = (size_t)d->max_batch;
+    const size_t t1 = (size_t)ts->grid[0] * ts->grid[0], t2 = (size_t)ts->grid[1] * ts->grid[1];
+    const size_t big = std::max({B * t1 * round_up(ts->din[0], PAD_K) * es, B * t2 * ts->din[1] * es,
+                                 B * t1 * 4 * 64 * es, B * sh.T * 4 * sh.max_inner * es,
+                                 B * sh.T * sh.max_ffn_st * es,
+                                 B * d->in_chans * S * S * sizeof(float)});
+    if (big >= (size_t)1 << 31)
+      return fail(EVT_EINVAL, "max_batch too large for more than 256 tokens per image: every "
+                              "activation buffer must stay below 2^31 bytes");
+  }
   return EVT_OK;
 }
 
@@ -1941,9 +1970,11 @@ int evt_dense_splitk(int dtype, const evt_dense_args* a, int splits, float* part
 
 int evt_attention_hd(int dtype, const void* qkv, int64_t ldq, void* out, int64_t ldo, int B,
                      int N, int H, int head_dim, float scale, void* stream) {
-  if (!qkv || !out || B < 0 || N <= 0 || N > 256 || H <= 0 || head_dim <= 0 || head_dim > 128 ||
-      ldq < 3 * (int64_t)H * head_dim || ldo < (int64_t)H * head_dim)
-    return fail(EVT_EINVAL, "attention: bad shape (N <= 256, head size in [1, 128])");
+  if (!qkv || !out || B < 0 || N <= 0 || N > EVT_ATTN_MAX_TOKENS || H <= 0 || head_dim <= 0 ||
+      head_dim > 128 || ldq < 3 * (int64_t)H * head_dim || ldo < (int64_t)H * head_dim)
+    return fail(EVT_EINVAL, "attention: bad shape (N <= 4096, head size in [1, 128])");
+  if (N > 256 && !(scale > 0.f && scale < INFINITY))
+    return fail(EVT_EINVAL, "attention: more than 256 tokens need a positive finite scale");
   // vector accesses: 16-B loads of q / k / v rows when h_k is a multiple of 16 B, 4-element stores
   // of O when h_k % 4 == 0 (head size 64: the tuned kernels' 16-B loads and stores)
   const int64_t vec = dtype == DT_BF16 ? 8 : 4;
@@ -1962,9 +1993,11 @@ int evt_attention(int dtype, const void* qkv, int64_t ldq, void* out, int64_t ld
                   int H, float scale, void* stream) {
   // 16-B Q / O accesses: row pitches of 16 bytes multiple, 16-B aligned bases
   const int64_t vec = dtype == DT_BF16 ? 8 : 4;
-  if (!qkv || !out || B < 0 || N <= 0 || N > 256 || H <= 0 || ldq < 3 * H * 64 || ldo < H * 64 ||
-      ldq % vec || ldo % vec || (((uintptr_t)qkv | (uintptr_t)out) & 15))
-    return fail(EVT_EINVAL, "attention: bad shape (N <= 256, head size 64, 16-B aligned rows)");
+  if (!qkv || !out || B < 0 || N <= 0 || N > EVT_ATTN_MAX_TOKENS || H <= 0 || ldq < 3 * H * 64 ||
+      ldo < H * 64 || ldq % vec || ldo % vec || (((uintptr_t)qkv | (uintptr_t)out) & 15))
+    return fail(EVT_EINVAL, "attention: bad shape (N <= 4096, head size 64, 16-B aligned rows)");
+  if (N > 256 && !(scale > 0.f && scale < INFINITY))
+    return fail(EVT_EINVAL, "attention: more than 256 tokens need a positive finite scale");
   AttnParams p{qkv, ldq, out, ldo, N, H, B, scale * 1.4426950408889634f};
   EVT_HIP(attention_launch(dtype, p, (hipStream_t)stream), "attention");
   return EVT_OK;

@@ -93,10 +93,14 @@ hipError_t ln_fold(int dtype, const void* Wp, int Kpad, const float* W, const fl
                    const float* bias, int K, int N, float* colsum, float* cvec, int Npad,
                    hipStream_t s);
 
+// Most tokens per image the attention kernels take (documented in include/evt.h): up to 256 the
+// one-pass kernels (whole K / V of a head in LDS), above them the streaming kernels.
+constexpr int EVT_ATTN_MAX_TOKENS = 4096;
+
 struct AttnParams {
   const void* qkv; int64_t ldq;   // token rows, columns (qkv h d)
   void* out;       int64_t ldo;   // token rows, columns (h d)
-  int N;                          // tokens per image (<= 256)
+  int N;                          // tokens per image (<= EVT_ATTN_MAX_TOKENS; MX8 output: <= 256)
   int H;                          // heads
   int B;                          // images
   float scale_log2;               // head_dim^-0.5 * log2(e)

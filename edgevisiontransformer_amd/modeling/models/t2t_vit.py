@@ -29,7 +29,8 @@ from .vit import _capture_graph, _replay_graph, _to_device_image
 
 
 class T2T_ViT:
-    """Tokens-to-Token ViT forward on MI355X (reference `T2T_ViT`, t2t_vit.py:91-135)."""
+    """Tokens-to-Token ViT forward on MI355X (reference `T2T_ViT`, t2t_vit.py:91-135).
+    `image_size`: a multiple of 16 with (image_size / 16)^2 + 1 <= 4096 tokens."""
 
     def __init__(self, image_size=224, tokens_type="performer", in_channels=3, num_classes=1000,
                  hidden_size=768, depth=12, num_heads=12, mlp_ratio=4., token_size=64,

@@ -89,7 +89,11 @@ def _replay_graph(model) -> None:
 
 
 class ViT:
-    """Vision Transformer forward on MI355X (reference `ViT`, vit.py:9-55)."""
+    """Vision Transformer forward on MI355X (reference `ViT`, vit.py:9-55).
+
+    `image_size` / `patch_size`: any pair with (image_size / patch_size)^2 + 1 <= 4096 tokens per
+    image (224 px: 197; 384 px as `get_torch_deit`, utils.py:52-62: 577; "mx8": <= 256 tokens);
+    the factories (`get_deit_*`, `build_named`) pass `image_size=` through."""
 
     SEMANTICS = _lib.VIT_REFERENCE
     _param_shapes = staticmethod(vit_param_shapes)

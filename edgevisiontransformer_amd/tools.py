@@ -1,6 +1,7 @@
 """Benchmark CLI of the MI355X ViT path, mirroring the reference `tools.py` conventions.
 
     python -m edgevisiontransformer_amd.tools gpu_benchmark --model deit_base --input_shape 512,3,224,224
+    python -m edgevisiontransformer_amd.tools gpu_benchmark --model deit_base --input_shape 64,3,384,384
     python -m edgevisiontransformer_amd.tools gpu_benchmark --model deit_tiny --prune_encoding all_head2_ffn0.7
     python -m edgevisiontransformer_amd.tools test_keras_latency --model t2t_vit_14 --input_shape 1,224,224,3
     python -m edgevisiontransformer_amd.tools prune_benchmark --types tiny --num_runs 20
@@ -37,11 +38,16 @@ SWIN_NAMED = ("swin_tiny", "swin_small", "swin_base")   # get_swin configs (tool
 
 
 def build_model(name: str, compute_dtype: str, prune_encoding: Optional[str] = None,
-                max_batch: int = 1, seed: int = 0):
-    """A model by reference name (deit_*, t2t_vit_*, swin_*), optionally head/FFN pruned."""
+                max_batch: int = 1, seed: int = 0, image_size: int = 224):
+    """A model by reference name (deit_*, t2t_vit_*, swin_*), optionally head/FFN pruned.
+    image_size: the input resolution (reference utils.py:52-62 loads 224 and 384 px DeiT; any size
+    the library takes works for DeiT and T2T-ViT; the named Swin configs are 224 px only)."""
+    kw = {} if image_size == 224 else {"image_size": image_size}
     if name in SWIN_NAMED or name.startswith("swin_") and name.endswith("_224"):
         if prune_encoding:
             raise ValueError("prune_encoding applies to DeiT models only")
+        if image_size != 224:
+            raise ValueError(f"{name} is a 224 px configuration; got image size {image_size}")
         from .modeling.models.swin import get_swin
         cfg_name = name if name.endswith("_224") else f"{name}_patch4_window7_224"
         return get_swin(cfg_name, dtype=compute_dtype, seed=seed, max_batch=max_batch)
@@ -49,7 +55,7 @@ def build_model(name: str, compute_dtype: str, prune_encoding: Optional[str] = N
         if prune_encoding:
             raise ValueError("prune_encoding applies to DeiT models only")
         from .modeling.models.t2t_vit import build_named
-        return build_named(name, dtype=compute_dtype, seed=seed, max_batch=max_batch)
+        return build_named(name, dtype=compute_dtype, seed=seed, max_batch=max_batch, **kw)
     if name not in VIT_NAMED:
         raise ValueError(f"unknown model {name!r}; one of "
                          f"{sorted(VIT_NAMED) + list(T2T_NAMED) + list(SWIN_NAMED)}")
@@ -58,14 +64,25 @@ def build_model(name: str, compute_dtype: str, prune_encoding: Optional[str] = N
         h = VIT_NAMED[name]
         return ViT_Pruned(dim=h * 64, depth=12, heads=h, mlp_dim=h * 64 * 4, head_size=64,
                           prune_encoding=prune_encoding, dtype=compute_dtype, seed=seed,
-                          max_batch=max_batch)
-    return build_named(name, dtype=compute_dtype, seed=seed, max_batch=max_batch)
+                          max_batch=max_batch, **kw)
+    return build_named(name, dtype=compute_dtype, seed=seed, max_batch=max_batch, **kw)
 
 
 def _input_shape(name: str, spec: Optional[str]) -> List[int]:
     if spec:
         return [int(x) for x in spec.split(",")]
     return [1, 224, 224, 3] if name in T2T_NAMED else [1, 3, 224, 224]
+
+
+def _image_size(name: str, shape: List[int]) -> int:
+    """The square image size of an --input_shape: NHWC for T2T-ViT (dims 1, 2), NCHW otherwise
+    (dims 2, 3), as the reference feeds its Keras T2T and its other models."""
+    if len(shape) != 4:
+        raise ValueError(f"input_shape needs 4 dimensions, got {shape}")
+    h, w = (shape[1], shape[2]) if name in T2T_NAMED else (shape[2], shape[3])
+    if h != w:
+        raise ValueError(f"input_shape must be square, got {h} x {w}")
+    return h
 
 
 def latency_samples(model, shape: List[int], num_runs: int, warmup_runs: int,
@@ -143,7 +160,8 @@ def gpu_benchmark(argv: Optional[List[str]] = None) -> str:
     if args.dtype != "float32":
         raise ValueError("input dtype must be float32 (the reference forward's input)")
     shape = _input_shape(args.model, args.input_shape)
-    model = build_model(args.model, args.compute_dtype, args.prune_encoding, max_batch=shape[0])
+    model = build_model(args.model, args.compute_dtype, args.prune_encoding, max_batch=shape[0],
+                        image_size=_image_size(args.model, shape))
     lat = latency_samples(model, shape, args.num_runs, args.warmup_runs, args.io_binding,
                           graph=args.graph)
     avg, std = summarize(lat, args.top)
@@ -164,7 +182,8 @@ def test_keras_latency(argv: Optional[List[str]] = None) -> str:
                         help="mx8: MXFP8 encoder Dense layers (ViT family; the quantization axis)")
     args = parser.parse_args(argv)
     shape = _input_shape(args.model, args.input_shape)
-    model = build_model(args.model, args.compute_dtype, max_batch=shape[0])
+    model = build_model(args.model, args.compute_dtype, max_batch=shape[0],
+                        image_size=_image_size(args.model, shape))
     print(f"Successfully loaded model from {args.model}.")
     lat = latency_samples(model, shape, args.test_times + 1, 0, io_binding=False)
     line = f"Avg latency: {np.average(lat[1:]) * 1000: .2f}ms"

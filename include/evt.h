@@ -47,7 +47,11 @@ extern "C" {
  * heads/head_dim/ffn are per-layer arrays of length `depth` (the pruned encoding, decoded by the
  * host mirror exactly as ViT_Pruned.decode_prune_encoding, vit.py:77-97). */
 typedef struct evt_vit_desc {
-  int32_t image_size;   /* 224 */
+  int32_t image_size;   /* 224; 384 (DeiT-384, 577 tokens), patch 8, 512 px ...: any size with
+                         * (image_size / patch_size)^2 + 1 <= 4096 tokens (EVT_DTYPE_MX8: <= 256)
+                         * and in_chans * patch_size * image_size * 4 <= 160 KiB (patchify).
+                         * With more than 256 tokens evt_vit_create refuses a max_batch whose
+                         * largest activation buffer would reach 2^31 bytes (EVT_EINVAL) */
   int32_t patch_size;   /* 16; image_size % patch_size == 0 (vit.py:13) */
   int32_t in_chans;     /* 3 */
   int32_t num_classes;  /* 1000 */
@@ -242,13 +246,17 @@ int evt_dense_splitk(int dtype, const evt_dense_args* args, int splits, float* p
                      void* stream);
 
 /* Multi-head attention core (attention.py:20-34): qkv [B*N, ldq] with columns (qkv h d), head
- * size 64 -> out [B*N, ldo] columns (h d). N <= 256. */
+ * size 64 -> out [B*N, ldo] columns (h d). N <= 4096 tokens per image: up to 256 the one-pass
+ * kernels (K and V of a head staged whole in LDS), above them the streaming kernels (64-key
+ * blocks, online softmax; same contract: fp32 statistics, keys past N contribute exactly 0);
+ * above 256 tokens `scale` must be positive and finite (EVT_EINVAL otherwise). */
 int evt_attention(int dtype, const void* qkv, int64_t ldq, void* out, int64_t ldo, int B, int N,
                   int H, float scale, void* stream);
 
 /* evt_attention for any head size h_k = head_dim in [1, 128] (attention.py:6-12: h_k = dim //
  * heads): qkv [B*N, ldq >= 3*H*h_k] columns (qkv h d), out [B*N, ldo >= H*h_k] columns (h d).
- * h_k == 64 runs the tuned kernels, other sizes generic ones (features zero-padded to 32 / 64). */
+ * h_k == 64 runs the tuned kernels, other sizes generic ones (features zero-padded to 32 / 64 /
+ * 96 / 128). N <= 4096 and the scale rule above 256 tokens as evt_attention. */
 int evt_attention_hd(int dtype, const void* qkv, int64_t ldq, void* out, int64_t ldo, int B, int N,
                      int H, int head_dim, float scale, void* stream);
 
@@ -274,7 +282,9 @@ int evt_patchify_cm(int dtype, const float* img, int B, int C, int HW, int ps, v
 
 /* Static shape of a T2T_ViT (t2t_vit.py:91-114; factories get_t2t_vit_{7,10,12,14} :138-148).
  * tokens_type 'performer' only (:49-59). Soft splits k7s4p2, k3s2p1, k3s2p1 give S/4, S/8 and
- * S/16 token grids; image_size must be a multiple of 16 with (S/16)^2 + 1 <= 256 tokens. */
+ * S/16 token grids; image_size must be a multiple of 16 with (S/16)^2 + 1 <= 4096 tokens. With
+ * more than 256 tokens evt_t2t_create refuses a max_batch whose largest activation buffer would
+ * reach 2^31 bytes (EVT_EINVAL). */
 typedef struct evt_t2t_desc {
   int32_t image_size;   /* S = 224 */
   int32_t in_chans;     /* 3 */

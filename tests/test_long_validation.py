@@ -1,0 +1,78 @@
+"""Host-side validation of the limits past 256 tokens per image (csrc/capi.cpp validate /
+validate_t2t through the workspace queries, and the op entry points' argument checks): no GPU is
+touched, every call returns before any launch."""
+import ctypes
+
+import pytest
+
+from edgevisiontransformer_amd import _lib
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return _lib.load_library()
+
+
+def _vit(lib, image, patch, dtype, batch, dim=768, heads=12, mlp=3072):
+    arr = (ctypes.c_int32 * 12)(*([heads] * 12))
+    hd = (ctypes.c_int32 * 12)(*([64] * 12))
+    ffn = (ctypes.c_int32 * 12)(*([mlp] * 12))
+    d = _lib.evt_vit_desc(image, patch, 3, 1000, dim, 12, mlp, arr, hd, ffn, _lib.DTYPE[dtype], batch)
+    out = ctypes.c_size_t()
+    rc = lib.evt_query_workspace(ctypes.byref(d), batch, ctypes.byref(out))
+    return rc, lib.evt_last_error().decode(), out.value
+
+
+def test_vit_token_limit(lib):
+    assert _vit(lib, 384, 16, "bf16", 64)[0] == _lib.EVT_OK          # 577 tokens
+    assert _vit(lib, 504, 8, "bf16", 1)[0] == _lib.EVT_OK            # 63^2 + 1 = 3970
+    rc, msg, _ = _vit(lib, 512, 8, "bf16", 1)                         # 64^2 + 1 = 4097
+    assert rc == _lib.EVT_EINVAL and "4095 patches" in msg
+    # the patchify kernel's own limit (one image strip in LDS) is met first at patch 16
+    rc, msg, _ = _vit(lib, 1008, 16, "bf16", 1)
+    assert rc == _lib.EVT_EINVAL and "image strip exceeds LDS" in msg
+
+
+def test_mx8_keeps_256_tokens(lib):
+    assert _vit(lib, 224, 16, "mx8", 8)[0] == _lib.EVT_OK
+    rc, msg, _ = _vit(lib, 384, 16, "mx8", 8)
+    assert rc == _lib.EVT_EINVAL and "EVT_DTYPE_MX8" in msg and "255 patches" in msg
+
+
+def test_vit_batch_whose_buffers_reach_2g_is_refused(lib):
+    """DeiT-base at 384 px and 512 images: 295424 rows. bf16: the FFN hidden buffer is 1.8 GB
+    (accepted); f32: the qkv buffer is 2.7 GB, past the 32-bit byte offsets of several kernels."""
+    rc, _, ws = _vit(lib, 384, 16, "bf16", 512)
+    assert rc == _lib.EVT_OK and ws > 3e9
+    rc, msg, _ = _vit(lib, 384, 16, "f32", 512)
+    assert rc == _lib.EVT_EINVAL and "2^31 bytes" in msg and "max_batch" in msg
+    # up to 256 tokens nothing changes: the same batch in f32 at 224 px is accepted as before
+    assert _vit(lib, 224, 16, "f32", 1024)[0] == _lib.EVT_OK
+
+
+def _t2t(lib, image, dtype, batch):
+    d = _lib.evt_t2t_desc(image, 3, 1000, 384, 14, 6, 1152, 64, _lib.DTYPE[dtype], batch)
+    out = ctypes.c_size_t()
+    rc = lib.evt_t2t_query_workspace(ctypes.byref(d), batch, ctypes.byref(out))
+    return rc, lib.evt_last_error().decode()
+
+
+def test_t2t_limits(lib):
+    assert _t2t(lib, 272, "bf16", 2)[0] == _lib.EVT_OK                # 290 tokens
+    rc, msg = _t2t(lib, 1024, "bf16", 1)                              # 4097 tokens
+    assert rc == _lib.EVT_EINVAL and "4095 patches" in msg
+    # 384 px, 4096 images: the first unfold buffer is 4096 * 96^2 * 192 * 2 B = 14 GB
+    rc, msg = _t2t(lib, 384, "bf16", 4096)
+    assert rc == _lib.EVT_EINVAL and "2^31 bytes" in msg
+    assert _t2t(lib, 224, "bf16", 4096)[0] == _lib.EVT_OK             # 197 tokens: as before
+
+
+@pytest.mark.parametrize("scale", [0.0, -0.125, float("inf"), float("nan")])
+def test_long_attention_needs_a_positive_scale(lib, scale):
+    """The online softmax rescales by 2^((m_old - m_new) scale): refused before any launch (the
+    pointers are never dereferenced). Up to 256 tokens the scale is not checked, as before."""
+    p = ctypes.c_void_p(0x1000)
+    assert lib.evt_attention(1, p, 192, p, 64, 1, 577, 1, scale, None) == _lib.EVT_EINVAL
+    assert "positive finite scale" in lib.evt_last_error().decode()
+    assert lib.evt_attention_hd(0, p, 96, p, 32, 1, 577, 1, 32, scale, None) == _lib.EVT_EINVAL
+    assert "positive finite scale" in lib.evt_last_error().decode()
