@@ -32,6 +32,19 @@ namespace evt {
 
 namespace {
 
+// The one-pass softmax below takes the maximum of the raw scores and masks keys past N with -inf
+// before it scales, which needs a positive scale: with scale <= 0 (allowed up to 256 tokens) the
+// raw maximum does not bound the scaled scores and -inf * scale is NaN or +inf. That rare case (a
+// wave-uniform test) scales the still finite raw scores here, before the masking, and goes on with
+// c = 1; a positive scale is returned as it is and the scores stay raw.
+template <int NKT>
+__device__ __forceinline__ float prescale_nonpositive(f32x4 (&s)[NKT], float scale_log2) {
+  if (scale_log2 > 0.f) return scale_log2;
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt) s[kt] = s[kt] * scale_log2;
+  return 1.f;
+}
+
 // One 16-query tile of one (image, head): S^T = K Q^T, softmax, O^T = V^T P^T, stores.
 // Ks / Vs: the head's K and V rows staged in LDS (NKT*16 rows of 128 B, swizzle chunk ^ (row & 7)).
 
@@ -58,6 +71,7 @@ __device__ __forceinline__ void attn_tile_bf16(const AttnParams& p, const EVT_LD
   // tiles that reach past N (a wave-uniform test): the rest skip the masking VALU work.
   // (NFULL: tiles that are full for every N this NKT is launched for, attention_launch)
   constexpr int NFULL = NKT == 13 ? 12 : NKT == 12 ? 8 : NKT == 14 ? 13 : NKT == 16 ? 14 : NKT == 8 ? 4 : 0;
+  const float c = prescale_nonpositive(s, p.scale_log2);
 #pragma unroll
   for (int kt = NFULL; kt < NKT; ++kt)
 #pragma unroll
@@ -65,7 +79,7 @@ __device__ __forceinline__ void attn_tile_bf16(const AttnParams& p, const EVT_LD
       if (kt * 16 + 4 * g + j >= p.N) s[kt][j] = -INFINITY;
   // max of the raw scores in two v_max3 chains (one new pair per op; -fno-honor-nans: no
   // canonicalising v_max per MFMA result), then exp2(s c - m c) as one packed FMA per pair
-  // (scale_log2 > 0, so the max commutes with the scale). Round 3: 521 -> 458 VALU instructions
+  // (c > 0, so the max commutes with the scale). Round 3: 521 -> 458 VALU instructions
   // per tile, attention 131.5 -> 129.3 us per layer (DeiT-base bs512, alternating same-box runs)
   float m0 = fmaxf(fmaxf(s[0][0], s[0][1]), s[0][2]), m1 = fmaxf(fmaxf(s[0][3], s[1][0]), s[1][1]);
 #pragma unroll
@@ -77,8 +91,8 @@ __device__ __forceinline__ void attn_tile_bf16(const AttnParams& p, const EVT_LD
   if constexpr ((4 * NKT - 6) % 4 != 0) mx = fmaxf(fmaxf(mx, s[NKT - 1][2]), s[NKT - 1][3]);
   mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
   mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  const f32x2 sc2 = {p.scale_log2, p.scale_log2};
-  const f32x2 mo2 = {-mx * p.scale_log2, -mx * p.scale_log2};
+  const f32x2 sc2 = {c, c};
+  const f32x2 mo2 = {-mx * c, -mx * c};
   f32x2 sum2 = {0.f, 0.f};
 #pragma unroll
   for (int kt = 0; kt < NKT; ++kt)
@@ -328,6 +342,7 @@ __global__ __launch_bounds__(64 * ATTN_F32_WAVES) void attn_f32_kernel(AttnParam
       }
       s[kt] = acc;
     }
+    const float c = prescale_nonpositive(s, p.scale_log2);
     float mx = -INFINITY;
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt)
@@ -339,13 +354,13 @@ __global__ __launch_bounds__(64 * ATTN_F32_WAVES) void attn_f32_kernel(AttnParam
       }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float moff = mx * p.scale_log2;
+    const float moff = mx * c;
     float sum = 0.f;
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float e = exp2f(s[kt][j] * p.scale_log2 - moff);
+        const float e = exp2f(s[kt][j] * c - moff);
         s[kt][j] = e;
         sum += e;
       }
@@ -444,6 +459,7 @@ __global__ __launch_bounds__(256) void attn_gen_bf16_kernel(AttnParams p) {
       }
       s[kt] = acc;  // S^T[key = kt*16 + 4g + j][query = qt*16 + c16]
     }
+    const float c = prescale_nonpositive(s, p.scale_log2);
     float mx = -INFINITY;
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt)
@@ -454,13 +470,13 @@ __global__ __launch_bounds__(256) void attn_gen_bf16_kernel(AttnParams p) {
       }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float moff = mx * p.scale_log2;
+    const float moff = mx * c;
     float sum = 0.f;
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float e = __builtin_amdgcn_exp2f(s[kt][j] * p.scale_log2 - moff);
+        const float e = __builtin_amdgcn_exp2f(s[kt][j] * c - moff);
         s[kt][j] = e;
         sum += e;
       }
@@ -547,6 +563,7 @@ __global__ __launch_bounds__(256) void attn_gen_f32_kernel(AttnParams p) {
         for (int e = 0; e < 4; ++e) s[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[e], qf[e], s[kt], 0, 0, 0);
       }
     }
+    const float c = prescale_nonpositive(s, p.scale_log2);
     float mx = -INFINITY;
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt)
@@ -557,13 +574,13 @@ __global__ __launch_bounds__(256) void attn_gen_f32_kernel(AttnParams p) {
       }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float moff = mx * p.scale_log2;
+    const float moff = mx * c;
     float sum = 0.f;
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float e = exp2f(s[kt][j] * p.scale_log2 - moff);
+        const float e = exp2f(s[kt][j] * c - moff);
         s[kt][j] = e;
         sum += e;
       }

@@ -157,7 +157,9 @@ __device__ __forceinline__ void epi_rows_t(const GemmParams& p, EVT_LDS char* st
     int64_t orow = m;
     if (FL & EPI_LNIN) {
       const float mu = row_bcast(in_mu, 2 * i, sub), r = row_bcast(in_r, 2 * i, sub);
-      v = v * r - cs4 * (r * mu) + bias4;
+      // f32: gemm_nt_kernel subtracted mu from the A rows, acc is (x - mu) . W' already
+      if constexpr (std::is_same<T, float>::value) v = v * r + bias4;
+      else v = v * r - cs4 * (r * mu) + bias4;
     } else if (FL & EPI_BIAS) {
       v += bias4;
     }
@@ -440,6 +442,23 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmParams p) {
   const int nk = p.K * (int)sizeof(T) / ROWB;
   stage(0, 0);
   const int frow = lane & 15, fsw = lane & 7, fg = lane >> 4;
+  // f32 with EPI_LNIN: the A fragments are centred (x - mu, mu from the row's statistics) before
+  // the product. The folded form r acc - r mu colsum subtracts two fp32 sums of ~|mu| |colsum|
+  // whose rounding (a few 1e-6 over K = 768) r then multiplies: up to 1 / sqrt(eps) = 316 on a
+  // constant row, 2e-3 against the 1e-3 this path promises. bf16 keeps the folded form (the
+  // products are exact in fp32 there and its tolerance is 100 times wider). Columns past K are
+  // zero in Wp, so the -mu they pick up contributes nothing.
+  constexpr bool CENTER = std::is_same<T, float>::value && (FL & EPI_LNIN) != 0;
+  float amu[4] = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (CENTER) {
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      const int mr = min(m0 + wm * 64 + mt * 16 + frow, p.M - 1);
+      float r_unused;
+      ln_coef(p.stats_in, p.nslots, (int64_t)mr * (p.stats_step > 1 ? p.stats_step : 1), p.inv_d,
+              p.eps, amu[mt], r_unused);
+    }
+  }
   for (int kt = 0; kt < nk; ++kt) {
     wait_vmcnt0();
     __syncthreads();
@@ -453,6 +472,11 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmParams p) {
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt)
         a[mt] = *(const EVT_LDS u32x4*)(As + (wm * 64 + mt * 16 + frow) * ROWB + coff);
+      if constexpr (CENTER) {
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+          a[mt] = __builtin_bit_cast(u32x4, __builtin_bit_cast(f32x4, a[mt]) - amu[mt]);
+      }
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt)
         w[nt] = *(const EVT_LDS u32x4*)(Ws + (wn * 64 + nt * 16 + frow) * ROWB + coff);

@@ -44,7 +44,9 @@ def ln_fold(dtype, wp, kpad, npad, W, beta, bias=None):
 
 def dense(dtype, flags, A, wp, kpad, npad, M, N, ldc=None, bias=None, resid=None, pos=None, P=0,
           C=None, colsum=None, stats_in=None, rstats=None, rgamma=None, rbeta=None,
-          stats_out=None, ln_width=0, ln_eps=1e-5):
+          stats_out=None, ln_width=0, ln_eps=1e-5, stats_step=0):
+    """lda / ldr follow the row strides of A / resid (pass a column slice of a wider tensor for a
+    padded pitch); stats_step: A row m reads stats_in row m * stats_step (include/evt.h)."""
     out_f32 = bool(flags & _lib.EPI_OUT_F32)
     ldc = ldc or N
     if C is None:
@@ -59,7 +61,7 @@ def dense(dtype, flags, A, wp, kpad, npad, M, N, ldc=None, bias=None, resid=None
         setattr(a, name, t.data_ptr() if t is not None else None)
     a.ldr = resid.stride(0) if resid is not None else 0
     a.ldp = pos.stride(0) if pos is not None else 0
-    a.P, a.ln_width, a.ln_eps = P, ln_width, ln_eps
+    a.P, a.ln_width, a.ln_eps, a.stats_step = P, ln_width, ln_eps, stats_step
     _lib.check(_lib.load_library().evt_dense(_lib.DTYPE[dtype], ctypes.byref(a), _s()))
     return C
 
