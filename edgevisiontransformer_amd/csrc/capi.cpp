@@ -98,6 +98,7 @@ struct SwinBlock {  // one Swin block (microsoft SwinTransformerBlock)
 
 struct SwinStage {
   int C = 0, Cst = 0, H = 0, R = 0, mlp = 0, mst = 0;
+  int w = 7;                 // window of the stage: min(window_size, R), 7 or 12
   DenseW merge;              // LN(4C)-folded reduction Linear(4C, 2C, bias=False) (stage > 0)
   std::vector<SwinBlock> blocks;
 };
@@ -761,6 +762,7 @@ struct SwinGeo {
   int ns = 0;
   int C[EVT_SWIN_MAX_STAGES], Cst[EVT_SWIN_MAX_STAGES], R[EVT_SWIN_MAX_STAGES];
   int mlp[EVT_SWIN_MAX_STAGES], mst[EVT_SWIN_MAX_STAGES];
+  int w[EVT_SWIN_MAX_STAGES];  // window of the stage: min(window_size, R)
   int pd = 0, pdst = 0;  // patch vector width (c, kh, kw) and its K padding
 };
 
@@ -774,7 +776,8 @@ int validate_swin(const evt_swin_desc* d, SwinGeo* g) {
     return fail(EVT_EINVAL, "image_size must be a multiple of patch_size");
   if (d->in_chans <= 0 || d->num_classes <= 0 || d->max_batch <= 0 || !(d->mlp_ratio > 0.f))
     return fail(EVT_EINVAL, "in_chans, num_classes, max_batch, mlp_ratio must be positive");
-  if (d->window_size != 7) return fail(EVT_EINVAL, "window_size must be 7 in this build");
+  if (d->window_size != 7 && d->window_size != 12)
+    return fail(EVT_EINVAL, "window_size must be 7 or 12 in this build");
   if (d->embed_dim <= 0 || d->embed_dim % 32)
     return fail(EVT_EINVAL, "embed_dim must be a positive multiple of 32");
   g->ns = d->num_stages;
@@ -786,7 +789,14 @@ int validate_swin(const evt_swin_desc* d, SwinGeo* g) {
       if (R % 2) return fail(EVT_EINVAL, "patch merging needs an even resolution");
       R /= 2;
     }
-    if (R % 7) return fail(EVT_EINVAL, "every stage resolution must be a multiple of the window (7)");
+    // the reference rule: a stage no larger than the window is one window of its own size
+    const int win = std::min(d->window_size, R);
+    if ((win != 7 && win != 12) || R % win)
+      return fail(EVT_EINVAL, "stage " + std::to_string(i) + ": resolution " + std::to_string(R) +
+                                  " with window " + std::to_string(win) +
+                                  "; every stage resolution must be a multiple of the window (" +
+                                  std::to_string(d->window_size) + ") and its window 7 or 12");
+    g->w[i] = win;
     const int C = d->embed_dim << i;
     if (C > 1024) return fail(EVT_EINVAL, "stage width must be <= 1024");
     if (d->depths[i] < 0) return fail(EVT_EINVAL, "depths must be >= 0");
@@ -802,6 +812,24 @@ int validate_swin(const evt_swin_desc* d, SwinGeo* g) {
     g->mlp[i] = (int)(C * d->mlp_ratio);
     if (g->mlp[i] <= 0) return fail(EVT_EINVAL, "mlp width must be positive");
     g->mst[i] = (int)round_up(g->mlp[i], PAD_N);
+  }
+  if (g->R[0] * g->R[0] > 3136) {
+    // As validate() past 256 tokens: several kernels form byte offsets into an activation buffer
+    // in 32 bits. Up to 56 x 56 tokens (224 px) the supported batches are as they were; past
+    // them a max_batch whose largest buffer (image batch, patch matrix, qkv, MLP hidden, merge
+    // gather, row statistics) would reach 2^31 bytes is refused.
+    const size_t es = d->dtype == EVT_DTYPE_F32 ? 4 : 2, B = (size_t)d->max_batch;
+    size_t big = B * d->in_chans * d->image_size * d->image_size * sizeof(float);
+    big = std::max(big, B * g->R[0] * g->R[0] * g->pdst * es);
+    for (int i = 0; i < g->ns; ++i) {
+      const size_t rows = B * g->R[i] * g->R[i];
+      const size_t widest = std::max<size_t>({(size_t)3 * g->C[i], (size_t)g->mst[i],
+                                              i > 0 ? (size_t)4 * g->C[i - 1] : 0});
+      big = std::max({big, rows * widest * es, rows * stats_slots(g->C[i]) * 2 * sizeof(float)});
+    }
+    if (big >= (size_t)1 << 31)
+      return fail(EVT_EINVAL, "max_batch too large for more than 3136 tokens per image: every "
+                              "activation buffer must stay below 2^31 bytes");
   }
   return EVT_OK;
 }
@@ -1563,6 +1591,7 @@ int evt_swin_create(const evt_swin_desc* desc, const float* const* w, int n_weig
       st.R = g.R[i];
       st.mlp = g.mlp[i];
       st.mst = g.mst[i];
+      st.w = g.w[i];
       if (i > 0) {  // PatchMerging: LayerNorm(4C) folded into reduction Linear(4C, 2C, bias=False)
         EVT_RC(make_dense(m, &st.merge, w[k + 2], nullptr, 4 * g.C[i - 1], st.C, s, w[k], w[k + 1]));
         k += 3;
@@ -1570,11 +1599,12 @@ int evt_swin_create(const evt_swin_desc* desc, const float* const* w, int n_weig
       st.blocks.resize(desc->depths[i]);
       for (int j = 0; j < desc->depths[i]; ++j) {
         SwinBlock& bl = st.blocks[j];
-        bl.shift = (j % 2 == 1 && st.R > 7) ? 3 : 0;  // SW-MSA on odd blocks; none at R == window
+        // SW-MSA on odd blocks; none where the stage is one window (R <= window_size)
+        bl.shift = (j % 2 == 1 && st.R > desc->window_size) ? desc->window_size / 2 : 0;
         const int C = st.C;
         EVT_RC(make_dense(m, &bl.qkv, w[k + 2], w[k + 3], C, 3 * C, s, w[k + 0], w[k + 1]));
-        EVT_RC(dev_alloc(m, (void**)&bl.bias, rpb_table_floats(st.H, 7, bl.shift) * sizeof(float)));
-        EVT_HIP(rpb_dense_launch(w[k + 4], st.H, 7, bl.shift, bl.bias, s), "relative position bias");
+        EVT_RC(dev_alloc(m, (void**)&bl.bias, rpb_table_floats(st.H, st.w, bl.shift) * sizeof(float)));
+        EVT_HIP(rpb_dense_launch(w[k + 4], st.H, st.w, bl.shift, bl.bias, s), "relative position bias");
         EVT_RC(make_dense(m, &bl.proj, w[k + 5], w[k + 6], C, C, s));
         EVT_RC(make_dense(m, &bl.fc1, w[k + 9], w[k + 10], C, st.mlp, s, w[k + 7], w[k + 8]));
         EVT_RC(make_dense(m, &bl.fc2, w[k + 11], w[k + 12], st.mlp, C, s));
@@ -1613,7 +1643,7 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
   const double es = (double)elem_size(dt);
   const bool stem96 = dt == DT_BF16 && d.in_chans == 3 && d.patch_size == 4 && s0.C == 96 &&
                       s0.Cst == 96 && m->patch.kpad == 64 && d.image_size % 16 == 0 &&
-                      d.image_size <= 256;
+                      d.image_size <= 256 && s0.w == 7;
   if (stem96) {  // Conv2d + embedding LayerNorm in one kernel (swin.hip, swin_embed96_kernel)
     ProfScope ps(m, EVT_PROF_PATCH_EMBED, s);
     prof_work(m, 2.0 * rows * 96 * 48,
@@ -1687,7 +1717,8 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
       }
     }
     for (const SwinBlock& bl : st.blocks) {
-      const bool fuse96 = dt == DT_BF16 && C == 96 && st.H == 3 && gemm_auto();
+      // the fused C = 96 sublayers are window-7 kernels; a window-12 stage takes the GEMM path
+      const bool fuse96 = dt == DT_BF16 && C == 96 && st.H == 3 && st.w == 7 && gemm_auto();
       const double slot_rows = (double)rows * stats_slots(C) * 8;
       if (fuse96) {  // stage-1 attention sublayer fused (swin.hip, swin_attn96_kernel)
         ProfScope ps(m, EVT_PROF_ATTN_SUBLAYER, s);
@@ -1709,10 +1740,11 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
         }
         {
           ProfScope ps(m, EVT_PROF_ATTENTION, s);
-          prof_work(m, 4.0 * rows * 49 * C, 4.0 * rows * C * es);  // 49 keys per query
-          SwinAttnParams ap{m->qkv, 3 * C, m->o, Cst, bl.bias, B, st.R, st.R / 7, C, st.H,
+          prof_work(m, 4.0 * rows * st.w * st.w * C, 4.0 * rows * C * es);  // w^2 keys per query
+          SwinAttnParams ap{m->qkv, 3 * C, m->o, Cst, bl.bias, B, st.R, st.R / st.w, C, st.H,
                             bl.shift, scale_log2};
-          EVT_HIP(window_attn_launch(dt, ap, s), "window attention");
+          EVT_HIP(st.w == 12 ? window12_attn_launch(dt, ap, s) : window_attn_launch(dt, ap, s),
+                  "window attention");
         }
         ProfScope ps(m, EVT_PROF_OUT_PROJ, s);
         DenseCall pc;  // proj + bias + residual x -> xm (+ stats)
@@ -1721,7 +1753,7 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
         pc.resid = m->x; pc.ldr = Cst; pc.stats_out = m->sm; pc.ln_width = C;
         EVT_RC(dense(m, bl.proj, pc, s));
       }
-      if (dt == DT_BF16 && C == 96 && st.mlp == 384 && gemm_auto()) {
+      if (dt == DT_BF16 && C == 96 && st.mlp == 384 && st.w == 7 && gemm_auto()) {
         // stage-1 MLP (C = 96) fused: hidden kept on chip (swin.hip, swin_mlp96_kernel)
         ProfScope ps(m, EVT_PROF_MLP, s);
         prof_work(m, 4.0 * rows * C * st.mlp, 2.0 * rows * C * es + 2 * slot_rows +

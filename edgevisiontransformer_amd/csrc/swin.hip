@@ -19,6 +19,8 @@
 //                        position bias + SW-MSA mask (one precomputed table per window type),
 //                        exact softmax
 //   window_attn_f32      the exact fp32 parity path (VALU dot products, K / V in LDS)
+//   window12_attn_bf16 / _f32   the same for 12 x 12 windows (the 384 px configurations): block =
+//                        3 waves = one (image, window, head); the window-7 kernels are 7-specific
 //   ln_pool_kernel       final LayerNorm + mean over tokens (AdaptiveAvgPool1d) -> [B][Cst]
 #include <algorithm>
 
@@ -540,7 +542,351 @@ __global__ __launch_bounds__(256) void window_attn_f32_kernel(SwinAttnParams p) 
   }
 }
 
+// ---- window 12 (swin_*_patch4_window12_384) -------------------------------------------------
+// The only table of the w = 12 path is the compact relative-position table per head:
+// RPB12_CROW floats per head, entries 0 .. 528 = table[r][h] * log2(e), 0 after. Both w = 12
+// kernels work the SW-MSA regions out themselves, so no dense [q][k] table exists for w = 12 and
+// the w = 7 tables (and rpb_compact's offset into them) are what they were.
+constexpr int RPB12_CROW = 576;  // 9 x 64 floats
+__global__ void rpb12_kernel(const float* __restrict__ table, int H, float* __restrict__ out) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= H * RPB12_CROW) return;
+  const int h = e / RPB12_CROW, r = e - h * RPB12_CROW;
+  out[e] = r < 529 ? table[r * H + h] * kLog2e : 0.f;
+}
+
+constexpr int div12(int t) { return (t * 171) >> 11; }  // t / 12 for t < 160
+constexpr bool div12_exact() {
+  for (int t = 0; t < 160; ++t)
+    if (div12(t) != t / 12) return false;
+  return true;
+}
+static_assert(div12_exact(), "div12 must equal t / 12 over the padded window");
+
+// bf16 window attention for 12 x 12 windows: 144 tokens = 9 full tiles of 16, no key padding in
+// the scores. Block = 3 waves = one (image, window, head); the waves share the V tile (160 key
+// rows x 64 B, rows 144 .. 159 a finite copy of key 143, LDS-DMA with the w = 7 kernel's chunk
+// swizzle) and the head's compact bias table (529 entries x log2 e), and each takes three of the
+// nine query tiles. As in the w = 7 kernel, Q / K fragments are 16-B loads straight from the
+// raster-order QKV rows through the image's buffer descriptor (each wave loads all nine K tiles:
+// the repeats hit the L1 / L2, HBM sees each row once), the shift and the window partition /
+// reverse are row arithmetic only, S^T = K Q^T and O^T = V^T P^T run on
+// v_mfma_f32_16x16x32_bf16, and the softmax is exact.
+//   bias(q, k) = T[(qi - ki + 11) 23 + (qj - kj + 11)] = T[a(q) - b(k)],
+//   a(q) = 11 qi + q + 264, b(k) = 11 ki + k; SW-MSA regions with cut = 12 - shift.
+// P . V takes 4.5 k-steps of 32 keys: the fifth step's upper 16 keys (144 .. 159) carry P = 0.
+// Per query tile 9 + 10 MFMAs, per block 81 + 90 (the w = 7 wave: 32). Three waves rather than
+// four because nine query tiles split evenly over three; a fourth wave would idle for a third of
+// the block's life. Registers: 9 K tiles (36) + 3 Q tiles (12) + 9 score tiles (36) + 36 table
+// offsets per lane; LDS 12.25 KiB per block, so the waves per SIMD are bound by registers.
+// Measured (Swin-B 384 px stage 1, 64 images, profiles/swin384_window12_measure.json): 213.6 us
+// per launch = 35 % of HBM peak on QKV read + O write and 204 TFLOP/s (8 % of MFMA peak), against
+// the w = 7 kernel's 53 % / 104 TFLOP/s in the same run: three times the MFMA work per byte, and
+// neither HBM nor the MFMA binds - the per-score VALU / LDS work (bias read, scale, mask, exp2:
+// 144 scores per query) at 3 waves per SIMD does.
+constexpr int W12_VROWS = 160;
+__global__ __launch_bounds__(192) void window12_attn_bf16_kernel(SwinAttnParams p) {
+  __shared__ __attribute__((aligned(16))) char smem[W12_VROWS * 64 + RPB12_CROW * 4];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // uniform: scalar index math
+  const int pair = blockIdx.x;  // (B * windows * H < 2^31: checked at launch)
+  const int nw = p.nwx * p.nwx;
+  const int h = pair % p.H;
+  const int bw = pair / p.H;
+  const int win = bw % nw, b = bw / nw;
+  const int R = p.R, s0 = p.shift;
+  const int wy = win / p.nwx, wx = win - wy * p.nwx;
+  const int y0 = wy * 12 + s0, x0 = wx * 12 + s0;
+  const int wtype = s0 ? (wy == p.nwx - 1 ? 2 : 0) + (wx == p.nwx - 1 ? 1 : 0) : 0;
+  // image-local raster row of window token t (with the cyclic shift)
+  auto lrow = [&](int t) {
+    const int i = div12(t), j = t - 12 * i;
+    int y = y0 + i, x = x0 + j;
+    if (y >= R) y -= R;
+    if (x >= R) x -= R;
+    return y * R + x;
+  };
+  const int ldq2 = (int)p.ldq * 2, ldo2 = (int)p.ldo * 2;
+  const int64_t img0 = (int64_t)b * R * R;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+      (char*)const_cast<void*>(p.qkv) + img0 * ldq2, 0, R * R * ldq2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
+      (char*)p.out + img0 * ldo2, 0, R * R * ldo2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(p.bias) + h * RPB12_CROW, 0, RPB12_CROW * 4, 0x00020000);
+  const int g = lane >> 4, c16 = lane & 15;
+  EVT_LDS char* Vs = (EVT_LDS char*)smem;
+  EVT_LDS char* Ts = (EVT_LDS char*)smem + W12_VROWS * 64;
+  const int C2 = p.C * 2;
+
+  // the head's compact bias table -> LDS (9 x 64 lanes x 4 B, three per wave)
+#pragma unroll
+  for (int n = 0; n < 3; ++n) {
+    const int i = wave + 3 * n;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rt, Ts + i * 256, 4, lane * 4, i * 256, 0, 0);
+  }
+  // V rows (keys) -> LDS: instruction i covers rows 16 i + (lane >> 2), 16-B chunk lane & 3;
+  // i = 9 (rows 144 .. 159, P = 0 there) repeats key 143 so that the products are 0, not NaN
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    const int i = wave + 3 * n;
+    if (i < W12_VROWS / 16) {
+      const int r = 16 * i + (lane >> 2), ch = (lane & 3) ^ ((r >> 2) & 3);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, Vs + i * 1024, 16,
+                                               lrow(min(r, 143)) * ldq2 + (h * 32 + ch * 8) * 2,
+                                               2 * C2, 0, 0);
+    }
+  }
+  // K fragments of all nine tiles, Q fragments of this wave's three: tile i, lane (token
+  // 16 i + c16, d 8 g .. 8 g + 7)
+  u32x4 qf[3], kf[9];
+  int qoff[3];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) {
+    const int vo = lrow(16 * i + c16) * ldq2 + (h * 32 + 8 * g) * 2;
+    kf[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, C2, 0));
+  }
+#pragma unroll
+  for (int n = 0; n < 3; ++n) {
+    const int lr = lrow(16 * (3 * wave + n) + c16);
+    qoff[n] = lr * ldo2 + (h * 32 + 4 * g) * 2;  // the query's output row, this lane's columns
+    qf[n] = __builtin_bit_cast(
+        u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lr * ldq2 + (h * 32 + 8 * g) * 2, 0, 0));
+  }
+  // per-lane table offsets b(k) of its 36 keys k = 16 kt + 4 g + j and, for SW-MSA windows, their
+  // region codes (bit 0: lower part of the last window row, bit 1: right part of the last window
+  // column), one byte per j
+  int kofs[9][4];
+  unsigned kc[9];
+  const int cut = 12 - s0;
+  const bool lr_ = wtype & 2, lc_ = wtype & 1;
+#pragma unroll
+  for (int kt = 0; kt < 9; ++kt) {
+    kc[kt] = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int k = 16 * kt + 4 * g + j, ki = div12(k), kj = k - 12 * ki;
+      kofs[kt][j] = (11 * ki + k) * 4;
+      kc[kt] |= (unsigned)((lr_ && ki >= cut ? 1 : 0) | (lc_ && kj >= cut ? 2 : 0)) << (8 * j);
+    }
+  }
+  wait_vmcnt0();    // this wave's LDS-DMA has landed ...
+  __syncthreads();  // ... and so has the other two waves'
+
+  const int tq = (lane >> 2) & 3, tp = lane & 3;
+  const float NEG = -INFINITY;
+#pragma unroll
+  for (int n = 0; n < 3; ++n) {
+    const int q = 16 * (3 * wave + n) + c16;
+    const int qi = div12(q), qj = q - 12 * qi;
+    const EVT_LDS char* Tq = Ts + (11 * qi + q + 264) * 4;
+    const unsigned cq = ((lr_ && qi >= cut ? 1u : 0u) | (lc_ && qj >= cut ? 2u : 0u)) * 0x01010101u;
+    f32x4 s[9];
+#pragma unroll
+    for (int kt = 0; kt < 9; ++kt) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf[kt]),
+                                                      __builtin_bit_cast(bf16x8, qf[n]), acc, 0,
+                                                      0, 0);
+    }
+    // s[kt][j] = S^T[key 16 kt + 4 g + j][query q]: scores in the log2 domain + bias on packed
+    // pairs, then the region mask
+    const f32x2 sc2 = {p.scale_log2, p.scale_log2};
+#pragma unroll
+    for (int kt = 0; kt < 9; ++kt) {
+      f32x4 bv;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bv[j] = *(const EVT_LDS float*)(Tq - kofs[kt][j]);
+      const f32x2 lo = f32x2{s[kt][0], s[kt][1]} * sc2 + f32x2{bv[0], bv[1]};
+      const f32x2 hi = f32x2{s[kt][2], s[kt][3]} * sc2 + f32x2{bv[2], bv[3]};
+      s[kt] = f32x4{lo[0], lo[1], hi[0], hi[1]};
+      if (wtype) {  // SW-MSA window on the last row / column: keys of another region
+        const unsigned x = kc[kt] ^ cq;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if ((x >> (8 * j)) & 3u) s[kt][j] = NEG;
+      }
+    }
+    float mx = NEG;
+#pragma unroll
+    for (int kt = 0; kt < 9; ++kt)
+      mx = fmaxf(mx, fmaxf(fmaxf(s[kt][0], s[kt][1]), fmaxf(s[kt][2], s[kt][3])));
+    mx = bfly_max_16_32(mx);
+    float sum = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < 9; ++kt) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[kt][j] = __builtin_amdgcn_exp2f(s[kt][j] - mx);
+      sum += (s[kt][0] + s[kt][1]) + (s[kt][2] + s[kt][3]);
+    }
+    sum = bfly_sum_16_32(sum);
+
+    f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int ks = 0; ks < 5; ++ks) {
+      bf16x8 pf;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        pf[j] = (bf16)s[2 * ks][j];
+        pf[4 + j] = ks < 4 ? (bf16)s[(2 * ks + 1) % 9][j] : (bf16)0.f;  // keys 144 .. 159: P = 0
+      }
+      const int key0 = ks * 32 + 4 * g + tq;  // and key0 + 16: same (row >> 2) & 3 swizzle
+      const int sw = (key0 >> 2) & 3;
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt) {
+        const int chunk = 2 * dt + (tp >> 1);
+        const int off = ((chunk ^ sw) * 16) + (tp & 1) * 8;
+        const i16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((EVT_LDS i16x4*)(Vs + key0 * 64 + off));
+        const i16x4 v1 =
+            __builtin_amdgcn_ds_read_tr16_b64_v4i16((EVT_LDS i16x4*)(Vs + (key0 + 16) * 64 + off));
+        const i16x8 vv = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
+        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vv), pf, o[dt],
+                                                        0, 0, 0);
+      }
+    }
+    // o[dt][j] = O^T[d = 16 dt + 4 g + j][query q]
+    const float inv = __builtin_amdgcn_rcpf(sum);
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) {
+      const f32x4 v = o[dt] * inv;
+      const bf16x4 ob = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
+      buffer_store_b64<0>(__builtin_bit_cast(u32x2, ob), ro, qoff[n], 32 * dt);
+    }
+    if (h == 0)  // pad columns [C, ldo) of the attention output (the proj GEMM's K padding)
+      for (int c = p.C + 4 * g; c < p.ldo; c += 16)
+        buffer_store_b64<0>(u32x2{0u, 0u}, ro, qoff[n] + (c - 4 * g) * 2, 0);
+  }
+}
+
+// fp32 window attention for 12 x 12 windows (parity path): block = 3 waves = one (image, window,
+// head), thread = query (144 of 192); K / V and the compact bias table in LDS. A query's 144
+// scores do not fit its registers beside q and o, so the scores are computed twice: once for the
+// row maximum, once for exp2, the sum and P . V (the same expression, so the same bits). The
+// SW-MSA mask is the reference's -100 on keys of another region.
+__global__ __launch_bounds__(192) void window12_attn_f32_kernel(SwinAttnParams p) {
+  __shared__ float Ks[144][33];
+  __shared__ float Vs[144][33];
+  __shared__ float Ts[RPB12_CROW];
+  const int tid = threadIdx.x;
+  const int64_t pair = blockIdx.x;
+  const int nw = p.nwx * p.nwx;
+  const int h = (int)(pair % p.H);
+  const int64_t bw = pair / p.H;
+  const int win = (int)(bw % nw), b = (int)(bw / nw);
+  const int R = p.R, s0 = p.shift;
+  const int wy = win / p.nwx, wx = win - wy * p.nwx;
+  const int wtype = s0 ? (wy == p.nwx - 1 ? 2 : 0) + (wx == p.nwx - 1 ? 1 : 0) : 0;
+  const int64_t base = (int64_t)b * R * R;
+  auto row = [&](int t) {
+    const int i = t / 12, j = t - 12 * i;
+    int y = wy * 12 + s0 + i, x = wx * 12 + s0 + j;
+    if (y >= R) y -= R;
+    if (x >= R) x -= R;
+    return base + (y * R + x);
+  };
+  const float* qkv = (const float*)p.qkv;
+  for (int e = tid; e < 144 * 32; e += 192) {
+    const int t = e >> 5, d = e & 31;
+    const float* rp = qkv + row(t) * p.ldq + h * 32 + d;
+    Ks[t][d] = rp[p.C];
+    Vs[t][d] = rp[2 * p.C];
+  }
+  for (int e = tid; e < RPB12_CROW; e += 192) Ts[e] = p.bias[h * RPB12_CROW + e];
+  __syncthreads();
+  if (tid >= 144) return;
+  const int t = tid, qi = t / 12, qj = t - 12 * qi;
+  const int64_t qrow = row(t);
+  float q[32];
+#pragma unroll
+  for (int d = 0; d < 32; ++d) q[d] = qkv[qrow * p.ldq + h * 32 + d];
+  const int cut = 12 - s0;
+  const bool lr_ = wtype & 2, lc_ = wtype & 1;
+  const int cq = (lr_ && qi >= cut ? 1 : 0) | (lc_ && qj >= cut ? 2 : 0);
+  const float* Tq = Ts + (11 * qi + t + 264);
+  auto score = [&](int k, int ki, int kj) {
+    float a = 0.f;
+#pragma unroll
+    for (int d = 0; d < 32; ++d) a += q[d] * Ks[k][d];
+    float v = a * p.scale_log2 + Tq[-(11 * ki + k)];
+    const int ck = (lr_ && ki >= cut ? 1 : 0) | (lc_ && kj >= cut ? 2 : 0);
+    if (ck != cq) v += -100.0f * kLog2e;
+    return v;
+  };
+  float mx = -INFINITY;
+#pragma unroll 1
+  for (int ki = 0, k = 0; ki < 12; ++ki)
+#pragma unroll 2
+    for (int kj = 0; kj < 12; ++kj, ++k) mx = fmaxf(mx, score(k, ki, kj));
+  float sum = 0.f;
+  float o[32];
+#pragma unroll
+  for (int d = 0; d < 32; ++d) o[d] = 0.f;
+#pragma unroll 1
+  for (int ki = 0, k = 0; ki < 12; ++ki)
+#pragma unroll 2
+    for (int kj = 0; kj < 12; ++kj, ++k) {
+      const float e = exp2f(score(k, ki, kj) - mx);
+      sum += e;
+#pragma unroll
+      for (int d = 0; d < 32; ++d) o[d] += e * Vs[k][d];
+    }
+  float* op = (float*)p.out + qrow * p.ldo;
+  const float inv = 1.0f / sum;
+#pragma unroll
+  for (int d = 0; d < 32; ++d) op[h * 32 + d] = o[d] * inv;
+  if (h == 0)
+    for (int c = p.C; c < p.ldo; ++c) op[c] = 0.f;
+}
+
 // ---- final LayerNorm + token mean: one block per image -------------------------------------
+// More than 256 tokens in the last stage (a single-stage model at R = 24 or 36): the same sums in
+// the same token order, with the per-token coefficients refilled for every 256 tokens.
+template <typename T>
+__global__ __launch_bounds__(256) void ln_pool_long_kernel(const T* __restrict__ x, int64_t ldx,
+                                                           int T_, int D,
+                                                           const float* __restrict__ stats,
+                                                           int nslots,
+                                                           const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta,
+                                                           float eps, T* __restrict__ out,
+                                                           int64_t ldo) {
+  __shared__ float coef[256][2];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float inv_d = 1.0f / (float)D;
+  const T* xb = x + (int64_t)b * T_ * ldx;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};  // columns tid + 256 i (ldo <= 1024: checked at launch)
+  for (int t0 = 0; t0 < T_; t0 += 256) {
+    const int nt = min(256, T_ - t0);
+    __syncthreads();
+    if (tid < nt) {
+      const float* st = stats + 2 * (int64_t)nslots * ((int64_t)b * T_ + t0 + tid);
+      float s1 = 0.f, s2 = 0.f;
+      for (int j = 0; j < nslots; ++j) {
+        s1 += st[2 * j];
+        s2 += st[2 * j + 1];
+      }
+      const float mu = s1 * inv_d;
+      coef[tid][0] = mu;
+      coef[tid][1] = rsqrtf(fmaxf(s2 * inv_d - mu * mu, 0.f) + eps);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = tid + 256 * i;
+      if (c < D)
+        for (int t = 0; t < nt; ++t)
+          acc[i] += (to_f32(xb[(int64_t)(t0 + t) * ldx + c]) - coef[t][0]) * coef[t][1];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int c = tid + 256 * i;
+    if (c < ldo)
+      out[(int64_t)b * ldo + c] =
+          from_f32<T>(c < D ? acc[i] / (float)T_ * gamma[c] + beta[c] : 0.f);
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void ln_pool_kernel(const T* __restrict__ x, int64_t ldx, int T_,
                                                       int D, const float* __restrict__ stats,
@@ -1239,6 +1585,11 @@ hipError_t merge_launch(int dtype, const void* x, int64_t ldx, int B, int R, int
 
 hipError_t rpb_dense_launch(const float* table, int H, int w, int shift, float* dense,
                             hipStream_t s) {
+  if (w == 12) {  // the compact per-head tables are all the w = 12 kernels read
+    hipLaunchKernelGGL(rpb12_kernel, dim3((H * RPB12_CROW + 255) / 256), dim3(256), 0, s, table, H,
+                       dense);
+    return hipGetLastError();
+  }
   const int n = (shift ? 4 : 1) * H * w * w * 64;
   hipLaunchKernelGGL(rpb_dense_kernel, dim3((n + 255) / 256), dim3(256), 0, s, table, H, w, shift,
                      dense);
@@ -1249,6 +1600,7 @@ hipError_t rpb_dense_launch(const float* table, int H, int w, int shift, float* 
 }
 
 size_t rpb_table_floats(int H, int w, int shift) {
+  if (w == 12) return (size_t)H * RPB12_CROW;
   return (size_t)(shift ? 4 : 1) * H * w * w * 64 + (size_t)H * RPB_CROW;
 }
 
@@ -1267,6 +1619,23 @@ hipError_t window_attn_launch(int dtype, const SwinAttnParams& p, hipStream_t s)
     hipLaunchKernelGGL(window_attn_bf16_kernel, grid, dim3(256), 0, s, p);
   else
     hipLaunchKernelGGL(window_attn_f32_kernel, grid, dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+hipError_t window12_attn_launch(int dtype, const SwinAttnParams& p, hipStream_t s) {
+  if (p.B <= 0) return hipSuccess;
+  if (p.R % 12 || p.nwx * 12 != p.R || p.C != p.H * 32 || p.ldo < p.C || p.shift < 0 ||
+      p.shift >= 12 || (p.ldq % 8) || (p.ldo % 4))
+    return hipErrorInvalidValue;
+  // one block per (image, window, head); the bf16 kernel forms 32-bit byte offsets per image
+  const int64_t pairs = (int64_t)p.B * p.nwx * p.nwx * p.H;
+  if (pairs >= (int64_t)1 << 31 ||
+      (dtype == DT_BF16 && (int64_t)p.R * p.R * std::max(p.ldq, p.ldo) * 2 >= (int64_t)1 << 31))
+    return hipErrorInvalidValue;
+  if (dtype == DT_BF16)
+    hipLaunchKernelGGL(window12_attn_bf16_kernel, dim3((unsigned)pairs), dim3(192), 0, s, p);
+  else
+    hipLaunchKernelGGL(window12_attn_f32_kernel, dim3((unsigned)pairs), dim3(192), 0, s, p);
   return hipGetLastError();
 }
 
@@ -1338,7 +1707,17 @@ hipError_t ln_pool_launch(int dtype, const void* x, int64_t ldx, int B, int T, i
                           const float* stats, int nslots, const float* gamma, const float* beta,
                           void* out, int64_t ldo, hipStream_t s) {
   if (B <= 0) return hipSuccess;
-  if (T <= 0 || T > 256 || D > ldo) return hipErrorInvalidValue;
+  if (T <= 0 || D > ldo) return hipErrorInvalidValue;
+  if (T > 256) {
+    if (ldo > 1024) return hipErrorInvalidValue;
+    if (dtype == DT_BF16)
+      hipLaunchKernelGGL(ln_pool_long_kernel<bf16>, dim3(B), dim3(256), 0, s, (const bf16*)x, ldx,
+                         T, D, stats, nslots, gamma, beta, 1e-5f, (bf16*)out, ldo);
+    else
+      hipLaunchKernelGGL(ln_pool_long_kernel<float>, dim3(B), dim3(256), 0, s, (const float*)x,
+                         ldx, T, D, stats, nslots, gamma, beta, 1e-5f, (float*)out, ldo);
+    return hipGetLastError();
+  }
   if (dtype == DT_BF16)
     hipLaunchKernelGGL(ln_pool_kernel<bf16>, dim3(B), dim3(256), 0, s, (const bf16*)x, ldx, T, D,
                        stats, nslots, gamma, beta, 1e-5f, (bf16*)out, ldo);

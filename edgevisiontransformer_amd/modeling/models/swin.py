@@ -7,16 +7,19 @@ and builds it from `configs/{config_file_name}.yaml`; `tools.py:272-282` benchma
 
     model = get_swin("swin_tiny_patch4_window7_224", dtype="bf16")  # reference utils.py:14
     logits = model(img)                                             # SwinTransformer.forward
+    model = get_swin("swin_base_patch4_window12_384", dtype="bf16")  # the 384 px configurations
 
 `SwinTransformer(...)` takes the constructor keywords get_swin passes (utils.py:28-43). The yaml
 files are not available offline, so the three published configs are built in
-(`edgevisiontransformer_amd.weights.SWIN_VARIANTS`); `swin_root_path` is accepted and ignored.
+(`edgevisiontransformer_amd.weights.SWIN_VARIANTS`), each at window 7 / 224 px and at window 12 /
+384 px; `swin_root_path` is accepted and ignored.
 The forward is one call into libevt_hip.so (`evt_swin_forward`, include/evt.h). Deliberate
 differences: `seed=` / `weights=` select the parameters (Keras [in, out] dict, or
 `params_from_state_dict` of a microsoft checkpoint), `dtype` selects bf16 MFMA or exact fp32;
 inference only (dropout / drop-path are identity, as in eval mode). Unsupported options raise
-ValueError: window_size != 7, head size != 32, ape=True, patch_norm=False, qkv_bias=False,
-qk_scale != None, stage resolutions that are not multiples of 7.
+ValueError: window_size other than 7 or 12, head size != 32, ape=True, patch_norm=False,
+qkv_bias=False, qk_scale != None, a stage whose window (min(window_size, resolution), the
+reference's clamp) is not 7 or 12 or does not divide its resolution.
 """
 from __future__ import annotations
 
@@ -42,8 +45,8 @@ class SwinTransformer:
                  patch_norm=True, use_checkpoint=False, *, dtype: str = "bf16", seed: int = 0,
                  weights: Optional[Dict[str, np.ndarray]] = None, device=None,
                  max_batch: int = 0, lanes: Optional[int] = None):
-        if window_size != 7:
-            raise ValueError("window_size must be 7 in this build")
+        if window_size not in (7, 12):
+            raise ValueError("window_size must be 7 or 12 in this build")
         if ape or not patch_norm or not qkv_bias or qk_scale is not None:
             raise ValueError("this build supports ape=False, patch_norm=True, qkv_bias=True, "
                              "qk_scale=None (the published Swin configs)")
@@ -57,8 +60,10 @@ class SwinTransformer:
         for i in range(self.cfg.num_stages):
             if self.cfg.dim(i) % num_heads[i] or self.cfg.dim(i) // num_heads[i] != 32:
                 raise ValueError(f"stage {i}: head size {self.cfg.dim(i)}/{num_heads[i]} must be 32")
-            if self.cfg.res(i) % 7 or self.cfg.res(i) < 7:
-                raise ValueError(f"stage {i}: resolution {self.cfg.res(i)} is not a multiple of 7")
+            w = self.cfg.window(i)
+            if w not in (7, 12) or self.cfg.res(i) % w:
+                raise ValueError(f"stage {i}: resolution {self.cfg.res(i)} is not a multiple of "
+                                 f"{window_size} (window {w}; windows are 7 or 12)")
         self.num_classes = num_classes
         self.num_features = self.cfg.num_features
         if dtype not in _lib.DTYPE:
@@ -174,7 +179,8 @@ _CONFIG_RE = re.compile(r"swin_(tiny|small|base)_patch(\d+)_window(\d+)_(\d+)$")
 
 
 def swin_config_from_name(config_file_name: str, num_classes: int = 1000) -> SwinConfig:
-    """The SwinConfig of a microsoft config name (configs/swin_{tiny,small,base}_patch4_window7_224)."""
+    """The SwinConfig of a microsoft config name (configs/swin_{tiny,small,base}_patch4_window7_224
+    or _window12_384)."""
     m = _CONFIG_RE.match(config_file_name)
     if not m:
         raise NotImplementedError(f"Unkown model: {config_file_name}")  # utils.py:45 wording

@@ -26,6 +26,7 @@ from __future__ import annotations
 
 import argparse
 import os
+import re
 import sys
 import timeit
 from typing import List, Optional
@@ -41,15 +42,18 @@ def build_model(name: str, compute_dtype: str, prune_encoding: Optional[str] = N
                 max_batch: int = 1, seed: int = 0, image_size: int = 224):
     """A model by reference name (deit_*, t2t_vit_*, swin_*), optionally head/FFN pruned.
     image_size: the input resolution (reference utils.py:52-62 loads 224 and 384 px DeiT; any size
-    the library takes works for DeiT and T2T-ViT; the named Swin configs are 224 px only)."""
+    the library takes works for DeiT and T2T-ViT; a full Swin config name carries its own size,
+    e.g. swin_base_patch4_window12_384, the short names swin_tiny|small|base are 224 px)."""
     kw = {} if image_size == 224 else {"image_size": image_size}
-    if name in SWIN_NAMED or name.startswith("swin_") and name.endswith("_224"):
+    full_swin = re.match(r"swin_.*_(\d+)$", name)
+    if name in SWIN_NAMED or full_swin:
         if prune_encoding:
             raise ValueError("prune_encoding applies to DeiT models only")
-        if image_size != 224:
-            raise ValueError(f"{name} is a 224 px configuration; got image size {image_size}")
+        size = int(full_swin.group(1)) if full_swin else 224
+        if image_size != size:
+            raise ValueError(f"{name} is a {size} px configuration; got image size {image_size}")
         from .modeling.models.swin import get_swin
-        cfg_name = name if name.endswith("_224") else f"{name}_patch4_window7_224"
+        cfg_name = name if full_swin else f"{name}_patch4_window7_224"
         return get_swin(cfg_name, dtype=compute_dtype, seed=seed, max_batch=max_batch)
     if name in T2T_NAMED:
         if prune_encoding:

@@ -347,8 +347,13 @@ int64_t evt_performer_scratch(int B, int T);
 /* Static shape of a SwinTransformer(img_size, patch_size, in_chans, num_classes, embed_dim, depths,
  * num_heads, window_size, mlp_ratio, qkv_bias=True, ape=False, patch_norm=True) as get_swin builds
  * it (utils.py:28-43; swin_tiny_patch4_window7_224 = embed 96, depths (2,2,6,2), heads
- * (3,6,12,24)). This build: window 7, head size 32 (stage width / heads), every stage resolution
- * a multiple of 7 (no padding), stage width <= 1024. */
+ * (3,6,12,24); swin_base_patch4_window12_384 = embed 128, depths (2,2,18,2), heads (4,8,16,32),
+ * window 12 at 384 px). This build: window_size 7 or 12, head size 32 (stage width / heads), stage
+ * width <= 1024. A stage's window is min(window_size, its resolution) and must itself be 7 or 12,
+ * with the stage resolution a multiple of it (no padding); a stage no larger than window_size is
+ * one unshifted window, the others shift by window_size / 2 on odd blocks. Past 56 x 56 tokens
+ * per image max_batch is limited so that every activation buffer stays below 2^31 bytes
+ * (EVT_EINVAL otherwise; Swin-B at 384 px: 227 images in bf16). */
 typedef struct evt_swin_desc {
   int32_t image_size;   /* 224 */
   int32_t patch_size;   /* 4 */
@@ -358,7 +363,7 @@ typedef struct evt_swin_desc {
   int32_t num_stages;   /* len(depths), <= EVT_SWIN_MAX_STAGES */
   int32_t depths[EVT_SWIN_MAX_STAGES];
   int32_t num_heads[EVT_SWIN_MAX_STAGES];
-  int32_t window_size;  /* 7 */
+  int32_t window_size;  /* 7 or 12 */
   float mlp_ratio;      /* 4.0: MLP width int(C * mlp_ratio) */
   int32_t dtype;        /* EVT_DTYPE_* */
   int32_t max_batch;
@@ -390,7 +395,9 @@ int evt_swin_query_workspace(const evt_swin_desc* desc, int batch, size_t* bytes
  * cyclic shift / window partition / reverse around it): qkv [B*R*R, ldq] raster-order token rows
  * with columns (qkv h d) (the qkv Linear output incl. bias), head size 32, window 7, cyclic shift
  * `shift` (0 = W-MSA; else SW-MSA with the -100 region mask) -> out [B*R*R, ldo] raster rows,
- * columns (h d), columns [C, ldo) set to 0. rpb = relative_position_bias_table [169, H]. */
+ * columns (h d), columns [C, ldo) set to 0. rpb = relative_position_bias_table [169, H].
+ * This op is the window-7 core only (R a multiple of 7): the window-12 kernels of the 384 px
+ * configurations are reached through evt_swin_create / evt_swin_forward. */
 int evt_window_attention(int dtype, const void* qkv, int64_t ldq, void* out, int64_t ldo,
                          const float* rpb, int B, int R, int C, int H, int shift, void* stream);
 
