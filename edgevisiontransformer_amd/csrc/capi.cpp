@@ -798,7 +798,7 @@ int validate_swin(const evt_swin_desc* d, SwinGeo* g) {
                                   std::to_string(d->window_size) + ") and its window 7 or 12");
     g->w[i] = win;
     const int C = d->embed_dim << i;
-    if (C > 1024) return fail(EVT_EINVAL, "stage width must be <= 1024");
+    if (C > 1536) return fail(EVT_EINVAL, "stage width must be <= 1536");
     if (d->depths[i] < 0) return fail(EVT_EINVAL, "depths must be >= 0");
     if (d->num_heads[i] <= 0 || C % d->num_heads[i] || C / d->num_heads[i] != 32)
       return fail(EVT_EINVAL, "head size (stage width / num_heads) must be 32 in this build");
@@ -813,11 +813,13 @@ int validate_swin(const evt_swin_desc* d, SwinGeo* g) {
     if (g->mlp[i] <= 0) return fail(EVT_EINVAL, "mlp width must be positive");
     g->mst[i] = (int)round_up(g->mlp[i], PAD_N);
   }
-  if (g->R[0] * g->R[0] > 3136) {
+  if (g->R[0] * g->R[0] > 3136 || g->C[g->ns - 1] > 1024) {
     // As validate() past 256 tokens: several kernels form byte offsets into an activation buffer
-    // in 32 bits. Up to 56 x 56 tokens (224 px) the supported batches are as they were; past
-    // them a max_batch whose largest buffer (image batch, patch matrix, qkv, MLP hidden, merge
-    // gather, row statistics) would reach 2^31 bytes is refused.
+    // in 32 bits. Up to 56 x 56 tokens (224 px) and stage widths of 1024 the supported batches are
+    // as they were; past either a max_batch whose largest buffer (image batch, patch matrix, qkv,
+    // MLP hidden, merge gather, row statistics) would reach 2^31 bytes is refused. A model with a
+    // stage wider than 1024 has wider rows at every resolution: Swin-L at 224 px holds
+    // 3136 x 768 elements per image in its MLP hidden, 2^31 bytes at 446 bf16 / 223 f32 images.
     const size_t es = d->dtype == EVT_DTYPE_F32 ? 4 : 2, B = (size_t)d->max_batch;
     size_t big = B * d->in_chans * d->image_size * d->image_size * sizeof(float);
     big = std::max(big, B * g->R[0] * g->R[0] * g->pdst * es);
@@ -828,8 +830,8 @@ int validate_swin(const evt_swin_desc* d, SwinGeo* g) {
       big = std::max({big, rows * widest * es, rows * stats_slots(g->C[i]) * 2 * sizeof(float)});
     }
     if (big >= (size_t)1 << 31)
-      return fail(EVT_EINVAL, "max_batch too large for more than 3136 tokens per image: every "
-                              "activation buffer must stay below 2^31 bytes");
+      return fail(EVT_EINVAL, "max_batch too large for more than 3136 tokens per image or a stage "
+                              "wider than 1024: every activation buffer must stay below 2^31 bytes");
   }
   return EVT_OK;
 }

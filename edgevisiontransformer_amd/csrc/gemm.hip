@@ -997,15 +997,18 @@ __device__ __forceinline__ void big8_kt(const P& p, char* smem,
 // last: issues LX further VMEM loads per wave just before the last K-tile (added to its waits:
 // they are younger than every DMA that tile waits for); last3: LX3 more at the start of the last
 // K-tile's phase 3.
+// after: called with t after every steady-state K-tile t (1 <= t <= nk - 3); the persistent
+// kernel's wide-row statistics rounds hang on it (pers_run).
 template <int X, bool OPEN = false, typename Pre1 = NoOp, typename Mid = NoOp, int LX = 0,
           typename Last = NoOp, int LX3 = 0, typename Last3 = NoOp, typename P = GemmParams,
-          bool KT2 = false, bool U2 = false>
+          bool KT2 = false, bool U2 = false, typename After = NoOp>
 __device__ __forceinline__ void big8_loop(const P& p, char* smem,
                                           f32x4 (&acc)[GeoOf<P>::NF][GeoOf<P>::MF],
                                           int wave, int lane, int wm, int wn, int m0, int n0,
                                           int nk, bool cont = false, int nm0 = 0, int nn0 = 0,
                                           Pre1 pre1 = {}, Mid mid = {}, Last last = {},
-                                          Last3 last3 = {}, int par = 0) {
+                                          Last3 last3 = {}, int par = 0, After after = {}) {
+  constexpr bool AFTER = !std::is_same<After, NoOp>::value;
   // K-tile t of this tile sits in buffer (t ^ par) & 1; the next tile (cont) starts at the parity
   // of stream K-tile nk
   const int npar = par ^ (nk & 1);
@@ -1034,11 +1037,15 @@ __device__ __forceinline__ void big8_loop(const P& p, char* smem,
     if constexpr (U2) {
       for (; t + 3 < nk; t += 2) {
         big8_kt<KT2, 0, 0>(p, smem, acc, wave, lane, wm, wn, m0, n0, t, false, 0, 0, {}, par, 0);
+        if constexpr (AFTER) after(t);
         big8_kt<KT2, 0, 0>(p, smem, acc, wave, lane, wm, wn, m0, n0, t + 1, false, 0, 0, {}, par, 0);
+        if constexpr (AFTER) after(t + 1);
       }
     }
-    for (; t + 2 < nk; ++t)
+    for (; t + 2 < nk; ++t) {
       big8_kt<KT2, 0, 0>(p, smem, acc, wave, lane, wm, wn, m0, n0, t, false, 0, 0, {}, par, 0);
+      if constexpr (AFTER) after(t);
+    }
     big8_kt<KT2, 1, 0>(p, smem, acc, wave, lane, wm, wn, m0, n0, t, cont, nm0, nn0, {}, par, npar);
     last();
     big8_kt<KT2, 2, LX, OPEN, LX3>(p, smem, acc, wave, lane, wm, wn, m0, n0, t + 1, cont, nm0, nn0,
@@ -1199,6 +1206,19 @@ constexpr int PERS_PART = PERS_COLB + 3072;     // odd-wn waves' row partials [2
 constexpr int PERS_LDS = PERS_PART + 4096;
 constexpr int PERS_LDS_ALL = PERS_LDS + 16;
 constexpr int PERS_X = 16;                      // output stores per wave per interior tile
+// Wide LayerNorm rows (10 or 12 statistics slots, widths 1025..1536: the WIDE instantiations):
+// PERS_RAW holds 8 slots per row, so the statistics are staged in two DMA rounds. Round 0 (slots
+// 0..7, after K-tile 0 of the previous tile, where the one-round DMA sits) is summed per row in
+// slot order into PERS_ACC after K-tile 2; round 1 (slots 8.., [256][nslots - 8] at PERS_RAW)
+// is issued after K-tile 3, and the next tile's coefficients continue the sums from PERS_ACC in
+// the same slot order, so (s1, s2) are the sequential sums ln_coef forms. Both rounds are
+// followed by whole steady-state K-tiles (nk >= 8, use_pers): every counted wait of those K-tiles
+// leaves at most 8 DMAs in flight per wave, all younger, and they add VMEM instructions only where
+// X = 0 (waits there get stricter, never weaker); the first K-tile's X is unchanged.
+constexpr int PERS_ACC = PERS_LDS_ALL;          // partial (s1, s2) of slots 0..7 [256] f32x2
+constexpr int PERS_LDS_WIDE = PERS_ACC + 2048;
+constexpr int PERS_WIDE_MIN_NK = 8;
+static_assert(PERS_LDS_WIDE <= 160 * 1024, "LDS of one workgroup");
 
 template <int FL>
 struct PersFlags {
@@ -1217,12 +1237,25 @@ struct PersFlags {
 };
 
 // DMA the tile's LN statistics rows and column vectors into LDS (before its prologue DMAs).
-template <int FL>
+// WIDE: round 0 = slots 0..7 of every row ([256][8], the one-round image) and the column vectors,
+// round 1 = slots 8..nslots-1 ([256][nslots - 8]).
+template <int FL, bool WIDE = false>
 __device__ __forceinline__ void pers_coop_dma(const GemmParams& p, char* smem, int wave, int lane,
-                                              int m0, int n0) {
+                                              int m0, int n0, int round = 0) {
   typedef PersFlags<FL> F;
   asm volatile("" : "+v"(lane));
-  if constexpr (F::ln) {
+  if constexpr (F::ln && WIDE) {
+    const float* st = (FL & EPI_LNIN) ? p.stats_in : p.rstats;
+    const int cpr = round ? (p.nslots >> 1) - 4 : 4;  // 16-B chunks per row in this round: 1, 2 / 4
+    const int nch = 256 * cpr;
+    for (int c = wave * 64; c < nch; c += 512) {
+      const int cl = c + lane, r = cpr == 4 ? cl >> 2 : (cpr == 2 ? cl >> 1 : cl), q = cl - r * cpr;
+      const int64_t row = min(m0 + r, p.M - 1);
+      glds16(st + row * (2 * p.nslots) + (round ? 16 : 0) + 4 * q,
+             (EVT_LDS char*)smem + PERS_RAW + c * 16);
+    }
+    if (round) return;
+  } else if constexpr (F::ln) {
     const float* st = (FL & EPI_LNIN) ? p.stats_in : p.rstats;
     const int half = p.nslots >> 1;  // 16-B chunks per row
     const int nch = 256 * half;
@@ -1238,16 +1271,40 @@ __device__ __forceinline__ void pers_coop_dma(const GemmParams& p, char* smem, i
   if (v) glds16(v + min(n0 + 4 * lane, p.N - 4), (EVT_LDS char*)smem + PERS_COLRAW + wave * 1024);
 }
 
+// WIDE: (s1, s2) over the staged slots 0..7 of every tile row, in slot order, into PERS_ACC
+// (threads 0..255); the reads are retired on return, so a barrier later round 1 may overwrite them.
+__device__ __forceinline__ void pers_wide_reduce(char* smem, int tid) {
+  asm volatile("" : "+v"(tid));
+  if (tid < 256) {
+    const EVT_LDS f32x2* st = (const EVT_LDS f32x2*)(smem + PERS_RAW) + tid * 8;
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const f32x2 v = st[j];
+      s1 += v[0];
+      s2 += v[1];
+    }
+    ((EVT_LDS f32x2*)(smem + PERS_ACC))[tid] = f32x2{s1, s2};
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
 // Per-row LayerNorm coefficients (as ln_coef) and a copy of the column vectors for the epilogue.
-template <int FL>
+template <int FL, bool WIDE = false>
 __device__ __forceinline__ void pers_coef(const GemmParams& p, char* smem, int tid) {
   typedef PersFlags<FL> F;
   asm volatile("" : "+v"(tid));
   if (tid < 256) {
     if constexpr (F::ln) {
-      const EVT_LDS f32x2* st = (const EVT_LDS f32x2*)(smem + PERS_RAW) + tid * p.nslots;
+      const int ns = WIDE ? p.nslots - 8 : p.nslots;
+      const EVT_LDS f32x2* st = (const EVT_LDS f32x2*)(smem + PERS_RAW) + tid * ns;
       float s1 = 0.f, s2 = 0.f;
-      for (int j = 0; j < p.nslots; ++j) {
+      if constexpr (WIDE) {  // slots 0..7 summed by pers_wide_reduce; 8.. continue the same chain
+        const f32x2 a = ((const EVT_LDS f32x2*)(smem + PERS_ACC))[tid];
+        s1 = a[0];
+        s2 = a[1];
+      }
+      for (int j = 0; j < ns; ++j) {
         const f32x2 v = st[j];
         s1 += v[0];
         s2 += v[1];
@@ -1849,7 +1906,7 @@ __device__ __forceinline__ bool pers_tile(int t, int G, int ntiles, int xgroups,
 }
 
 // The persistent tile walk of one GEMM from logical tile `tile` in steps of gridDim.x.
-template <int FL, int DBG, bool PADN, typename P = GemmParams>
+template <int FL, int DBG, bool PADN, typename P = GemmParams, bool WIDE = false>
 __device__ __forceinline__ void pers_run(const P& p, int total, int tile, char* smem) {
   // a quarter of the residual before the last K-tile (out-proj 160 -> 153 us); DBG 20: A/B without
   constexpr int ER = ((FL & EPI_RESID) != 0 && DBG != 7 && DBG != 20 && DBG != 18)
@@ -1876,7 +1933,14 @@ __device__ __forceinline__ void pers_run(const P& p, int total, int tile, char* 
     const int q = (blockIdx.x >> 3) & 3;
     for (int i = 0; i < q * nk; ++i) __builtin_amdgcn_s_sleep(20);
   }
-  pers_coop_dma<FL>(p, smem, wave, lane, tm * BIG_BM, tn * BIG_BN);
+  pers_coop_dma<FL, WIDE>(p, smem, wave, lane, tm * BIG_BM, tn * BIG_BN);
+  if constexpr (WIDE) {  // the first tile's two statistics rounds, drained one after the other
+    wait_vmcnt0();
+    big8_bar();
+    pers_wide_reduce(smem, tid);
+    big8_bar();
+    pers_coop_dma<FL, WIDE>(p, smem, wave, lane, tm * BIG_BM, tn * BIG_BN, 1);
+  }
   big8_prologue(p, smem, wave, lane, tm * BIG_BM, tn * BIG_BN, nk);
   wait_vmcnt0();  // the first K-tile's waits assume PERS_X younger VMEM ops or a drain
   int par = 0;    // buffer parity of this tile's K-tile 0 (the stream alternates it for odd nk)
@@ -1916,11 +1980,24 @@ __device__ __forceinline__ void pers_run(const P& p, int total, int tile, char* 
       // this tile's LayerNorm coefficients by wave group 1 while it waits for group 0's first
       // phase; the next tile's statistics rows / column vectors DMA'd after K-tile 0 (PERS_RAW is
       // free once those coefficients are read: every later phase retires group 1's LDS ops)
-      auto pre1 = [&]() { pers_coef<FL>(p, smem, tid - 256); };
+      auto pre1 = [&]() { pers_coef<FL, WIDE>(p, smem, tid - 256); };
       auto mid = [&]() {
-        if (has_next) pers_coop_dma<FL>(p, smem, wave, lane, ntm * BIG_BM, ntn * BIG_BN);
+        if (has_next) pers_coop_dma<FL, WIDE>(p, smem, wave, lane, ntm * BIG_BM, ntn * BIG_BN);
       };
-      if constexpr (DBG == 18)  // A/B: groups re-synchronised before the epilogue
+      // WIDE (nk >= PERS_WIDE_MIN_NK): round 0 (mid) has landed in every wave once K-tile 1's
+      // waits and K-tile 2's barriers are past; its sums leave PERS_RAW free a K-tile before
+      // round 1 overwrites it (the comment at PERS_ACC)
+      auto after = [&](int t) {
+        if (!has_next) return;
+        if (t == 2) pers_wide_reduce(smem, tid);
+        if (t == 3) pers_coop_dma<FL, WIDE>(p, smem, wave, lane, ntm * BIG_BM, ntn * BIG_BN, 1);
+      };
+      if constexpr (WIDE)
+        big8_loop<PERS_X, true, decltype(pre1), decltype(mid), (ER > 0 ? 4 : 0), decltype(last),
+                  (ER > 1 ? 4 : 0), decltype(last3), P, KT2, U2, decltype(after)>(
+            p, smem, acc, wave, ln, wm, wn, m0, n0, nk, cont, ntm * BIG_BM, ntn * BIG_BN, pre1, mid,
+            last, last3, par, after);
+      else if constexpr (DBG == 18)  // A/B: groups re-synchronised before the epilogue
         big8_loop<PERS_X>(p, smem, acc, wave, ln, wm, wn, m0, n0, nk, cont, ntm * BIG_BM,
                           ntn * BIG_BN, pre1, mid, {}, {}, par);
       else
@@ -1963,9 +2040,9 @@ __device__ __forceinline__ void pers_run(const P& p, int total, int tile, char* 
   }
 }
 
-template <int FL, int DBG = 0, bool PADN = true>
+template <int FL, int DBG = 0, bool PADN = true, bool WIDE = false>
 __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmParams p, int total) {
-  __shared__ __attribute__((aligned(16))) char smem[PERS_LDS_ALL];
+  __shared__ __attribute__((aligned(16))) char smem[WIDE ? PERS_LDS_WIDE : PERS_LDS_ALL];
   const int G = gridDim.x;  // XCD-aware order when a multiple of 8
   const int tile = (G & 7) ? (int)blockIdx.x : (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
   {
@@ -1975,13 +2052,13 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmParams p, int tot
   if constexpr ((FL & EPI_GATHER) != 0) {
     MergeParams q;
     static_cast<GemmParams&>(q) = p;
-    pers_run<FL, DBG, PADN>(q, total, tile, smem);
+    pers_run<FL, DBG, PADN, MergeParams, WIDE>(q, total, tile, smem);
   } else if constexpr ((FL & EPI_SPLIT) != 0) {
     UnfoldParams q;
     static_cast<GemmParams&>(q) = p;
-    pers_run<FL, DBG, PADN>(q, total, tile, smem);
+    pers_run<FL, DBG, PADN, UnfoldParams, WIDE>(q, total, tile, smem);
   } else {
-    pers_run<FL, DBG, PADN>(p, total, tile, smem);
+    pers_run<FL, DBG, PADN, GemmParams, WIDE>(p, total, tile, smem);
   }
 }
 
@@ -2549,7 +2626,8 @@ constexpr bool pers_fl(int fl) {
          fl == (EPI_LNIN | EPI_BIAS | EPI_HM);
 }
 
-// persistent kernel: supported epilogue, 8-column output groups, LN rows of <= 8 slots
+// persistent kernel: supported epilogue, 8-column output groups, LN rows of <= 8 slots (10 / 12:
+// pers_wide)
 bool gemm_lab_pers_variant(int v) {
 #ifdef EVT_GEMM_LAB
   return v == 10 || v == 11 || v == 13 || v == 15 || (v >= 17 && v <= 25);
@@ -2559,6 +2637,19 @@ bool gemm_lab_pers_variant(int v) {
 #endif
 }
 
+// LayerNorm rows of 10 / 12 statistics slots (widths 1025..1536): the WIDE instantiations of the
+// persistent kernel (two statistics rounds, the comment at PERS_ACC), for the epilogues that meet
+// such rows (Swin-L's 1536-wide stage and evt_dense); not the T2T / head-major ViT ones
+constexpr bool pers_wide_fl(int fl) {
+  return fl == (EPI_LNIN | EPI_BIAS) || fl == (EPI_LNIN | EPI_BIAS | EPI_GELU) ||
+         fl == (EPI_LNIN | EPI_BIAS | EPI_GELU_ERF) || fl == (EPI_LNIN | EPI_BIAS | EPI_STATS) ||
+         fl == (EPI_LNIN | EPI_BIAS | EPI_STATS | EPI_GATHER) ||
+         fl == (EPI_BIAS | EPI_RESID | EPI_RESLN | EPI_STATS);
+}
+bool pers_wide(const GemmParams& p, int flags) {
+  return (flags & (EPI_LNIN | EPI_RESLN)) && p.nslots > 8;
+}
+
 bool use_pers(const GemmParams& p, int flags) {
   const int v = g_gemm_variant;
   if (v != 0 && v != 9 && v != 16 && v != 31 && v != 36 && !gemm_lab_pers_variant(v))
@@ -2566,7 +2657,12 @@ bool use_pers(const GemmParams& p, int flags) {
   // timeline variants stamp s_memtime through p.pos: never on the patch GEMM (p.pos = the table)
   if ((v == 13 || v == 15) && (flags & EPI_POS)) return false;
   if (p.N % 8 || p.vec_ok < 2) return false;
-  if ((flags & (EPI_LNIN | EPI_RESLN)) && (p.nslots > 8 || p.nslots % 2 || p.stats_step > 1))
+  if ((flags & (EPI_LNIN | EPI_RESLN)) && (p.nslots > 12 || p.nslots % 2 || p.stats_step > 1))
+    return false;
+  // 10 / 12 slots: two statistics rounds inside the main loop, which needs its K-tiles
+  // (not under the stream-K or lab variants)
+  if (pers_wide(p, flags) && (!pers_wide_fl(flags) || p.K / 64 < PERS_WIDE_MIN_NK || v == 16 ||
+                              gemm_lab_pers_variant(v)))
     return false;
   // POS: the bf16 copy of the position table rides in resid / ldr (else the staged-epilogue kernel)
   if ((flags & EPI_POS) && (!p.resid || p.ldr % 8 || p.P <= 0 || p.M >= (1 << 22))) return false;
@@ -2605,6 +2701,15 @@ hipError_t launch_pers(const GemmParams& p, hipStream_t s) {
   // block order the 3 went to 3 XCDs: 292 MB fetched per launch for ~100 MB of operands)
   else if (total <= G && (G & 7) && ((G + 7) & ~7) <= max(g_num_cus, 8)) G = (G + 7) & ~7;
   q.xgroups = pers_xgroups(q.ntiles, G, total);
+  if constexpr (pers_wide_fl(FL)) {
+    if (pers_wide(p, FL)) {
+      if (p.N % BIG_BN == 0)
+        hipLaunchKernelGGL((gemm_pers_kernel<FL, 0, false, true>), dim3(G), dim3(512), 0, s, q, total);
+      else
+        hipLaunchKernelGGL((gemm_pers_kernel<FL, 0, true, true>), dim3(G), dim3(512), 0, s, q, total);
+      return hipGetLastError();
+    }
+  }
   if (false) {
   }
 #ifdef EVT_GEMM_LAB

@@ -841,7 +841,8 @@ __global__ __launch_bounds__(192) void window12_attn_f32_kernel(SwinAttnParams p
 // ---- final LayerNorm + token mean: one block per image -------------------------------------
 // More than 256 tokens in the last stage (a single-stage model at R = 24 or 36): the same sums in
 // the same token order, with the per-token coefficients refilled for every 256 tokens.
-template <typename T>
+// NA: accumulator columns per thread (tid + 256 i, i < NA): 4 up to width 1024, 6 up to 1536.
+template <typename T, int NA = 4>
 __global__ __launch_bounds__(256) void ln_pool_long_kernel(const T* __restrict__ x, int64_t ldx,
                                                            int T_, int D,
                                                            const float* __restrict__ stats,
@@ -854,7 +855,9 @@ __global__ __launch_bounds__(256) void ln_pool_long_kernel(const T* __restrict__
   const int b = blockIdx.x, tid = threadIdx.x;
   const float inv_d = 1.0f / (float)D;
   const T* xb = x + (int64_t)b * T_ * ldx;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};  // columns tid + 256 i (ldo <= 1024: checked at launch)
+  float acc[NA];  // columns tid + 256 i (ldo <= 256 NA: checked at launch)
+#pragma unroll
+  for (int i = 0; i < NA; ++i) acc[i] = 0.f;
   for (int t0 = 0; t0 < T_; t0 += 256) {
     const int nt = min(256, T_ - t0);
     __syncthreads();
@@ -871,7 +874,7 @@ __global__ __launch_bounds__(256) void ln_pool_long_kernel(const T* __restrict__
     }
     __syncthreads();
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < NA; ++i) {
       const int c = tid + 256 * i;
       if (c < D)
         for (int t = 0; t < nt; ++t)
@@ -879,7 +882,7 @@ __global__ __launch_bounds__(256) void ln_pool_long_kernel(const T* __restrict__
     }
   }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < NA; ++i) {
     const int c = tid + 256 * i;
     if (c < ldo)
       out[(int64_t)b * ldo + c] =
@@ -1536,7 +1539,8 @@ hipError_t ln_rows_t(const void* x, int64_t ld, void* y, const float* g, const f
     return ln_rows_lc<T, 32, 1>(x, ld, y, g, bb, rows, D, eps, stats, nslots, s);
   if (ld <= 64 * V) return ln_rows_lc<T, 64, 1>(x, ld, y, g, bb, rows, D, eps, stats, nslots, s);
   if (ld <= 128 * V) return ln_rows_lc<T, 64, 2>(x, ld, y, g, bb, rows, D, eps, stats, nslots, s);
-  return ln_rows_lc<T, 64, 4>(x, ld, y, g, bb, rows, D, eps, stats, nslots, s);
+  if (ld <= 256 * V) return ln_rows_lc<T, 64, 4>(x, ld, y, g, bb, rows, D, eps, stats, nslots, s);
+  return ln_rows_lc<T, 64, 6>(x, ld, y, g, bb, rows, D, eps, stats, nslots, s);  // f32, ld <= 1536
 }
 
 }  // namespace
@@ -1561,7 +1565,7 @@ hipError_t ln_rows_launch(int dtype, const void* x, int64_t ld, void* y, const f
                           const float* beta, int rows, int D, float eps, float* stats, int nslots,
                           hipStream_t s) {
   if (rows <= 0) return hipSuccess;
-  if (D <= 0 || D > ld || ld > 1024 || nslots > 64 || ld % (dtype == DT_BF16 ? 8 : 4) ||
+  if (D <= 0 || D > ld || ld > 1536 || nslots > 64 || ld % (dtype == DT_BF16 ? 8 : 4) ||
       D % (dtype == DT_BF16 ? 8 : 4))
     return hipErrorInvalidValue;
   return dtype == DT_BF16 ? ln_rows_t<bf16>(x, ld, y, gamma, beta, rows, D, eps, stats, nslots, s)
@@ -1709,7 +1713,17 @@ hipError_t ln_pool_launch(int dtype, const void* x, int64_t ldx, int B, int T, i
   if (B <= 0) return hipSuccess;
   if (T <= 0 || D > ldo) return hipErrorInvalidValue;
   if (T > 256) {
-    if (ldo > 1024) return hipErrorInvalidValue;
+    if (ldo > 1536) return hipErrorInvalidValue;
+    if (ldo > 1024) {  // the same sums per column, six columns per thread
+      if (dtype == DT_BF16)
+        hipLaunchKernelGGL((ln_pool_long_kernel<bf16, 6>), dim3(B), dim3(256), 0, s, (const bf16*)x,
+                           ldx, T, D, stats, nslots, gamma, beta, 1e-5f, (bf16*)out, ldo);
+      else
+        hipLaunchKernelGGL((ln_pool_long_kernel<float, 6>), dim3(B), dim3(256), 0, s,
+                           (const float*)x, ldx, T, D, stats, nslots, gamma, beta, 1e-5f,
+                           (float*)out, ldo);
+      return hipGetLastError();
+    }
     if (dtype == DT_BF16)
       hipLaunchKernelGGL(ln_pool_long_kernel<bf16>, dim3(B), dim3(256), 0, s, (const bf16*)x, ldx,
                          T, D, stats, nslots, gamma, beta, 1e-5f, (bf16*)out, ldo);

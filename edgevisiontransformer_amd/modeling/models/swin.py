@@ -10,9 +10,10 @@ and builds it from `configs/{config_file_name}.yaml`; `tools.py:272-282` benchma
     model = get_swin("swin_base_patch4_window12_384", dtype="bf16")  # the 384 px configurations
 
 `SwinTransformer(...)` takes the constructor keywords get_swin passes (utils.py:28-43). The yaml
-files are not available offline, so the three published configs are built in
-(`edgevisiontransformer_amd.weights.SWIN_VARIANTS`), each at window 7 / 224 px and at window 12 /
-384 px; `swin_root_path` is accepted and ignored.
+files are not available offline, so the four published configs (tiny, small, base, large) are
+built in (`edgevisiontransformer_amd.weights.SWIN_VARIANTS`), each at window 7 / 224 px and at
+window 12 / 384 px, with the `_22k` / `_22kto1k` / `_22kto1k_finetune` name suffixes (21841 or
+1000 classes); `swin_root_path` is accepted and ignored. Stage widths go up to 1536 (Swin-L).
 The forward is one call into libevt_hip.so (`evt_swin_forward`, include/evt.h). Deliberate
 differences: `seed=` / `weights=` select the parameters (Keras [in, out] dict, or
 `params_from_state_dict` of a microsoft checkpoint), `dtype` selects bf16 MFMA or exact fp32;
@@ -37,7 +38,7 @@ from .vit import _capture_graph, _replay_graph, _to_device_image
 
 class SwinTransformer:
     """Swin Transformer forward on MI355X (microsoft `SwinTransformer`, built by reference
-    `utils.py:28-43`)."""
+    `utils.py:28-43`). Stage widths (embed_dim * 2^i) up to 1536: Swin-T / S / B / L."""
 
     def __init__(self, img_size=224, patch_size=4, in_chans=3, num_classes=1000, embed_dim=96,
                  depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), window_size=7, mlp_ratio=4.,
@@ -175,24 +176,30 @@ class SwinTransformer:
     forward = __call__
 
 
-_CONFIG_RE = re.compile(r"swin_(tiny|small|base)_patch(\d+)_window(\d+)_(\d+)$")
+_CONFIG_RE = re.compile(r"swin_(tiny|small|base|large)_patch(\d+)_window(\d+)_(\d+)"
+                        r"(_22k|_22kto1k|_22kto1k_finetune)?$")
+_CLASSES_22K = 21841  # ImageNet-22K head of the microsoft `_22k` configs
 
 
-def swin_config_from_name(config_file_name: str, num_classes: int = 1000) -> SwinConfig:
-    """The SwinConfig of a microsoft config name (configs/swin_{tiny,small,base}_patch4_window7_224
-    or _window12_384)."""
+def swin_config_from_name(config_file_name: str, num_classes: Optional[int] = None) -> SwinConfig:
+    """The SwinConfig of a microsoft config name (configs/swin_{tiny,small,base,large}_patch4_
+    window7_224 or _window12_384, optionally with the `_22k` suffix: 21841 classes unless
+    `num_classes` is given, or `_22kto1k` / `_22kto1k_finetune`: 1000 classes)."""
     m = _CONFIG_RE.match(config_file_name)
     if not m:
         raise NotImplementedError(f"Unkown model: {config_file_name}")  # utils.py:45 wording
     variant, patch, window, size = m.group(1), int(m.group(2)), int(m.group(3)), int(m.group(4))
+    if num_classes is None:
+        num_classes = _CLASSES_22K if m.group(5) == "_22k" else 1000
     return swin_config(variant, patch_size=patch, window_size=window, image_size=size,
                        num_classes=num_classes)
 
 
 def get_swin(config_file_name: str = "swin_tiny_patch4_window7_224", swin_root_path: str = "",
              **kw) -> SwinTransformer:
-    """Reference `utils.py:14-47` (`get_swin`), with the published configs built in."""
-    c = swin_config_from_name(config_file_name, kw.pop("num_classes", 1000))
+    """Reference `utils.py:14-47` (`get_swin`), with the published configs built in: swin_{tiny,
+    small,base,large}_patch4_window7_224 / _window12_384 (+ `_22k`, `_22kto1k[_finetune]`)."""
+    c = swin_config_from_name(config_file_name, kw.pop("num_classes", None))
     return SwinTransformer(img_size=c.image_size, patch_size=c.patch_size, in_chans=c.in_chans,
                            num_classes=c.num_classes, embed_dim=c.embed_dim, depths=c.depths,
                            num_heads=c.num_heads, window_size=c.window_size,
@@ -228,5 +235,5 @@ def params_from_state_dict(sd: Dict[str, np.ndarray], cfg: SwinConfig) -> Dict[s
 
 
 def build_named(name: str, **kw) -> SwinTransformer:
-    """'swin_tiny' | 'swin_small' | 'swin_base' (patch 4, window 7, 224)."""
+    """'swin_tiny' | 'swin_small' | 'swin_base' | 'swin_large' (patch 4, window 7, 224)."""
     return get_swin(f"{name}_patch4_window7_224", **kw)

@@ -35,7 +35,7 @@ import numpy as np
 
 VIT_NAMED = {"deit_tiny": 3, "deit_small": 6, "deit_base": 12}   # heads (vit.py:100-109)
 T2T_NAMED = ("t2t_vit_7", "t2t_vit_10", "t2t_vit_12", "t2t_vit_14")
-SWIN_NAMED = ("swin_tiny", "swin_small", "swin_base")   # get_swin configs (tools.py:282)
+SWIN_NAMED = ("swin_tiny", "swin_small", "swin_base", "swin_large")   # get_swin configs (tools.py:282)
 
 
 def build_model(name: str, compute_dtype: str, prune_encoding: Optional[str] = None,
@@ -43,7 +43,7 @@ def build_model(name: str, compute_dtype: str, prune_encoding: Optional[str] = N
     """A model by reference name (deit_*, t2t_vit_*, swin_*), optionally head/FFN pruned.
     image_size: the input resolution (reference utils.py:52-62 loads 224 and 384 px DeiT; any size
     the library takes works for DeiT and T2T-ViT; a full Swin config name carries its own size,
-    e.g. swin_base_patch4_window12_384, the short names swin_tiny|small|base are 224 px)."""
+    e.g. swin_large_patch4_window12_384, the short names swin_tiny|small|base|large are 224 px)."""
     kw = {} if image_size == 224 else {"image_size": image_size}
     full_swin = re.match(r"swin_.*_(\d+)$", name)
     if name in SWIN_NAMED or full_swin:

@@ -389,10 +389,11 @@ class SwinConfig:
         return f / 1e9
 
 
-SWIN_VARIANTS = {  # microsoft/Swin-Transformer configs/swin_{tiny,small,base}_patch4_window7_224.yaml
+SWIN_VARIANTS = {  # microsoft/Swin-Transformer configs/swin_{tiny,small,base,large}_patch4_*.yaml
     "tiny": dict(embed_dim=96, depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24)),
     "small": dict(embed_dim=96, depths=(2, 2, 18, 2), num_heads=(3, 6, 12, 24)),
     "base": dict(embed_dim=128, depths=(2, 2, 18, 2), num_heads=(4, 8, 16, 32)),
+    "large": dict(embed_dim=192, depths=(2, 2, 18, 2), num_heads=(6, 12, 24, 48)),
 }
 
 

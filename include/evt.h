@@ -207,7 +207,9 @@ int evt_ln_fold(int dtype, const void* Wp, int Kpad, int Npad, const float* W, c
 #define EVT_EPI_STATS 128  /* write per-slab (sum, sumsq) of each stored row into stats_out */
 #define EVT_EPI_GELU_ERF 256 /* exact erf GELU (torch nn.GELU, the Swin MLP) */
 /* LayerNorm row statistics layout: float stats[rows][S][2], S = 2 * ceil(ln_width / 256) slots
- * (one per 128-column slab); a row's (sum, sumsq) is the sum over its S slots. */
+ * (one per 128-column slab); a row's (sum, sumsq) is the sum over its S slots, taken in slot
+ * order. Widths up to 1536 (S <= 12) are read by the persistent 256 x 256 bf16 GEMM (S = 10, 12:
+ * in two rounds of 8 and S - 8 slots, Kpad >= 512); wider rows take the 128 x 128 kernel. */
 
 typedef struct evt_dense_args {
   int32_t flags;
@@ -224,7 +226,8 @@ typedef struct evt_dense_args {
   const float* rstats;              /* EVT_EPI_RESLN: [M][S][2] slot statistics of resid rows */
   const float* rgamma; const float* rbeta;
   float* stats_out;                 /* EVT_EPI_STATS: [rows][S][2], this call's slots written */
-  int32_t ln_width;                 /* LayerNorm width (D) for the stats */
+  int32_t ln_width;                 /* LayerNorm width (D) for the stats; any positive width,
+                                       up to 1536 on the persistent bf16 path */
   float ln_eps;                     /* LayerNorm epsilon (1e-5 in the reference) */
   int32_t stats_step;               /* EVT_EPI_LNIN: A row m uses stats_in row m * stats_step
                                        (0 or 1: consecutive; T: the CLS rows of a token stream) */
@@ -348,12 +351,15 @@ int64_t evt_performer_scratch(int B, int T);
  * num_heads, window_size, mlp_ratio, qkv_bias=True, ape=False, patch_norm=True) as get_swin builds
  * it (utils.py:28-43; swin_tiny_patch4_window7_224 = embed 96, depths (2,2,6,2), heads
  * (3,6,12,24); swin_base_patch4_window12_384 = embed 128, depths (2,2,18,2), heads (4,8,16,32),
- * window 12 at 384 px). This build: window_size 7 or 12, head size 32 (stage width / heads), stage
- * width <= 1024. A stage's window is min(window_size, its resolution) and must itself be 7 or 12,
+ * window 12 at 384 px; swin_large_* = embed 192, depths (2,2,18,2), heads (6,12,24,48)). This
+ * build: window_size 7 or 12, head size 32 (stage width / heads), stage width <= 1536 (Swin-L's
+ * last stage), embed_dim <= 1536. A stage's window is min(window_size, its resolution) and must itself be 7 or 12,
  * with the stage resolution a multiple of it (no padding); a stage no larger than window_size is
  * one unshifted window, the others shift by window_size / 2 on odd blocks. Past 56 x 56 tokens
- * per image max_batch is limited so that every activation buffer stays below 2^31 bytes
- * (EVT_EINVAL otherwise; Swin-B at 384 px: 227 images in bf16). */
+ * per image, or with a stage wider than 1024, max_batch is limited so that every activation
+ * buffer stays below 2^31 bytes (EVT_EINVAL otherwise; Swin-B at 384 px: 227 images in bf16;
+ * Swin-L at 384 px: 151 images in bf16, 75 in f32 (9216 tokens x 768 MLP columns per image);
+ * Swin-L at 224 px: 445 in bf16, 222 in f32). */
 typedef struct evt_swin_desc {
   int32_t image_size;   /* 224 */
   int32_t patch_size;   /* 4 */
