@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/evt.h"
@@ -109,36 +110,47 @@ static bool qkv_headmajor_default() {
   return !(e && std::strcmp(e, "token") == 0);
 }
 
-struct evt_model {
+// What is fixed once evt_*_create returns: configuration, geometry and the packed weights. Lane
+// children (evt_model_set_lanes) copy it, so they share the parent's weight allocations.
+struct ModelCore {
   int family = 0;            // 0: ViT / ViT_Pruned, 1: T2T-ViT, 2: Swin
   bool standard = false;     // ViT with EVT_VIT_STANDARD semantics
   bool mx8 = false;          // EVT_DTYPE_MX8: MXFP8 encoder Dense layers (dtype is then bf16)
   // QKV output head-major where the GEMM supports it (run_encoder); EVT_QKV_LAYOUT=token at model
   // creation keeps the token-major layout (the A/B and bitwise-equality tests)
   bool headmajor = qkv_headmajor_default();
-  int hm_layers = 0;         // encoder layers whose QKV stored head-major in the last forward
   bool patch_cm = false;     // ViT: channel-major patch vectors / patch weight rows
-  void* qa = nullptr;        // MX8: [rows][max(Dpad, innerpad)] e4m3 A operand (LN out / attn out)
-  uint32_t* sa = nullptr;    // MX8: its scales [pad/128][rows]
-  void* qh = nullptr;        // MX8: [rows][ffnpad] FC1 output (e4m3, zero-initialised)
-  uint32_t* shd = nullptr;   // MX8: its scales
-  float* lnst = nullptr;     // MX8: [rows][2] (mu, rstd) of the last LayerNorm'd rows
-  int qa_ld = 0, qh_ld = 0;
   float eps = 1e-5f;         // LayerNorm epsilon of every folded LayerNorm
-  int dtype = 0, D = 0, max_batch = 0, num_classes = 0;
+  int dtype = 0, D = 0, num_classes = 0;
+  size_t img_elems = 0;      // fp32 elements of one input image
   evt_vit_desc desc{};       // ViT only
   evt_t2t_desc tdesc{};      // T2T only
+  evt_swin_desc sdesc{};     // Swin only
   std::vector<int32_t> heads, head_dim, ffn;
   Shape sh;
   DenseW patch, head1, head2;
   float *cls = nullptr, *pos = nullptr;
   void* pos_h = nullptr;     // bf16 copy of pos (the persistent patch-embedding GEMM's EPI_POS)
   std::vector<Layer> layers;
-  std::vector<void*> allocs;
   // T2T stage
   Performer perf[2];
   DenseW project, head;      // head: LN-folded classifier (final LayerNorm, t2t_vit.py:129,134)
   int grid[3] = {0, 0, 0};   // token grids S/4, S/8, S/16
+  // Swin (family 2)
+  std::vector<SwinStage> stages;
+  float *pnorm_g = nullptr, *pnorm_b = nullptr, *norm_g = nullptr, *norm_b = nullptr;
+  // desc's per-layer arrays live in this core's own vectors (after every copy of a core)
+  void bind_desc() {
+    desc.heads = heads.data();
+    desc.head_dim = head_dim.data();
+    desc.ffn = ffn.data();
+  }
+};
+
+// The buffers a forward writes, filled in by the *_alloc_ws functions for one handle's max_batch
+// and never shared: every lane child has its own. The allocations are owned by evt_model::allocs.
+struct Workspace {
+  // T2T stage
   void* u = nullptr;         // unfold output (GEMM A operand)
   float* su = nullptr;       // unfold row statistics
   void* kqvb = nullptr;      // [B*T1, 192]
@@ -146,7 +158,7 @@ struct evt_model {
   float* tstats = nullptr;   // [B*T1, 2] per-token (sum, sumsq) of pout (gathered soft split)
   void* zrow = nullptr;      // 256 zero bytes: the soft split's padding rows (gathered loader)
   float* part = nullptr;     // performer partial sums
-  // workspace (activation dtype unless noted)
+  // token stream (activation dtype unless noted)
   void* apatch = nullptr;    // [B*P, pd] patch matrix (aliases hbuf)
   void* x = nullptr;         // [B*T, D] token stream at layer input / output
   void* xm = nullptr;        // [B*T, D] token stream between the two sublayers
@@ -158,12 +170,21 @@ struct evt_model {
   size_t hbuf_bytes = 0;
   void* hh = nullptr;        // [B, head_st]
   void* sk = nullptr;        // stream-K scratch of the model's GEMMs (gemm_sk_bytes)
-  // Swin (family 2)
-  evt_swin_desc sdesc{};
-  std::vector<SwinStage> stages;
-  float *pnorm_g = nullptr, *pnorm_b = nullptr, *norm_g = nullptr, *norm_b = nullptr;
-  void* pooled = nullptr;    // [B, Cst_last] LayerNorm + token mean (head A operand)
-  size_t ws_bytes = 0;
+  void* pooled = nullptr;    // Swin: [B, Cst_last] LayerNorm + token mean (head A operand)
+  void* qa = nullptr;        // MX8: [rows][max(Dpad, innerpad)] e4m3 A operand (LN out / attn out)
+  uint32_t* sa = nullptr;    // MX8: its scales [pad/128][rows]
+  void* qh = nullptr;        // MX8: [rows][ffnpad] FC1 output (e4m3, zero-initialised)
+  uint32_t* shd = nullptr;   // MX8: its scales
+  float* lnst = nullptr;     // MX8: [rows][2] (mu, rstd) of the last LayerNorm'd rows
+  int qa_ld = 0, qh_ld = 0;
+};
+static_assert(std::is_trivially_copyable<Workspace>::value, "raw pointers and integers only");
+
+struct evt_model : ModelCore {  // a handle: the core, its own workspace, its own runtime state
+  Workspace ws;
+  int max_batch = 0;
+  std::vector<void*> allocs;         // every device allocation this handle owns (weights, ws)
+  int hm_layers = 0;         // encoder layers whose QKV stored head-major in the last forward
   hipGraph_t graph = nullptr;        // evt_graph_capture
   hipGraphExec_t graph_exec = nullptr;
   // evt_model_profile: HIP events around every launch of the last forward, by role
@@ -187,7 +208,6 @@ struct evt_model {
 };
 
 namespace {
-
 
 // evt_model_profile: a pair of events around each launch of a forward (profiling forwards only)
 struct ProfScope {
@@ -461,7 +481,7 @@ GemmParams dense_params(const evt_model* m, const DenseW& w, const DenseCall& c)
   p.eps = m->eps;  // Keras LayerNormalization(epsilon=1e-5), reference norm.py:6
   p.nslots = stats_slots(c.slot_width ? c.slot_width : width);
   p.stats_step = c.stats_step;
-  gemm_sk_bind(m->sk, p);
+  gemm_sk_bind(m->ws.sk, p);
   return p;
 }
 
@@ -517,8 +537,8 @@ int build_encoder(evt_model* m, const float* const* w, hipStream_t s) {
 int alloc_encoder_ws(evt_model* m, int B, size_t hbuf_bytes, hipStream_t s) {
   const size_t es = elem_size(m->dtype);
   if (m->dtype == DT_BF16) {
-    EVT_RC(dev_alloc(m, &m->sk, gemm_sk_bytes()));
-    EVT_HIP(hipMemsetAsync(m->sk, 0, 4096, s), "memset stream-K flags");
+    EVT_RC(dev_alloc(m, &m->ws.sk, gemm_sk_bytes()));
+    EVT_HIP(hipMemsetAsync(m->ws.sk, 0, 4096, s), "memset stream-K flags");
   }
   const size_t rows = (size_t)B * m->sh.T;
   // x, xm (width D) and o (width heads * h_k) are GEMM A operands read in 64-column K-tiles: with
@@ -526,18 +546,18 @@ int alloc_encoder_ws(evt_model* m, int B, size_t hbuf_bytes, hipStream_t s) {
   // the zero-padded weight rows) and the last row into PAD_K zeroed slack elements; every byte is
   // zeroed once here (finite everywhere)
   const size_t xb = (rows * m->D + PAD_K) * es, ob = (rows * m->sh.max_inner + PAD_K) * es;
-  EVT_RC(dev_alloc(m, &m->x, xb));
-  EVT_RC(dev_alloc(m, &m->xm, xb));
+  EVT_RC(dev_alloc(m, &m->ws.x, xb));
+  EVT_RC(dev_alloc(m, &m->ws.xm, xb));
   const size_t stats_bytes = rows * stats_slots(m->D) * 2 * sizeof(float);
-  EVT_RC(dev_alloc(m, (void**)&m->sx, stats_bytes));
-  EVT_RC(dev_alloc(m, (void**)&m->sm, stats_bytes));
-  EVT_RC(dev_alloc(m, &m->qkv, rows * 3 * m->sh.max_inner * es));
-  EVT_RC(dev_alloc(m, &m->o, ob));
-  EVT_HIP(hipMemsetAsync(m->x, 0, xb, s), "memset x");
-  EVT_HIP(hipMemsetAsync(m->xm, 0, xb, s), "memset xm");
-  EVT_HIP(hipMemsetAsync(m->o, 0, ob, s), "memset o");
-  EVT_RC(dev_alloc(m, &m->hbuf, hbuf_bytes));
-  m->hbuf_bytes = hbuf_bytes;
+  EVT_RC(dev_alloc(m, (void**)&m->ws.sx, stats_bytes));
+  EVT_RC(dev_alloc(m, (void**)&m->ws.sm, stats_bytes));
+  EVT_RC(dev_alloc(m, &m->ws.qkv, rows * 3 * m->sh.max_inner * es));
+  EVT_RC(dev_alloc(m, &m->ws.o, ob));
+  EVT_HIP(hipMemsetAsync(m->ws.x, 0, xb, s), "memset x");
+  EVT_HIP(hipMemsetAsync(m->ws.xm, 0, xb, s), "memset xm");
+  EVT_HIP(hipMemsetAsync(m->ws.o, 0, ob, s), "memset o");
+  EVT_RC(dev_alloc(m, &m->ws.hbuf, hbuf_bytes));
+  m->ws.hbuf_bytes = hbuf_bytes;
   return EVT_OK;
 }
 
@@ -548,18 +568,18 @@ int dense_head(const evt_model* m, const DenseW& w, const DenseCall& c, hipStrea
   int S = 1;
   while (S < 8 && tiles * S * 2 <= device_cus() && w.kpad % (S * 2 * PAD_K) == 0) S *= 2;
   const size_t part = (size_t)S * c.M * w.npad * sizeof(float);
-  if (S < 2 || !m->hbuf || part > m->hbuf_bytes ||
+  if (S < 2 || !m->ws.hbuf || part > m->ws.hbuf_bytes ||
       (c.flags & ~(EPI_BIAS | EPI_GELU | EPI_OUT_F32)))
     return dense(m, w, c, s);
   dense_work(m, w, c);
   GemmParams p{};
   p.A = c.A; p.lda = c.lda; p.W = w.w; p.ldw = w.kpad; p.C = c.C; p.ldc = c.ldc;
   p.M = c.M; p.N = c.N; p.K = w.kpad; p.ntiles = w.npad / GEMM_BN; p.bias = w.b;
-  EVT_HIP(gemm_splitk_launch(m->dtype, c.flags, p, S, (float*)m->hbuf, s), "dense (split-K)");
+  EVT_HIP(gemm_splitk_launch(m->dtype, c.flags, p, S, (float*)m->ws.hbuf, s), "dense (split-K)");
   return EVT_OK;
 }
 
-// Encoder layers (transformer_encoder.py:13-18 / :26-34) on the token stream m->x (+ stats sx).
+// Encoder layers (transformer_encoder.py:13-18 / :26-34) on the token stream m->ws.x (+ stats sx).
 int run_encoder(evt_model* m, int B, hipStream_t s) {
   const int D = m->D, T = m->sh.T, rows = B * T;
   const float log2e = 1.4426950408889634f;
@@ -574,8 +594,8 @@ int run_encoder(evt_model* m, int B, hipStream_t s) {
       ProfScope ps(m, EVT_PROF_QKV, s);
       DenseCall c;
       c.flags = EPI_LNIN | EPI_BIAS;
-      c.A = m->x; c.lda = D; c.C = m->qkv; c.ldc = 3 * L.inner; c.M = rows; c.N = 3 * L.inner;
-      c.stats_in = m->sx;
+      c.A = m->ws.x; c.lda = D; c.C = m->ws.qkv; c.ldc = 3 * L.inner; c.M = rows; c.N = 3 * L.inner;
+      c.stats_in = m->ws.sx;
       if (L.hd == 64 && m->headmajor) {
         DenseCall h = c;
         h.flags |= EPI_HM;
@@ -593,7 +613,7 @@ int run_encoder(evt_model* m, int B, hipStream_t s) {
       ProfScope ps(m, EVT_PROF_ATTENTION, s);
       prof_work(m, 4.0 * B * L.heads * (double)T * T * L.hd,
                 (double)rows * 4 * L.inner * elem_size(m->dtype));  // qkv read + O written
-      AttnParams ap{m->qkv, 3 * L.inner, m->o, L.inner, T, L.heads, B, scale_log2};
+      AttnParams ap{m->ws.qkv, 3 * L.inner, m->ws.o, L.inner, T, L.heads, B, scale_log2};
       ap.hd = L.hd;
       if (hm) {
         ap.ldq = 64;
@@ -608,14 +628,14 @@ int run_encoder(evt_model* m, int B, hipStream_t s) {
     DenseCall co;
     co.flags = m->standard ? (EPI_BIAS | EPI_RESID | EPI_STATS)
                            : (EPI_BIAS | EPI_RESID | EPI_RESLN | EPI_STATS);
-    co.A = m->o; co.lda = L.inner; co.C = m->xm; co.ldc = D; co.M = rows; co.N = D;
-    co.resid = m->x; co.ldr = D; co.rstats = m->sx; co.rgamma = L.ln1_g; co.rbeta = L.ln1_b;
-    co.stats_out = m->sm;
+    co.A = m->ws.o; co.lda = L.inner; co.C = m->ws.xm; co.ldc = D; co.M = rows; co.N = D;
+    co.resid = m->ws.x; co.ldr = D; co.rstats = m->ws.sx; co.rgamma = L.ln1_g; co.rbeta = L.ln1_b;
+    co.stats_out = m->ws.sm;
     // LN2-folded FC1 + GELU (ffn.py:8; STANDARD: exact erf GELU)
     DenseCall c1;
     c1.flags = EPI_LNIN | EPI_BIAS | (m->standard ? EPI_GELU_ERF : EPI_GELU);
-    c1.A = m->xm; c1.lda = D; c1.C = m->hbuf; c1.ldc = L.ffn_st; c1.M = rows; c1.N = L.ffn_st;
-    c1.stats_in = m->sm;
+    c1.A = m->ws.xm; c1.lda = D; c1.C = m->ws.hbuf; c1.ldc = L.ffn_st; c1.M = rows; c1.N = L.ffn_st;
+    c1.stats_in = m->ws.sm;
     {
       ProfScope ps(m, EVT_PROF_OUT_PROJ, s);
       EVT_RC(dense(m, L.out, co, s));
@@ -629,9 +649,9 @@ int run_encoder(evt_model* m, int B, hipStream_t s) {
       DenseCall c;
       c.flags = m->standard ? (EPI_BIAS | EPI_RESID | EPI_STATS)
                             : (EPI_BIAS | EPI_RESID | EPI_RESLN | EPI_STATS);
-      c.A = m->hbuf; c.lda = L.ffn_st; c.C = m->x; c.ldc = D; c.M = rows; c.N = D;
-      c.resid = m->xm; c.ldr = D; c.rstats = m->sm; c.rgamma = L.ln2_g; c.rbeta = L.ln2_b;
-      c.stats_out = m->sx;
+      c.A = m->ws.hbuf; c.lda = L.ffn_st; c.C = m->ws.x; c.ldc = D; c.M = rows; c.N = D;
+      c.resid = m->ws.xm; c.ldr = D; c.rstats = m->ws.sm; c.rgamma = L.ln2_g; c.rbeta = L.ln2_b;
+      c.stats_out = m->ws.sx;
       EVT_RC(dense(m, L.fc2, c, s));
     }
   }
@@ -648,28 +668,29 @@ int run_encoder_mx8(evt_model* m, int B, hipStream_t s) {
   const float log2e = 1.4426950408889634f;
   const int dpad = (int)round_up(D, 128);
   for (const Layer& L : m->layers) {
-    EVT_HIP(ln_mx8_launch(m->x, rows, D, dpad, L.ln1_g, L.ln1_b, m->eps, m->lnst, m->qa, m->sa, s),
+    EVT_HIP(ln_mx8_launch(m->ws.x, rows, D, dpad, L.ln1_g, L.ln1_b, m->eps, m->ws.lnst, m->ws.qa,
+                          m->ws.sa, s),
             "ln1 mx8");
-    EVT_RC(dense_mx8(L.mqkv, EPI_BIAS, m->qa, dpad, m->sa, m->qkv, 3 * L.inner, nullptr, rows,
-                     nullptr, 0, s));
+    EVT_RC(dense_mx8(L.mqkv, EPI_BIAS, m->ws.qa, dpad, m->ws.sa, m->ws.qkv, 3 * L.inner, nullptr,
+                     rows, nullptr, 0, s));
     // attention writes O straight as the MX8 operand of the out-proj (columns [inner, ipad) of
     // qa keep finite stale values, cancelled by the zero rows of the packed weights)
     const int ipad = L.mout.kpad;
-    AttnParams ap{m->qkv, 3 * L.inner, m->o, L.inner, T, L.heads, B, 0.125f * log2e};
-    ap.q8 = (uint8_t*)m->qa;
-    ap.s8 = m->sa;
+    AttnParams ap{m->ws.qkv, 3 * L.inner, m->ws.o, L.inner, T, L.heads, B, 0.125f * log2e};
+    ap.q8 = (uint8_t*)m->ws.qa;
+    ap.s8 = m->ws.sa;
     ap.ldq8 = ipad;
     ap.rows8 = rows;
     EVT_HIP(attention_launch(DT_BF16, ap, s), "attention");
-    EVT_RC(dense_mx8(L.mout, EPI_BIAS | EPI_RESID | EPI_RESLN, m->qa, ipad, m->sa, m->xm, D,
-                     nullptr, rows, m->x, D, s, m->lnst, L.ln1_g, L.ln1_b));
-    EVT_HIP(ln_mx8_launch(m->xm, rows, D, dpad, L.ln2_g, L.ln2_b, m->eps, m->lnst, m->qa, m->sa,
-                          s),
+    EVT_RC(dense_mx8(L.mout, EPI_BIAS | EPI_RESID | EPI_RESLN, m->ws.qa, ipad, m->ws.sa, m->ws.xm,
+                     D, nullptr, rows, m->ws.x, D, s, m->ws.lnst, L.ln1_g, L.ln1_b));
+    EVT_HIP(ln_mx8_launch(m->ws.xm, rows, D, dpad, L.ln2_g, L.ln2_b, m->eps, m->ws.lnst, m->ws.qa,
+                          m->ws.sa, s),
             "ln2 mx8");
-    EVT_RC(dense_mx8(L.mfc1, EPI_BIAS | EPI_GELU | EPI_OUT_MX8, m->qa, dpad, m->sa, m->qh,
-                     m->qh_ld, m->shd, rows, nullptr, 0, s));
-    EVT_RC(dense_mx8(L.mfc2, EPI_BIAS | EPI_RESID | EPI_RESLN, m->qh, m->qh_ld, m->shd, m->x, D,
-                     nullptr, rows, m->xm, D, s, m->lnst, L.ln2_g, L.ln2_b));
+    EVT_RC(dense_mx8(L.mfc1, EPI_BIAS | EPI_GELU | EPI_OUT_MX8, m->ws.qa, dpad, m->ws.sa, m->ws.qh,
+                     m->ws.qh_ld, m->ws.shd, rows, nullptr, 0, s));
+    EVT_RC(dense_mx8(L.mfc2, EPI_BIAS | EPI_RESID | EPI_RESLN, m->ws.qh, m->ws.qh_ld, m->ws.shd,
+                     m->ws.x, D, nullptr, rows, m->ws.xm, D, s, m->ws.lnst, L.ln2_g, L.ln2_b));
   }
   return EVT_OK;
 }
@@ -755,7 +776,6 @@ size_t t2t_workspace_bytes(const evt_t2t_desc* d, const T2TShape& ts, int B) {
          2 * rows * stats_slots(d->dim) * 2 * 4 + rows * 4 * ts.enc.max_inner * es +
          rows * ts.enc.max_ffn_st * es + t1 * 2 * 4 + 256;
 }
-
 
 // ---- Swin geometry ------------------------------------------------------------------------
 struct SwinGeo {
@@ -865,6 +885,21 @@ size_t swin_workspace_bytes(const evt_swin_desc* d, const SwinGeo& g, int B) {
          2 * w.stats * sizeof(float);
 }
 
+// What the three creates open with: the checks of out, the descriptor (-> *geo) and the weights.
+template <class Desc, class Geo>
+int create_prologue(const Desc* desc, int (*validate_fn)(const Desc*, Geo*), Geo* geo,
+                    int (*num_weights)(const Desc*), const float* const* w, int n_weights,
+                    evt_model** out) {
+  if (!out) return fail(EVT_EINVAL, "out is NULL");
+  *out = nullptr;
+  EVT_RC(validate_fn(desc, geo));
+  if (n_weights != num_weights(desc) || !w)
+    return fail(EVT_EINVAL, "expected " + std::to_string(num_weights(desc)) + " weights");
+  for (int i = 0; i < n_weights; ++i)
+    if (!w[i]) return fail(EVT_EINVAL, "weight pointer " + std::to_string(i) + " is NULL");
+  return EVT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -929,8 +964,8 @@ static int swin_alloc_ws(evt_model* m, int B, hipStream_t s);  // (the Swin sect
 // [B i / k, B (i + 1) / k) on its own stream, forked from and joined to s by events (a HIP graph
 // capture on s records the lanes as parallel branches)
 typedef int (*ForwardFn)(evt_model*, const float*, int, float*, void*);
-static int lanes_forward(evt_model* m, ForwardFn fwd, const float* img, size_t img_elems, int B,
-                         float* logits, hipStream_t s) {
+static int lanes_forward(evt_model* m, ForwardFn fwd, const float* img, int B, float* logits,
+                         hipStream_t s) {
   // the joins go onto s after every lane's work: a lane stream that shares s's hardware queue
   // would otherwise queue its kernels behind s's wait for the previous lane (measured: lanes
   // serialised in part)
@@ -941,7 +976,7 @@ static int lanes_forward(evt_model* m, ForwardFn fwd, const float* img, size_t i
   for (int i = 0; i < k; ++i) {
     const int b0 = (int)((int64_t)B * i / k), b1 = (int)((int64_t)B * (i + 1) / k);
     if (b1 > b0)
-      EVT_RC(fwd(m->lanes[i], img + (size_t)b0 * img_elems, b1 - b0,
+      EVT_RC(fwd(m->lanes[i], img + (size_t)b0 * m->img_elems, b1 - b0,
                  logits + (size_t)b0 * m->num_classes, m->lane_s[i]));
     EVT_HIP(hipEventRecord(m->lane_ev[1 + i], m->lane_s[i]), "lane done");
   }
@@ -951,6 +986,20 @@ static int lanes_forward(evt_model* m, ForwardFn fwd, const float* img, size_t i
   return EVT_OK;
 }
 
+// What the three forwards (`fwd`: the caller itself) open with: the argument checks, then the lane
+// dispatch. RUN_HERE (no error code is positive): the caller runs the forward on this handle.
+constexpr int RUN_HERE = 1;
+static int forward_prologue(evt_model* m, int family, const char* wrong_family, ForwardFn fwd,
+                            const float* img, int B, float* logits, hipStream_t s) {
+  if (!m || !img || !logits) return fail(EVT_EINVAL, "model, img and logits must be non-null");
+  if (m->family != family) return fail(EVT_EINVAL, wrong_family);
+  if (B <= 0 || B > m->max_batch)
+    return fail(EVT_EINVAL, "batch must be in [1, max_batch=" + std::to_string(m->max_batch) + "]");
+  if (!m->lanes.empty() && !m->prof && B >= (int)m->lanes.size())  // profiling: one lane
+    return lanes_forward(m, fwd, img, B, logits, s);
+  return RUN_HERE;
+}
+
 // The ViT workspace for B images (activation buffers only; lanes allocate their own)
 static int vit_alloc_ws(evt_model* m, int B, hipStream_t s) {
   const Shape& sh = m->sh;
@@ -958,40 +1007,33 @@ static int vit_alloc_ws(evt_model* m, int B, hipStream_t s) {
   const size_t es = elem_size(m->dtype);
   EVT_RC(alloc_encoder_ws(m, B, std::max((size_t)B * sh.T * sh.max_ffn_st,
                                          (size_t)B * sh.P * sh.pd) * es, s));
-  m->apatch = m->hbuf;
-  EVT_RC(dev_alloc(m, &m->hh, (size_t)B * sh.head_st * es));
+  m->ws.apatch = m->ws.hbuf;
+  EVT_RC(dev_alloc(m, &m->ws.hh, (size_t)B * sh.head_st * es));
   if (m->mx8) {
     const size_t rows = (size_t)B * sh.T;
-    m->qa_ld = (int)std::max(round_up(D, 128), round_up(sh.max_inner, 128));
+    m->ws.qa_ld = (int)std::max(round_up(D, 128), round_up(sh.max_inner, 128));
     int maxffn = 0;
     for (int f : m->ffn) maxffn = std::max(maxffn, f);
-    m->qh_ld = (int)round_up(maxffn, 128);
-    EVT_RC(dev_alloc(m, &m->qa, rows * m->qa_ld));
-    EVT_RC(dev_alloc(m, (void**)&m->sa, rows * (m->qa_ld / 128) * 4));
-    EVT_RC(dev_alloc(m, &m->qh, rows * m->qh_ld));
-    EVT_RC(dev_alloc(m, (void**)&m->shd, rows * (m->qh_ld / 128) * 4));
-    EVT_RC(dev_alloc(m, (void**)&m->lnst, rows * 2 * sizeof(float)));
+    m->ws.qh_ld = (int)round_up(maxffn, 128);
+    EVT_RC(dev_alloc(m, &m->ws.qa, rows * m->ws.qa_ld));
+    EVT_RC(dev_alloc(m, (void**)&m->ws.sa, rows * (m->ws.qa_ld / 128) * 4));
+    EVT_RC(dev_alloc(m, &m->ws.qh, rows * m->ws.qh_ld));
+    EVT_RC(dev_alloc(m, (void**)&m->ws.shd, rows * (m->ws.qh_ld / 128) * 4));
+    EVT_RC(dev_alloc(m, (void**)&m->ws.lnst, rows * 2 * sizeof(float)));
     // every byte of the MX8 operands is written finite before it is read (NaN-free padding)
-    EVT_HIP(hipMemsetAsync(m->qa, 0, rows * m->qa_ld, s), "memset qa");
-    EVT_HIP(hipMemsetAsync(m->sa, 0, rows * (m->qa_ld / 128) * 4, s), "memset qa scales");
+    EVT_HIP(hipMemsetAsync(m->ws.qa, 0, rows * m->ws.qa_ld, s), "memset qa");
+    EVT_HIP(hipMemsetAsync(m->ws.sa, 0, rows * (m->ws.qa_ld / 128) * 4, s), "memset qa scales");
     // FC1 writes columns < roundup(ffn, 32) only: the rest of the FC2 operand stays zero
-    EVT_HIP(hipMemsetAsync(m->qh, 0, rows * m->qh_ld, s), "memset qh");
-    EVT_HIP(hipMemsetAsync(m->shd, 0, rows * (m->qh_ld / 128) * 4, s), "memset qh scales");
+    EVT_HIP(hipMemsetAsync(m->ws.qh, 0, rows * m->ws.qh_ld, s), "memset qh");
+    EVT_HIP(hipMemsetAsync(m->ws.shd, 0, rows * (m->ws.qh_ld / 128) * 4, s), "memset qh scales");
   }
-  m->ws_bytes = workspace_bytes(&m->desc, sh, B);
   return EVT_OK;
 }
 
 int evt_vit_create(const evt_vit_desc* desc, const float* const* w, int n_weights, void* stream,
                    evt_model** out) {
-  if (!out) return fail(EVT_EINVAL, "out is NULL");
-  *out = nullptr;
   Shape sh;
-  EVT_RC(validate(desc, &sh));
-  if (n_weights != evt_vit_num_weights(desc) || !w)
-    return fail(EVT_EINVAL, "expected " + std::to_string(evt_vit_num_weights(desc)) + " weights");
-  for (int i = 0; i < n_weights; ++i)
-    if (!w[i]) return fail(EVT_EINVAL, "weight pointer " + std::to_string(i) + " is NULL");
+  EVT_RC(create_prologue(desc, validate, &sh, evt_vit_num_weights, w, n_weights, out));
   hipStream_t s = (hipStream_t)stream;
   evt_model* m = new evt_model();
   m->family = 0;
@@ -1006,10 +1048,9 @@ int evt_vit_create(const evt_vit_desc* desc, const float* const* w, int n_weight
   m->heads.assign(desc->heads, desc->heads + desc->depth);
   m->head_dim.assign(desc->head_dim, desc->head_dim + desc->depth);
   m->ffn.assign(desc->ffn, desc->ffn + desc->depth);
-  m->desc.heads = m->heads.data();
-  m->desc.head_dim = m->head_dim.data();
-  m->desc.ffn = m->ffn.data();
+  m->bind_desc();
   m->sh = sh;
+  m->img_elems = (size_t)desc->in_chans * desc->image_size * desc->image_size;
   const int D = desc->dim;
   auto run = [&]() -> int {
     if (desc->patch_size % 8 == 0) {  // channel-major patch vectors (patchify_cm_kernel)
@@ -1044,15 +1085,10 @@ int evt_vit_create(const evt_vit_desc* desc, const float* const* w, int n_weight
 }
 
 int evt_vit_forward(evt_model* m, const float* img, int B, float* logits, void* stream) {
-  if (!m || !img || !logits) return fail(EVT_EINVAL, "model, img and logits must be non-null");
-  if (m->family != 0) return fail(EVT_EINVAL, "model is not a ViT (use evt_t2t_forward)");
-  if (B <= 0 || B > m->max_batch)
-    return fail(EVT_EINVAL, "batch must be in [1, max_batch=" + std::to_string(m->max_batch) + "]");
   hipStream_t s = (hipStream_t)stream;
-  if (!m->lanes.empty() && !m->prof && B >= (int)m->lanes.size())  // profiling: one lane
-    return lanes_forward(m, evt_vit_forward, img,
-                         (size_t)m->desc.in_chans * m->desc.image_size * m->desc.image_size, B,
-                         logits, s);
+  const int pre = forward_prologue(m, 0, "model is not a ViT (use evt_t2t_forward)",
+                                   evt_vit_forward, img, B, logits, s);
+  if (pre != RUN_HERE) return pre;
   const evt_vit_desc& d = m->desc;
   const Shape& sh = m->sh;
   const int D = d.dim, T = sh.T, dt = m->dtype;
@@ -1063,16 +1099,16 @@ int evt_vit_forward(evt_model* m, const float* img, int B, float* logits, void* 
     prof_work(m, 0.0, (double)B * d.in_chans * d.image_size * d.image_size * 4 +
                           (double)B * (sh.P * sh.pd + D) * elem_size(dt) +
                           (double)B * stats_slots(D) * 8);  // image read, patch rows + CLS rows
-    EVT_HIP(patchify_launch(dt, img, B, d.in_chans, d.image_size, d.patch_size, m->apatch, m->x,
-                            m->cls, m->pos, D, m->sx, s, m->patch_cm),
+    EVT_HIP(patchify_launch(dt, img, B, d.in_chans, d.image_size, d.patch_size, m->ws.apatch,
+                            m->ws.x, m->cls, m->pos, D, m->ws.sx, s, m->patch_cm),
             "patchify");
   }
   {
     ProfScope ps(m, EVT_PROF_PATCH_EMBED, s);
     DenseCall c;
     c.flags = EPI_BIAS | EPI_POS | EPI_STATS;
-    c.A = m->apatch; c.lda = sh.pd; c.C = m->x; c.ldc = D; c.M = B * sh.P; c.N = D;
-    c.pos = m->pos; c.ldp = D; c.P = sh.P; c.stats_out = m->sx;
+    c.A = m->ws.apatch; c.lda = sh.pd; c.C = m->ws.x; c.ldc = D; c.M = B * sh.P; c.N = D;
+    c.pos = m->pos; c.ldp = D; c.P = sh.P; c.stats_out = m->ws.sx;
     c.resid = m->pos_h; c.ldr = m->pos_h ? D : 0;  // bf16 table for the persistent kernel
     EVT_RC(dense(m, m->patch, c, s));
   }
@@ -1081,8 +1117,8 @@ int evt_vit_forward(evt_model* m, const float* img, int B, float* logits, void* 
   if (m->standard) {  // final LayerNorm of the CLS rows folded into the Linear head
     DenseCall c;
     c.flags = EPI_LNIN | EPI_BIAS | EPI_OUT_F32;
-    c.A = m->x; c.lda = (int64_t)T * D; c.C = logits; c.ldc = d.num_classes; c.M = B;
-    c.N = d.num_classes; c.stats_in = m->sx; c.stats_step = T;
+    c.A = m->ws.x; c.lda = (int64_t)T * D; c.C = logits; c.ldc = d.num_classes; c.M = B;
+    c.N = d.num_classes; c.stats_in = m->ws.sx; c.stats_step = T;
     EVT_RC(dense(m, m->head, c, s));
     return EVT_OK;
   }
@@ -1090,13 +1126,14 @@ int evt_vit_forward(evt_model* m, const float* img, int B, float* logits, void* 
   {
     DenseCall c;
     c.flags = EPI_BIAS | EPI_GELU;
-    c.A = m->x; c.lda = (int64_t)T * D; c.C = m->hh; c.ldc = sh.head_st; c.M = B; c.N = sh.head_st;
+    c.A = m->ws.x; c.lda = (int64_t)T * D; c.C = m->ws.hh; c.ldc = sh.head_st; c.M = B;
+    c.N = sh.head_st;
     EVT_RC(dense_head(m, m->head1, c, s));
   }
   {
     DenseCall c;
     c.flags = EPI_BIAS | EPI_OUT_F32;
-    c.A = m->hh; c.lda = sh.head_st; c.C = logits; c.ldc = d.num_classes; c.M = B;
+    c.A = m->ws.hh; c.lda = sh.head_st; c.C = logits; c.ldc = d.num_classes; c.M = B;
     c.N = d.num_classes;
     EVT_RC(dense_head(m, m->head2, c, s));
   }
@@ -1124,30 +1161,23 @@ static int t2t_alloc_ws(evt_model* m, int B, hipStream_t s) {
   EVT_RC(validate_t2t(&m->tdesc, &ts));
   const size_t es = elem_size(m->dtype);
   const size_t t1 = (size_t)B * ts.grid[0] * ts.grid[0];
-  EVT_RC(dev_alloc(m, &m->u, t2t_unfold_elems(ts, B) * es));
-  EVT_RC(dev_alloc(m, (void**)&m->su, t2t_unfold_stat_floats(ts, B) * sizeof(float)));
-  EVT_RC(dev_alloc(m, &m->kqvb, t1 * 3 * 64 * es));
-  EVT_RC(dev_alloc(m, &m->pout, t1 * 64 * es));
-  EVT_RC(dev_alloc(m, (void**)&m->tstats, t1 * 2 * sizeof(float)));
-  EVT_RC(dev_alloc(m, &m->zrow, 256));
-  EVT_HIP(hipMemsetAsync(m->zrow, 0, 256, s), "memset zero row");
-  EVT_RC(dev_alloc(m, (void**)&m->part, performer_part_floats(B, ts.grid[0] * ts.grid[0]) *
+  EVT_RC(dev_alloc(m, &m->ws.u, t2t_unfold_elems(ts, B) * es));
+  EVT_RC(dev_alloc(m, (void**)&m->ws.su, t2t_unfold_stat_floats(ts, B) * sizeof(float)));
+  EVT_RC(dev_alloc(m, &m->ws.kqvb, t1 * 3 * 64 * es));
+  EVT_RC(dev_alloc(m, &m->ws.pout, t1 * 64 * es));
+  EVT_RC(dev_alloc(m, (void**)&m->ws.tstats, t1 * 2 * sizeof(float)));
+  EVT_RC(dev_alloc(m, &m->ws.zrow, 256));
+  EVT_HIP(hipMemsetAsync(m->ws.zrow, 0, 256, s), "memset zero row");
+  EVT_RC(dev_alloc(m, (void**)&m->ws.part, performer_part_floats(B, ts.grid[0] * ts.grid[0]) *
                                             sizeof(float)));
   EVT_RC(alloc_encoder_ws(m, B, (size_t)B * ts.enc.T * ts.enc.max_ffn_st * es, s));
-  m->ws_bytes = t2t_workspace_bytes(&m->tdesc, ts, B);
   return EVT_OK;
 }
 
 int evt_t2t_create(const evt_t2t_desc* desc, const float* const* w, int n_weights, void* stream,
                    evt_model** out) {
-  if (!out) return fail(EVT_EINVAL, "out is NULL");
-  *out = nullptr;
   T2TShape ts;
-  EVT_RC(validate_t2t(desc, &ts));
-  if (n_weights != evt_t2t_num_weights(desc) || !w)
-    return fail(EVT_EINVAL, "expected " + std::to_string(evt_t2t_num_weights(desc)) + " weights");
-  for (int i = 0; i < n_weights; ++i)
-    if (!w[i]) return fail(EVT_EINVAL, "weight pointer " + std::to_string(i) + " is NULL");
+  EVT_RC(create_prologue(desc, validate_t2t, &ts, evt_t2t_num_weights, w, n_weights, out));
   hipStream_t s = (hipStream_t)stream;
   evt_model* m = new evt_model();
   m->family = 1;
@@ -1160,6 +1190,7 @@ int evt_t2t_create(const evt_t2t_desc* desc, const float* const* w, int n_weight
   m->head_dim.assign(desc->depth, desc->dim / desc->heads);  // h_k = dim // heads
   m->ffn.assign(desc->depth, desc->mlp_dim);
   m->sh = ts.enc;
+  m->img_elems = (size_t)desc->image_size * desc->image_size * desc->in_chans;
   for (int i = 0; i < 3; ++i) m->grid[i] = ts.grid[i];
   const int D = desc->dim;
   auto run = [&]() -> int {
@@ -1205,15 +1236,10 @@ int evt_t2t_create(const evt_t2t_desc* desc, const float* const* w, int n_weight
 }
 
 int evt_t2t_forward(evt_model* m, const float* img, int B, float* logits, void* stream) {
-  if (!m || !img || !logits) return fail(EVT_EINVAL, "model, img and logits must be non-null");
-  if (m->family != 1) return fail(EVT_EINVAL, "model is not a T2T-ViT (use evt_vit_forward)");
-  if (B <= 0 || B > m->max_batch)
-    return fail(EVT_EINVAL, "batch must be in [1, max_batch=" + std::to_string(m->max_batch) + "]");
   hipStream_t s = (hipStream_t)stream;
-  if (!m->lanes.empty() && !m->prof && B >= (int)m->lanes.size())  // profiling: one lane
-    return lanes_forward(m, evt_t2t_forward, img,
-                         (size_t)m->tdesc.image_size * m->tdesc.image_size * m->tdesc.in_chans, B,
-                         logits, s);
+  const int pre = forward_prologue(m, 1, "model is not a T2T-ViT (use evt_vit_forward)",
+                                   evt_t2t_forward, img, B, logits, s);
+  if (pre != RUN_HERE) return pre;
   prof_reset(m);
   const evt_t2t_desc& d = m->tdesc;
   const int dt = d.dtype, D = d.dim, T = m->sh.T, P = m->sh.P, S = d.image_size;
@@ -1229,7 +1255,7 @@ int evt_t2t_forward(evt_model* m, const float* img, int B, float* logits, void* 
     ProfScope ps(m, EVT_PROF_T2T_UNFOLD, s);
     prof_work(m, 0.0, (double)B * S * S * d.in_chans * 4 + (double)B * t1 * P1.din * es +
                           (double)B * t1 * stats_slots(P1.din) * 8);
-    EVT_HIP(unfold_launch(dt, 1, img, B, S, S, d.in_chans, 7, 4, 2, m->u, P1.dpad, m->su,
+    EVT_HIP(unfold_launch(dt, 1, img, B, S, S, d.in_chans, 7, 4, 2, m->ws.u, P1.dpad, m->ws.su,
                           stats_slots(P1.din), s),
             "soft_split0");
   }
@@ -1237,19 +1263,19 @@ int evt_t2t_forward(evt_model* m, const float* img, int B, float* logits, void* 
     ProfScope ps(m, EVT_PROF_T2T_KQV, s);
     DenseCall c;
     c.flags = EPI_LNIN | EPI_BIAS;
-    c.A = m->u; c.lda = P1.dpad; c.C = m->kqvb; c.ldc = 3 * 64; c.M = B * t1; c.N = 3 * 64;
-    c.stats_in = m->su; c.ln_width = P1.din;
+    c.A = m->ws.u; c.lda = P1.dpad; c.C = m->ws.kqvb; c.ldc = 3 * 64; c.M = B * t1; c.N = 3 * 64;
+    c.stats_in = m->ws.su; c.ln_width = P1.din;
     EVT_RC(dense(m, P1.kqv, c, s));
   }
   // soft_split1 gathered inside the kqv GEMM's A loader where it can (bf16, persistent GEMM): the
   // performer then also writes per-token statistics, from which the split rows' are summed
   const Performer& P2 = m->perf[1];
-  const bool gather1 = dt == DT_BF16 && P2.dpad == 9 * 64 && g2 == (g1 + 1) / 2 && m->zrow;
+  const bool gather1 = dt == DT_BF16 && P2.dpad == 9 * 64 && g2 == (g1 + 1) / 2 && m->ws.zrow;
   {
     ProfScope ps(m, EVT_PROF_T2T_PERFORMER, s);
     prof_work(m, perf_flops * B * t1, (double)B * t1 * (3 * 64 + 64) * es);
-    EVT_HIP(performer_launch(dt, m->kqvb, 3 * 64, B, t1, P1.w, m->part, m->pout, 64, s,
-                             gather1 ? m->tstats : nullptr, dt == DT_BF16),
+    EVT_HIP(performer_launch(dt, m->ws.kqvb, 3 * 64, B, t1, P1.w, m->ws.part, m->ws.pout, 64, s,
+                             gather1 ? m->ws.tstats : nullptr, dt == DT_BF16),
             "performer1");
   }
   // iteration 2: soft_split1 (k3 s2 p1) of the [B, S/4, S/4, 64] map -> TokenPerformer (:72-77)
@@ -1258,12 +1284,12 @@ int evt_t2t_forward(evt_model* m, const float* img, int B, float* logits, void* 
     ProfScope ps(m, EVT_PROF_T2T_KQV, s);
     DenseCall c;
     c.flags = EPI_LNIN | EPI_BIAS | EPI_SPLIT;
-    c.A = m->pout; c.lda = 64; c.C = m->kqvb; c.ldc = 3 * 64; c.M = B * t2; c.N = 3 * 64;
-    c.stats_in = m->su; c.ln_width = P2.din;
+    c.A = m->ws.pout; c.lda = 64; c.C = m->ws.kqvb; c.ldc = 3 * 64; c.M = B * t2; c.N = 3 * 64;
+    c.stats_in = m->ws.su; c.ln_width = P2.din;
     GemmParams p = dense_params(m, P2.kqv, c);
-    p.gmode = 2; p.gR = g1; p.gC = 64; p.gOW = g2; p.gzero = m->zrow;
+    p.gmode = 2; p.gR = g1; p.gC = 64; p.gOW = g2; p.gzero = m->ws.zrow;
     p.g_inv_rr = 1.0f / (float)(g2 * g2); p.g_inv_r = 1.0f / (float)g2;
-    EVT_HIP(unfold_stats_launch(m->tstats, B, g1, m->su, stats_slots(P2.din), s),
+    EVT_HIP(unfold_stats_launch(m->ws.tstats, B, g1, m->ws.su, stats_slots(P2.din), s),
             "soft_split1 statistics");
     const hipError_t e = gemm_launch(dt, c.flags, p, s);
     if (e == hipSuccess) {
@@ -1279,39 +1305,39 @@ int evt_t2t_forward(evt_model* m, const float* img, int B, float* logits, void* 
       ProfScope ps(m, EVT_PROF_T2T_UNFOLD, s);
       prof_work(m, 0.0, (double)B * t1 * 64 * es + (double)B * t2 * P2.din * es +
                             (double)B * t2 * stats_slots(P2.din) * 8);
-      EVT_HIP(unfold_launch(dt, 0, m->pout, B, g1, g1, 64, 3, 2, 1, m->u, P2.dpad, m->su,
+      EVT_HIP(unfold_launch(dt, 0, m->ws.pout, B, g1, g1, 64, 3, 2, 1, m->ws.u, P2.dpad, m->ws.su,
                             stats_slots(P2.din), s),
               "soft_split1");
     }
     ProfScope ps(m, EVT_PROF_T2T_KQV, s);
     DenseCall c;
     c.flags = EPI_LNIN | EPI_BIAS;
-    c.A = m->u; c.lda = P2.dpad; c.C = m->kqvb; c.ldc = 3 * 64; c.M = B * t2; c.N = 3 * 64;
-    c.stats_in = m->su; c.ln_width = P2.din;
+    c.A = m->ws.u; c.lda = P2.dpad; c.C = m->ws.kqvb; c.ldc = 3 * 64; c.M = B * t2; c.N = 3 * 64;
+    c.stats_in = m->ws.su; c.ln_width = P2.din;
     EVT_RC(dense(m, P2.kqv, c, s));
   }
   {
     ProfScope ps(m, EVT_PROF_T2T_PERFORMER, s);
     prof_work(m, perf_flops * B * t2, (double)B * t2 * (3 * 64 + 64) * es);
-    EVT_HIP(performer_launch(dt, m->kqvb, 3 * 64, B, t2, P2.w, m->part, m->pout, 64, s, nullptr,
-                             dt == DT_BF16),
+    EVT_HIP(performer_launch(dt, m->ws.kqvb, 3 * 64, B, t2, P2.w, m->ws.part, m->ws.pout, 64, s,
+                             nullptr, dt == DT_BF16),
             "performer2");
   }
   // soft_split2 -> project Dense(D) into token rows 1..P, + CLS row, + sinusoid pos (:81-86,121-125)
   // (the split gathered inside the project GEMM's A loader where it can, as soft_split1)
   const int g3 = m->grid[2];
   bool fused2 = false;
-  if (dt == DT_BF16 && g3 == (g2 + 1) / 2 && m->zrow && m->pos_h) {
+  if (dt == DT_BF16 && g3 == (g2 + 1) / 2 && m->ws.zrow && m->pos_h) {
     ProfScope ps(m, EVT_PROF_PATCH_EMBED, s);
     prof_work(m, 0.0, (double)B * D * es + (double)B * stats_slots(D) * 8);
-    EVT_HIP(cls_rows_launch(dt, m->x, B, T, D, m->cls, m->pos, m->sx, s), "cls rows");
+    EVT_HIP(cls_rows_launch(dt, m->ws.x, B, T, D, m->cls, m->pos, m->ws.sx, s), "cls rows");
     DenseCall c;
     c.flags = EPI_BIAS | EPI_POS | EPI_STATS | EPI_SPLIT;
-    c.A = m->pout; c.lda = 64; c.C = m->x; c.ldc = D; c.M = B * P; c.N = D;
-    c.pos = m->pos; c.ldp = D; c.P = P; c.stats_out = m->sx;
+    c.A = m->ws.pout; c.lda = 64; c.C = m->ws.x; c.ldc = D; c.M = B * P; c.N = D;
+    c.pos = m->pos; c.ldp = D; c.P = P; c.stats_out = m->ws.sx;
     c.resid = m->pos_h; c.ldr = D;
     GemmParams p = dense_params(m, m->project, c);
-    p.gmode = 2; p.gR = g2; p.gC = 64; p.gOW = g3; p.gzero = m->zrow;
+    p.gmode = 2; p.gR = g2; p.gC = 64; p.gOW = g3; p.gzero = m->ws.zrow;
     p.g_inv_rr = 1.0f / (float)(g3 * g3); p.g_inv_r = 1.0f / (float)g3;
     const hipError_t e = gemm_launch(dt, c.flags, p, s);
     if (e == hipSuccess) {
@@ -1326,16 +1352,17 @@ int evt_t2t_forward(evt_model* m, const float* img, int B, float* logits, void* 
     {
       ProfScope ps(m, EVT_PROF_T2T_UNFOLD, s);
       prof_work(m, 0.0, (double)B * t2 * 64 * es + (double)B * P * 9 * 64 * es);
-      EVT_HIP(unfold_launch(dt, 0, m->pout, B, g2, g2, 64, 3, 2, 1, m->u, 9 * 64, nullptr, 0, s),
+      EVT_HIP(unfold_launch(dt, 0, m->ws.pout, B, g2, g2, 64, 3, 2, 1, m->ws.u, 9 * 64, nullptr, 0,
+                            s),
               "soft_split2");
     }
     ProfScope ps(m, EVT_PROF_PATCH_EMBED, s);
     prof_work(m, 0.0, (double)B * D * es + (double)B * stats_slots(D) * 8);
-    EVT_HIP(cls_rows_launch(dt, m->x, B, T, D, m->cls, m->pos, m->sx, s), "cls rows");
+    EVT_HIP(cls_rows_launch(dt, m->ws.x, B, T, D, m->cls, m->pos, m->ws.sx, s), "cls rows");
     DenseCall c;
     c.flags = EPI_BIAS | EPI_POS | EPI_STATS;
-    c.A = m->u; c.lda = 9 * 64; c.C = m->x; c.ldc = D; c.M = B * P; c.N = D;
-    c.pos = m->pos; c.ldp = D; c.P = P; c.stats_out = m->sx;
+    c.A = m->ws.u; c.lda = 9 * 64; c.C = m->ws.x; c.ldc = D; c.M = B * P; c.N = D;
+    c.pos = m->pos; c.ldp = D; c.P = P; c.stats_out = m->ws.sx;
     EVT_RC(dense(m, m->project, c, s));
   }
   EVT_RC(run_encoder(m, B, s));  // :127
@@ -1343,8 +1370,8 @@ int evt_t2t_forward(evt_model* m, const float* img, int B, float* logits, void* 
     ProfScope ps(m, EVT_PROF_HEAD, s);
     DenseCall c;
     c.flags = EPI_LNIN | EPI_BIAS | EPI_OUT_F32;
-    c.A = m->x; c.lda = (int64_t)T * D; c.C = logits; c.ldc = d.num_classes; c.M = B;
-    c.N = d.num_classes; c.stats_in = m->sx; c.stats_step = T;
+    c.A = m->ws.x; c.lda = (int64_t)T * D; c.C = logits; c.ldc = d.num_classes; c.M = B;
+    c.N = d.num_classes; c.stats_in = m->ws.sx; c.stats_step = T;
     EVT_RC(dense(m, m->head, c, s));
   }
   return EVT_OK;
@@ -1394,28 +1421,14 @@ int evt_model_set_lanes(evt_model* m, int lanes, void* stream) {
   const int per = (m->max_batch + lanes - 1) / lanes;
   auto run = [&]() -> int {
     for (int i = 0; i < lanes; ++i) {
-      // the copy shares the parent's weights (its allocations stay the parent's); everything
-      // per-model is reset and the workspace allocated anew for `per` images
-      evt_model* c = new evt_model(*m);
-      c->allocs.clear();
-      c->lanes.clear();
-      c->lane_s.clear();
-      c->lane_own.clear();
-      c->lane_ev.clear();
-      c->graph = nullptr;
-      c->graph_exec = nullptr;
-      c->prof = false;
-      c->prof_ev.clear();
-      c->prof_role.clear();
-      c->prof_gflop.clear();
-      c->prof_gbytes.clear();
+      // a fresh handle with a copy of the parent's core: it shares the weights (whose allocations
+      // stay the parent's) and nothing else, and allocates its own workspace for `per` images
+      evt_model* c = new evt_model();
+      static_cast<ModelCore&>(*c) = *m;
+      c->bind_desc();
       c->is_lane = true;
       c->max_batch = per;
       c->no_balance = m->family == 1 ? 1 : 0;
-      c->u = c->kqvb = c->pout = c->zrow = c->x = c->xm = c->qkv = c->o = c->hbuf = nullptr;
-      c->hh = c->sk = c->pooled = c->apatch = c->qa = c->qh = nullptr;
-      c->su = c->tstats = c->part = c->sx = c->sm = c->lnst = nullptr;
-      c->sa = c->shd = nullptr;
       m->lanes.push_back(c);
       EVT_RC(m->family == 0   ? vit_alloc_ws(c, per, s)
              : m->family == 1 ? t2t_alloc_ws(c, per, s)
@@ -1540,35 +1553,28 @@ static int swin_alloc_ws(evt_model* m, int B, hipStream_t s) {
   EVT_RC(validate_swin(&m->sdesc, &g));
   const SwinWs ws = swin_ws(g, B);
   const size_t es = elem_size(m->dtype);
-  EVT_RC(dev_alloc(m, &m->x, (ws.stream + SWIN_SLACK) * es));
-  EVT_RC(dev_alloc(m, &m->xm, (ws.stream + SWIN_SLACK) * es));
-  EVT_HIP(hipMemsetAsync(m->x, 0, (ws.stream + SWIN_SLACK) * es, s), "memset x");
-  EVT_HIP(hipMemsetAsync(m->xm, 0, (ws.stream + SWIN_SLACK) * es, s), "memset xm");
-  EVT_RC(dev_alloc(m, (void**)&m->sx, ws.stats * sizeof(float)));
-  EVT_RC(dev_alloc(m, (void**)&m->sm, ws.stats * sizeof(float)));
-  EVT_RC(dev_alloc(m, &m->qkv, ws.qkv * es));
-  EVT_RC(dev_alloc(m, &m->o, (ws.o + SWIN_SLACK) * es));
-  EVT_HIP(hipMemsetAsync(m->o, 0, (ws.o + SWIN_SLACK) * es, s), "memset o");
-  EVT_RC(dev_alloc(m, &m->hbuf, ws.hbuf * es));
-  EVT_RC(dev_alloc(m, &m->pooled, ws.pooled * es));
+  EVT_RC(dev_alloc(m, &m->ws.x, (ws.stream + SWIN_SLACK) * es));
+  EVT_RC(dev_alloc(m, &m->ws.xm, (ws.stream + SWIN_SLACK) * es));
+  EVT_HIP(hipMemsetAsync(m->ws.x, 0, (ws.stream + SWIN_SLACK) * es, s), "memset x");
+  EVT_HIP(hipMemsetAsync(m->ws.xm, 0, (ws.stream + SWIN_SLACK) * es, s), "memset xm");
+  EVT_RC(dev_alloc(m, (void**)&m->ws.sx, ws.stats * sizeof(float)));
+  EVT_RC(dev_alloc(m, (void**)&m->ws.sm, ws.stats * sizeof(float)));
+  EVT_RC(dev_alloc(m, &m->ws.qkv, ws.qkv * es));
+  EVT_RC(dev_alloc(m, &m->ws.o, (ws.o + SWIN_SLACK) * es));
+  EVT_HIP(hipMemsetAsync(m->ws.o, 0, (ws.o + SWIN_SLACK) * es, s), "memset o");
+  EVT_RC(dev_alloc(m, &m->ws.hbuf, ws.hbuf * es));
+  EVT_RC(dev_alloc(m, &m->ws.pooled, ws.pooled * es));
   if (m->dtype == DT_BF16) {
-    EVT_RC(dev_alloc(m, &m->sk, gemm_sk_bytes()));
-    EVT_HIP(hipMemsetAsync(m->sk, 0, 4096, s), "memset stream-K flags");
+    EVT_RC(dev_alloc(m, &m->ws.sk, gemm_sk_bytes()));
+    EVT_HIP(hipMemsetAsync(m->ws.sk, 0, 4096, s), "memset stream-K flags");
   }
-  m->ws_bytes = swin_workspace_bytes(&m->sdesc, g, B);
   return EVT_OK;
 }
 
 int evt_swin_create(const evt_swin_desc* desc, const float* const* w, int n_weights, void* stream,
                     evt_model** out) {
-  if (!out) return fail(EVT_EINVAL, "out is NULL");
-  *out = nullptr;
   SwinGeo g;
-  EVT_RC(validate_swin(desc, &g));
-  if (n_weights != evt_swin_num_weights(desc) || !w)
-    return fail(EVT_EINVAL, "expected " + std::to_string(evt_swin_num_weights(desc)) + " weights");
-  for (int i = 0; i < n_weights; ++i)
-    if (!w[i]) return fail(EVT_EINVAL, "weight pointer " + std::to_string(i) + " is NULL");
+  EVT_RC(create_prologue(desc, validate_swin, &g, evt_swin_num_weights, w, n_weights, out));
   hipStream_t s = (hipStream_t)stream;
   evt_model* m = new evt_model();
   m->family = 2;
@@ -1577,6 +1583,7 @@ int evt_swin_create(const evt_swin_desc* desc, const float* const* w, int n_weig
   m->max_batch = desc->max_batch;
   m->num_classes = desc->num_classes;
   m->sdesc = *desc;
+  m->img_elems = (size_t)desc->in_chans * desc->image_size * desc->image_size;
   auto run = [&]() -> int {
     const int E = desc->embed_dim;
     int k = 0;
@@ -1625,15 +1632,10 @@ int evt_swin_create(const evt_swin_desc* desc, const float* const* w, int n_weig
 }
 
 int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void* stream) {
-  if (!m || !img || !logits) return fail(EVT_EINVAL, "model, img and logits must be non-null");
-  if (m->family != 2) return fail(EVT_EINVAL, "model is not a Swin Transformer");
-  if (B <= 0 || B > m->max_batch)
-    return fail(EVT_EINVAL, "batch must be in [1, max_batch=" + std::to_string(m->max_batch) + "]");
   hipStream_t s = (hipStream_t)stream;
-  if (!m->lanes.empty() && !m->prof && B >= (int)m->lanes.size())  // profiling: one lane
-    return lanes_forward(m, evt_swin_forward, img,
-                         (size_t)m->sdesc.in_chans * m->sdesc.image_size * m->sdesc.image_size, B,
-                         logits, s);
+  const int pre = forward_prologue(m, 2, "model is not a Swin Transformer", evt_swin_forward, img,
+                                   B, logits, s);
+  if (pre != RUN_HERE) return pre;
   prof_reset(m);
   const evt_swin_desc& d = m->sdesc;
   const int dt = d.dtype;
@@ -1653,7 +1655,7 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
                   (double)rows * stats_slots(96) * 8);
     SwinEmbedParams ep;
     ep.img = img; ep.w = m->patch.w; ep.ldw = m->patch.kpad; ep.bias = m->patch.b;
-    ep.gamma = m->pnorm_g; ep.beta = m->pnorm_b; ep.x = m->x; ep.stats = m->sx;
+    ep.gamma = m->pnorm_g; ep.beta = m->pnorm_b; ep.x = m->ws.x; ep.stats = m->ws.sx;
     ep.B = B; ep.S = d.image_size; ep.nslots = stats_slots(96); ep.eps = 1e-5f;
     EVT_HIP(swin_embed96_launch(ep, s), "fused patch embedding");
   } else {
@@ -1661,18 +1663,19 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
     ProfScope ps(m, EVT_PROF_PATCHIFY, s);
     prof_work(m, 0.0, (double)B * d.in_chans * d.image_size * d.image_size * 4 +
                           (double)rows * d.in_chans * d.patch_size * d.patch_size * es);
-    EVT_HIP(swin_patch_launch(dt, img, B, d.in_chans, d.image_size, d.patch_size, m->hbuf, pdst, s),
+    EVT_HIP(swin_patch_launch(dt, img, B, d.in_chans, d.image_size, d.patch_size, m->ws.hbuf, pdst,
+                              s),
             "patch im2col");
   }
   {
     ProfScope ps(m, EVT_PROF_PATCH_EMBED, s);
     DenseCall c;
     c.flags = EPI_BIAS;
-    c.A = m->hbuf; c.lda = pdst; c.C = m->xm; c.ldc = s0.Cst; c.M = rows; c.N = s0.Cst;
+    c.A = m->ws.hbuf; c.lda = pdst; c.C = m->ws.xm; c.ldc = s0.Cst; c.M = rows; c.N = s0.Cst;
     EVT_RC(dense(m, m->patch, c, s));
     prof_work(m, 0.0, 2.0 * rows * s0.C * es + (double)rows * stats_slots(s0.C) * 8);
-    EVT_HIP(ln_rows_launch(dt, m->xm, s0.Cst, m->x, m->pnorm_g, m->pnorm_b, rows, s0.C, 1e-5f,
-                           m->sx, stats_slots(s0.C), s),
+    EVT_HIP(ln_rows_launch(dt, m->ws.xm, s0.Cst, m->ws.x, m->pnorm_g, m->pnorm_b, rows, s0.C, 1e-5f,
+                           m->ws.sx, stats_slots(s0.C), s),
             "patch norm");
   }
   }
@@ -1685,26 +1688,27 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
       ProfScope ps(m, EVT_PROF_MERGE, s);
       DenseCall c;
       c.flags = EPI_LNIN | EPI_BIAS | EPI_STATS;
-      c.C = m->x; c.ldc = Cst; c.M = rows; c.N = Cst;
-      c.stats_in = m->sm; c.stats_out = m->sx; c.ln_width = 4 * pv.C; c.slot_width = C;
+      c.C = m->ws.x; c.ldc = Cst; c.M = rows; c.N = Cst;
+      c.stats_in = m->ws.sm; c.stats_out = m->ws.sx; c.ln_width = 4 * pv.C; c.slot_width = C;
       bool fused = false;
       if (dt == DT_BF16 && pv.Cst == pv.C && pv.R % 2 == 0) {
         // the gather inside the reduction GEMM's A loader (gemm.hip, EPI_GATHER): A = the old
         // stream, read in place, so the new stream goes to xm and the two buffers swap roles
         DenseCall g = c;
         g.flags |= EPI_GATHER;
-        g.A = m->x; g.lda = pv.Cst; g.C = m->xm;
+        g.A = m->ws.x; g.lda = pv.Cst; g.C = m->ws.xm;
         GemmParams p = dense_params(m, st.merge, g);
         const int R2 = pv.R / 2;
         p.gmode = 1; p.gR = pv.R; p.gC = pv.C; p.gOW = R2;
         p.g_inv_rr = 1.0f / (float)(R2 * R2); p.g_inv_r = 1.0f / (float)R2;
-        EVT_HIP(merge_stats_launch(m->sx, stats_slots(pv.C), B, pv.R, m->sm, stats_slots(C), s),
+        EVT_HIP(merge_stats_launch(m->ws.sx, stats_slots(pv.C), B, pv.R, m->ws.sm, stats_slots(C),
+                                   s),
                 "merge statistics");
         const hipError_t e = gemm_launch(dt, g.flags, p, s);
         if (e == hipSuccess) {
-          c.A = m->x; c.lda = 4 * pv.C;  // (work accounting: the same A bytes, gathered)
+          c.A = m->ws.x; c.lda = 4 * pv.C;  // (work accounting: the same A bytes, gathered)
           dense_work(m, st.merge, c);
-          std::swap(m->x, m->xm);
+          std::swap(m->ws.x, m->ws.xm);
           fused = true;
         } else if (e != hipErrorNotSupported) {
           EVT_HIP(e, "patch merge (gathered)");
@@ -1712,9 +1716,10 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
       }
       if (!fused) {
         prof_work(m, 0.0, 2.0 * rows * 4 * pv.C * es + (double)rows * stats_slots(C) * 8);
-        EVT_HIP(merge_launch(dt, m->x, pv.Cst, B, pv.R, pv.C, m->hbuf, m->sm, stats_slots(C), s),
+        EVT_HIP(merge_launch(dt, m->ws.x, pv.Cst, B, pv.R, pv.C, m->ws.hbuf, m->ws.sm,
+                             stats_slots(C), s),
                 "patch merge");
-        c.A = m->hbuf; c.lda = 4 * pv.C;
+        c.A = m->ws.hbuf; c.lda = 4 * pv.C;
         EVT_RC(dense(m, st.merge, c, s));
       }
     }
@@ -1726,7 +1731,7 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
         ProfScope ps(m, EVT_PROF_ATTN_SUBLAYER, s);
         prof_work(m, 2.0 * rows * C * 4 * C + 4.0 * rows * 49 * C,
                   2.0 * rows * C * es + 2 * slot_rows + 4.0 * C * C * es);
-        SwinAttnBlockParams ab{m->x, m->xm, m->sx, m->sm, bl.qkv.w, bl.qkv.b, bl.proj.w,
+        SwinAttnBlockParams ab{m->ws.x, m->ws.xm, m->ws.sx, m->ws.sm, bl.qkv.w, bl.qkv.b, bl.proj.w,
                                bl.proj.b, bl.bias, bl.qkv.kpad, bl.proj.kpad, B, st.R, bl.shift,
                                stats_slots(C), m->eps};
         EVT_HIP(swin_attn96_launch(ab, s), "fused window attention sublayer");
@@ -1736,14 +1741,14 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
           ProfScope ps(m, EVT_PROF_QKV, s);
           DenseCall c;
           c.flags = EPI_LNIN | EPI_BIAS;
-          c.A = m->x; c.lda = Cst; c.C = m->qkv; c.ldc = 3 * C; c.M = rows; c.N = 3 * C;
-          c.stats_in = m->sx; c.ln_width = C;
+          c.A = m->ws.x; c.lda = Cst; c.C = m->ws.qkv; c.ldc = 3 * C; c.M = rows; c.N = 3 * C;
+          c.stats_in = m->ws.sx; c.ln_width = C;
           EVT_RC(dense(m, bl.qkv, c, s));
         }
         {
           ProfScope ps(m, EVT_PROF_ATTENTION, s);
           prof_work(m, 4.0 * rows * st.w * st.w * C, 4.0 * rows * C * es);  // w^2 keys per query
-          SwinAttnParams ap{m->qkv, 3 * C, m->o, Cst, bl.bias, B, st.R, st.R / st.w, C, st.H,
+          SwinAttnParams ap{m->ws.qkv, 3 * C, m->ws.o, Cst, bl.bias, B, st.R, st.R / st.w, C, st.H,
                             bl.shift, scale_log2};
           EVT_HIP(st.w == 12 ? window12_attn_launch(dt, ap, s) : window_attn_launch(dt, ap, s),
                   "window attention");
@@ -1751,8 +1756,8 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
         ProfScope ps(m, EVT_PROF_OUT_PROJ, s);
         DenseCall pc;  // proj + bias + residual x -> xm (+ stats)
         pc.flags = EPI_BIAS | EPI_RESID | EPI_STATS;
-        pc.A = m->o; pc.lda = Cst; pc.C = m->xm; pc.ldc = Cst; pc.M = rows; pc.N = Cst;
-        pc.resid = m->x; pc.ldr = Cst; pc.stats_out = m->sm; pc.ln_width = C;
+        pc.A = m->ws.o; pc.lda = Cst; pc.C = m->ws.xm; pc.ldc = Cst; pc.M = rows; pc.N = Cst;
+        pc.resid = m->ws.x; pc.ldr = Cst; pc.stats_out = m->ws.sm; pc.ln_width = C;
         EVT_RC(dense(m, bl.proj, pc, s));
       }
       if (dt == DT_BF16 && C == 96 && st.mlp == 384 && st.w == 7 && gemm_auto()) {
@@ -1760,7 +1765,7 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
         ProfScope ps(m, EVT_PROF_MLP, s);
         prof_work(m, 4.0 * rows * C * st.mlp, 2.0 * rows * C * es + 2 * slot_rows +
                                                    2.0 * C * st.mlp * es);
-        SwinMlpParams mp{m->xm, m->x, m->sm, m->sx, bl.fc1.w, bl.fc1.colsum, bl.fc1.b,
+        SwinMlpParams mp{m->ws.xm, m->ws.x, m->ws.sm, m->ws.sx, bl.fc1.w, bl.fc1.colsum, bl.fc1.b,
                          bl.fc2.w, bl.fc2.b, bl.fc1.kpad, bl.fc2.kpad, rows, stats_slots(C),
                          m->eps};
         EVT_HIP(swin_mlp96_launch(mp, s), "fused MLP");
@@ -1770,16 +1775,16 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
         ProfScope ps(m, EVT_PROF_FC1, s);
         DenseCall c;
         c.flags = EPI_LNIN | EPI_BIAS | EPI_GELU_ERF;
-        c.A = m->xm; c.lda = Cst; c.C = m->hbuf; c.ldc = st.mst; c.M = rows; c.N = st.mst;
-        c.stats_in = m->sm; c.ln_width = C;
+        c.A = m->ws.xm; c.lda = Cst; c.C = m->ws.hbuf; c.ldc = st.mst; c.M = rows; c.N = st.mst;
+        c.stats_in = m->ws.sm; c.ln_width = C;
         EVT_RC(dense(m, bl.fc1, c, s));
       }
       {  // FC2 + bias + residual xm -> x (+ stats)
         ProfScope ps(m, EVT_PROF_FC2, s);
         DenseCall c;
         c.flags = EPI_BIAS | EPI_RESID | EPI_STATS;
-        c.A = m->hbuf; c.lda = st.mst; c.C = m->x; c.ldc = Cst; c.M = rows; c.N = Cst;
-        c.resid = m->xm; c.ldr = Cst; c.stats_out = m->sx; c.ln_width = C;
+        c.A = m->ws.hbuf; c.lda = st.mst; c.C = m->ws.x; c.ldc = Cst; c.M = rows; c.N = Cst;
+        c.resid = m->ws.xm; c.ldr = Cst; c.stats_out = m->ws.sx; c.ln_width = C;
         EVT_RC(dense(m, bl.fc2, c, s));
       }
     }
@@ -1789,13 +1794,13 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
   ProfScope ps_head(m, EVT_PROF_HEAD, s);
   prof_work(m, 0.0, (double)B * sl.R * sl.R * sl.C * es + (double)B * sl.R * sl.R * stats_slots(sl.C) * 8 +
                         (double)B * sl.C * es);
-  EVT_HIP(ln_pool_launch(dt, m->x, sl.Cst, B, sl.R * sl.R, sl.C, m->sx, stats_slots(sl.C),
-                         m->norm_g, m->norm_b, m->pooled, sl.Cst, s),
+  EVT_HIP(ln_pool_launch(dt, m->ws.x, sl.Cst, B, sl.R * sl.R, sl.C, m->ws.sx, stats_slots(sl.C),
+                         m->norm_g, m->norm_b, m->ws.pooled, sl.Cst, s),
           "norm + avgpool");
   {
     DenseCall c;
     c.flags = EPI_BIAS | EPI_OUT_F32;
-    c.A = m->pooled; c.lda = sl.Cst; c.C = logits; c.ldc = d.num_classes; c.M = B;
+    c.A = m->ws.pooled; c.lda = sl.Cst; c.C = logits; c.ldc = d.num_classes; c.M = B;
     c.N = d.num_classes;
     EVT_RC(dense(m, m->head, c, s));
   }

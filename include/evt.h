@@ -142,6 +142,9 @@ int evt_model_set_lanes(evt_model* model, int lanes, void* stream);
  * from the other lanes' (HIP gives a new stream the least-used of GPU_MAX_HW_QUEUES queues; two
  * lanes on one queue run one after the other). Synchronises the device. */
 int evt_model_set_lane_streams(evt_model* model, int n, void* const* streams);
+/* evt_model_set_lanes, evt_model_set_lane_streams and evt_model_destroy synchronise the whole
+ * device (hipDeviceSynchronize): they are setup-time calls, not to be made while any stream of the
+ * process is being captured into a HIP graph. */
 /* The handle's lane count (1 without lanes). */
 int evt_model_lanes(const evt_model* model, int* lanes);
 

@@ -77,6 +77,34 @@ def test_lanes_odd_splits(gpu, name, mod, layout, dtype, lanes, batch):
         lo = hi
 
 
+@pytest.mark.parametrize("dtype", ["bf16", "mx8"])
+def test_lanes_own_workspace_small_vit(gpu, dtype):
+    """The ViT configurations whose lanes hold workspace the cases above never lane: bf16 (stream-K
+    scratch, the patch matrix aliasing the FFN hidden buffer, the head's split-K partials in it)
+    and MXFP8 (the quantized operands, their scales and the LayerNorm row statistics). The config
+    is the small ViT as given (image 32, patch 16, dim 64, one head of 64, FFN 128, 10 classes),
+    which the MX8 validation accepts. A buffer shared between two lanes would be written from two
+    streams at once: each lane's rows must equal the one-lane handle's forward of that part
+    bitwise, and repeated laned forwards must return the same bits."""
+    kw = dict(image_size=32, patch_size=16, num_classes=10, dim=64, depth=2, heads=1, mlp_dim=128,
+              dtype=dtype, seed=0, max_batch=6, device=gpu)
+    m2, m1 = vit.ViT(lanes=2, **kw), vit.ViT(lanes=1, **kw)
+    assert m2.lanes() == 2 and m1.lanes() == 1
+    full = torch.from_numpy(make_images(6, seed=43, image_size=32)).to(gpu)
+    for batch in (6, 5):  # 3 + 3 and 2 + 3
+        img = full[:batch].contiguous()
+        a = m2(img)
+        torch.cuda.synchronize()
+        assert torch.isfinite(a).all()
+        lo = 0
+        for i in range(2):
+            hi = batch * (i + 1) // 2
+            assert torch.equal(a[lo:hi], m1(img[lo:hi].contiguous()))
+            lo = hi
+        for _ in range(2):  # three laned forwards in all: identical bits
+            assert torch.equal(m2(img), a)
+
+
 def test_lanes_errors(gpu):
     lib = _lib.load_library()
     m = vit.build_named("deit_tiny", dtype="bf16", seed=0, max_batch=4)
