@@ -151,6 +151,10 @@ SIGNATURES = {
     "evt_mx8_layernorm": (_I, [_P, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P]),
     "evt_attention_mx8": (_I, [_P, _I64, _P, _I64, _P, _I64, _I, _I, _I, _F, _P]),
 }
+# the entry points of include/evt_patchify.h (evt.h includes it; bound like SIGNATURES)
+EXT_SIGNATURES = {
+    "evt_patchify_ld": (_I, [_I, _P, _I, _I, _I, _I, _P, _I64, _P, _P, _P, _I, _P, _P]),
+}
 
 _lib = None
 _lock = threading.Lock()
@@ -171,7 +175,7 @@ def load_library() -> ctypes.CDLL:
             # entry points added since: those stay unbound there; the in-tree library must export
             # every one (tests/test_capi.py)
             lenient = "EVT_LIB" in os.environ
-            for name, (res, args) in SIGNATURES.items():
+            for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES}.items():
                 if lenient and not hasattr(lib, name):
                     continue
                 fn = getattr(lib, name)

@@ -81,6 +81,7 @@ struct Layer {
 
 struct Shape {
   int P = 0, T = 0, pd = 0, D = 0, max_inner = 0, max_ffn_st = 0, head_st = 0;
+  int pdst = 0;  // ViT: row stride of the patch matrix, pd rounded up to PAD_K (patch 14: 640)
 };
 
 }  // namespace
@@ -120,6 +121,8 @@ struct ModelCore {
   // creation keeps the token-major layout (the A/B and bitwise-equality tests)
   bool headmajor = qkv_headmajor_default();
   bool patch_cm = false;     // ViT: channel-major patch vectors / patch weight rows
+  bool patch_ld = false;     // ViT: pd % 64 != 0 (patch 14): channel-major rows at the padded
+                             // stride sh.pdst with a zeroed tail (patchify_ld_kernel)
   float eps = 1e-5f;         // LayerNorm epsilon of every folded LayerNorm
   int dtype = 0, D = 0, num_classes = 0;
   size_t img_elems = 0;      // fp32 elements of one input image
@@ -159,7 +162,7 @@ struct Workspace {
   void* zrow = nullptr;      // 256 zero bytes: the soft split's padding rows (gathered loader)
   float* part = nullptr;     // performer partial sums
   // token stream (activation dtype unless noted)
-  void* apatch = nullptr;    // [B*P, pd] patch matrix (aliases hbuf)
+  void* apatch = nullptr;    // [B*P, pdst] patch matrix (aliases hbuf)
   void* x = nullptr;         // [B*T, D] token stream at layer input / output
   void* xm = nullptr;        // [B*T, D] token stream between the two sublayers
   float* sx = nullptr;       // [B*T, nslots, 2] fp32 per-slab (sum, sumsq) of x rows
@@ -266,8 +269,11 @@ int validate(const evt_vit_desc* d, Shape* sh) {
     return fail(EVT_EINVAL, "image dimensions must be divisible by the patch size");
   if (d->in_chans <= 0 || d->num_classes <= 0 || d->depth < 0 || d->mlp_dim <= 0)
     return fail(EVT_EINVAL, "in_chans, num_classes, mlp_dim must be positive, depth >= 0");
-  if (d->dim <= 0 || d->dim % 8 != 0 || d->dim > 1024)
-    return fail(EVT_EINVAL, "dim must be a positive multiple of 8 and <= 1024");
+  if (d->dim <= 0 || d->dim % 8 != 0 || d->dim > 1536)
+    return fail(EVT_EINVAL, "dim must be a positive multiple of 8 and <= 1536");
+  if (d->dtype == EVT_DTYPE_MX8 && d->dim > 1024)
+    return fail(EVT_EINVAL, "EVT_DTYPE_MX8 supports dim <= 1024 (the MX8 LayerNorm quantizer holds "
+                            "rows of at most 1024 columns); wider models run in bf16 or f32");
   if (d->dtype == EVT_DTYPE_MX8 && d->dim % 64 != 0)
     return fail(EVT_EINVAL, "EVT_DTYPE_MX8 needs dim % 64 == 0");
   if (d->max_batch <= 0) return fail(EVT_EINVAL, "max_batch must be positive");
@@ -285,7 +291,8 @@ int validate(const evt_vit_desc* d, Shape* sh) {
     return fail(EVT_EINVAL, "EVT_DTYPE_MX8 supports at most 255 patches per image (its attention "
                             "kernel writes MX8 output for up to 256 tokens only)");
   sh->pd = d->patch_size * d->patch_size * d->in_chans;
-  if (sh->pd % PAD_K) return fail(EVT_EINVAL, "patch_size^2 * in_chans must be a multiple of 64");
+  // pd % 64 != 0 (patch 14: 588): rows at the next multiple of 64, the tail zeroed by the kernel
+  sh->pdst = (int)round_up(sh->pd, PAD_K);
   if (d->patch_size * d->image_size % 4)
     return fail(EVT_EINVAL, "patch_size * image_size must be a multiple of 4");
   if ((size_t)d->in_chans * d->patch_size * d->image_size * 4 > 160 * 1024)
@@ -314,7 +321,7 @@ int validate(const evt_vit_desc* d, Shape* sh) {
     const size_t es = d->dtype == EVT_DTYPE_F32 ? 4 : 2, B = (size_t)d->max_batch;
     const size_t widest = std::max<size_t>({(size_t)3 * sh->max_inner, (size_t)sh->max_ffn_st,
                                             (size_t)sh->D});
-    const size_t big = std::max({B * sh->T * widest * es, B * sh->P * sh->pd * es,
+    const size_t big = std::max({B * sh->T * widest * es, B * sh->P * sh->pdst * es,
                                  B * d->in_chans * d->image_size * d->image_size * sizeof(float)});
     if (big >= (size_t)1 << 31)
       return fail(EVT_EINVAL, "max_batch too large for more than 256 tokens per image: every "
@@ -393,7 +400,7 @@ size_t workspace_bytes(const evt_vit_desc* d, const Shape& sh, int B) {
   const bool mx8 = d->dtype == EVT_DTYPE_MX8;
   const size_t es = elem_size(mx8 ? DT_BF16 : d->dtype);
   const size_t rows = (size_t)B * sh.T;
-  const size_t hb = std::max(rows * sh.max_ffn_st, (size_t)B * sh.P * sh.pd) * es;
+  const size_t hb = std::max(rows * sh.max_ffn_st, (size_t)B * sh.P * sh.pdst) * es;
   size_t extra = 0;
   if (mx8) {  // qa + sa, qh + its scales, LayerNorm row statistics (run_encoder_mx8)
     const size_t qa = std::max(round_up(sh.D, 128), round_up(sh.max_inner, 128));
@@ -567,7 +574,10 @@ int dense_head(const evt_model* m, const DenseW& w, const DenseCall& c, hipStrea
   const int tiles = ((c.M + GEMM_BM - 1) / GEMM_BM) * (w.npad / GEMM_BN);
   int S = 1;
   while (S < 8 && tiles * S * 2 <= device_cus() && w.kpad % (S * 2 * PAD_K) == 0) S *= 2;
-  const size_t part = (size_t)S * c.M * w.npad * sizeof(float);
+  // sized for the handle's max_batch, not this call's M: whether the partials fit the hidden buffer
+  // (they always do from about 20 tokens per image; 5-token models are where it matters) must not
+  // depend on the batch, or one image alone and the same image in a batch take different sums
+  const size_t part = (size_t)S * std::max(c.M, m->max_batch) * w.npad * sizeof(float);
   if (S < 2 || !m->ws.hbuf || part > m->ws.hbuf_bytes ||
       (c.flags & ~(EPI_BIAS | EPI_GELU | EPI_OUT_F32)))
     return dense(m, w, c, s);
@@ -1006,7 +1016,7 @@ static int vit_alloc_ws(evt_model* m, int B, hipStream_t s) {
   const int D = m->D;
   const size_t es = elem_size(m->dtype);
   EVT_RC(alloc_encoder_ws(m, B, std::max((size_t)B * sh.T * sh.max_ffn_st,
-                                         (size_t)B * sh.P * sh.pd) * es, s));
+                                         (size_t)B * sh.P * sh.pdst) * es, s));
   m->ws.apatch = m->ws.hbuf;
   EVT_RC(dev_alloc(m, &m->ws.hh, (size_t)B * sh.head_st * es));
   if (m->mx8) {
@@ -1053,12 +1063,15 @@ int evt_vit_create(const evt_vit_desc* desc, const float* const* w, int n_weight
   m->img_elems = (size_t)desc->in_chans * desc->image_size * desc->image_size;
   const int D = desc->dim;
   auto run = [&]() -> int {
-    if (desc->patch_size % 8 == 0) {  // channel-major patch vectors (patchify_cm_kernel)
+    m->patch_ld = sh.pd % PAD_K != 0;
+    if (desc->patch_size % 8 == 0 || m->patch_ld) {
+      // channel-major patch vectors (patchify_cm_kernel; patchify_ld_kernel with its rows padded
+      // to sh.pdst columns: make_dense packs K = pd rows and zero rows up to kpad = pdst)
       float* wcm = nullptr;
       EVT_RC(dev_alloc(m, (void**)&wcm, (size_t)sh.pd * D * sizeof(float)));
       EVT_HIP(patch_weight_cm(w[0], wcm, desc->in_chans, desc->patch_size, D, s), "patch weight");
       EVT_RC(make_dense(m, &m->patch, wcm, w[1], sh.pd, D, s));
-      m->patch_cm = true;
+      m->patch_cm = !m->patch_ld;
     } else {
       EVT_RC(make_dense(m, &m->patch, w[0], w[1], sh.pd, D, s));
     }
@@ -1097,17 +1110,22 @@ int evt_vit_forward(evt_model* m, const float* img, int B, float* logits, void* 
   {
     ProfScope ps(m, EVT_PROF_PATCHIFY, s);
     prof_work(m, 0.0, (double)B * d.in_chans * d.image_size * d.image_size * 4 +
-                          (double)B * (sh.P * sh.pd + D) * elem_size(dt) +
+                          (double)B * (sh.P * sh.pdst + D) * elem_size(dt) +
                           (double)B * stats_slots(D) * 8);  // image read, patch rows + CLS rows
-    EVT_HIP(patchify_launch(dt, img, B, d.in_chans, d.image_size, d.patch_size, m->ws.apatch,
-                            m->ws.x, m->cls, m->pos, D, m->ws.sx, s, m->patch_cm),
-            "patchify");
+    if (m->patch_ld)
+      EVT_HIP(patchify_ld_launch(dt, img, B, d.in_chans, d.image_size, d.patch_size, m->ws.apatch,
+                                 sh.pdst, m->ws.x, m->cls, m->pos, D, m->ws.sx, s),
+              "patchify");
+    else
+      EVT_HIP(patchify_launch(dt, img, B, d.in_chans, d.image_size, d.patch_size, m->ws.apatch,
+                              m->ws.x, m->cls, m->pos, D, m->ws.sx, s, m->patch_cm),
+              "patchify");
   }
   {
     ProfScope ps(m, EVT_PROF_PATCH_EMBED, s);
     DenseCall c;
     c.flags = EPI_BIAS | EPI_POS | EPI_STATS;
-    c.A = m->ws.apatch; c.lda = sh.pd; c.C = m->ws.x; c.ldc = D; c.M = B * sh.P; c.N = D;
+    c.A = m->ws.apatch; c.lda = sh.pdst; c.C = m->ws.x; c.ldc = D; c.M = B * sh.P; c.N = D;
     c.pos = m->pos; c.ldp = D; c.P = sh.P; c.stats_out = m->ws.sx;
     c.resid = m->pos_h; c.ldr = m->pos_h ? D : 0;  // bf16 table for the persistent kernel
     EVT_RC(dense(m, m->patch, c, s));
@@ -2069,6 +2087,22 @@ int evt_patchify_cm(int dtype, const float* img, int B, int C, int HW, int ps, v
   EVT_HIP(patchify_launch(dtype, img, B, C, HW, ps, out, x, cls, pos, D, stats,
                           (hipStream_t)stream, true),
           "patchify_cm");
+  return EVT_OK;
+}
+
+int evt_patchify_ld(int dtype, const float* img, int B, int C, int HW, int ps, void* out,
+                    int64_t ldo, void* x, const float* cls, const float* pos, int D, float* stats,
+                    void* stream) {
+  if (dtype != EVT_DTYPE_F32 && dtype != EVT_DTYPE_BF16)
+    return fail(EVT_EINVAL, "patchify_ld: dtype must be EVT_DTYPE_F32 or EVT_DTYPE_BF16");
+  if (B < 0 || D <= 0 || !patchify_ld_ok(C, HW, ps, ldo))
+    return fail(EVT_EINVAL, "patchify_ld: bad shape (HW % ps == 0, ps*HW % 4 == 0, ldo >= ps*ps*C, "
+                            "ldo % 8 == 0, C*ps*HW*4 <= 160 KiB)");
+  if (!img || !out || !x || !cls || !pos || ((uintptr_t)out & 15))
+    return fail(EVT_EINVAL, "patchify_ld: img, out, x, cls, pos must be non-null, out 16-B aligned");
+  EVT_HIP(patchify_ld_launch(dtype, img, B, C, HW, ps, out, ldo, x, cls, pos, D, stats,
+                             (hipStream_t)stream),
+          "patchify_ld");
   return EVT_OK;
 }
 

@@ -140,6 +140,14 @@ __host__ __device__ inline int stats_slots(int D) { return 2 * ((D + 255) / 256)
 hipError_t patchify_launch(int dtype, const float* img, int B, int C, int HW, int ps, void* out,
                            void* x, const float* cls, const float* pos, int D, float* stats,
                            hipStream_t s, bool channel_major = false);
+// Any patch size: the channel-major patch vectors written at row stride ldo (elements), columns
+// [ps*ps*C, ldo) as zeros on every launch; CLS row and statistics as patchify_launch. The shapes
+// it takes (patchify_ld_ok): HW % ps == 0, ps*HW % 4 == 0, ldo >= ps*ps*C, ldo % 8 == 0, an LDS
+// strip C*ps*HW*4 <= 160 KiB; out 16-B aligned. The weight rows: patch_weight_cm, zero padded.
+bool patchify_ld_ok(int C, int HW, int ps, int64_t ldo);
+hipError_t patchify_ld_launch(int dtype, const float* img, int B, int C, int HW, int ps, void* out,
+                              int64_t ldo, void* x, const float* cls, const float* pos, int D,
+                              float* stats, hipStream_t s);
 // Keras patch_to_embedding kernel W [(p1 p2 c), N] -> Wcm [(c p1 p2), N] (rows permuted).
 hipError_t patch_weight_cm(const float* W, float* Wcm, int C, int ps, int N, hipStream_t s);
 

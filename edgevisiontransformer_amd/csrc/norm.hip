@@ -198,6 +198,106 @@ __global__ __launch_bounds__(256) void patchify_cm_kernel(const float* __restric
   }
 }
 
+// Patch vectors of any patch size at a padded row stride: out[patch][k] for k < ldo, with
+// k = (c ps + p1) ps + p2 below pd = ps ps C (the channel-major order of patchify_cm_kernel, so
+// patch_weight_cm packs the matching weight rows) and 0 from pd up to ldo. The GEMM reads its A
+// operand in 64-column K-tiles at a row stride that is a multiple of 64; a patch of 14 has pd = 588,
+// so the rows are written 640 apart and the 52 columns of padding are zeros written here, on every
+// launch: the patch matrix shares its buffer with the FFN hidden activations, and a stale NaN in
+// the padding would survive the zero weight rows (NaN * 0).
+// k = r ps + p2 with run r = c ps + p1, and run r of patch ww starts at strip[r HW + ww ps] (the
+// strip is [C ps][HW]): one division by ps per 8-element chunk, then the chunk walks p2 and steps
+// HW - ps floats at a run end. Every thread owns one chunk of 8 consecutive k: one 16-B store
+// (bf16) or two (f32), the zero tail included. Even ps: k, pd and every run start are even, so the
+// chunk is four 8-B LDS reads (a pair never crosses a run end or pd); odd ps: eight 4-B reads.
+// grid (HW/ps, B); ldo % 8 == 0, ldo >= pd, out 16-B aligned.
+template <typename TO>
+__global__ __launch_bounds__(256) void patchify_ld_kernel(const float* __restrict__ img, int C,
+                                                          int HW, int ps, TO* __restrict__ out,
+                                                          int ldo, TO* __restrict__ x,
+                                                          const float* __restrict__ cls,
+                                                          const float* __restrict__ pos, int D,
+                                                          float* __restrict__ stats) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* strip = (float*)smem;
+  const int hh = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int np = HW / ps;
+  const int per_c = ps * HW;  // multiple of 4 (checked on the host)
+  for (int c = 0; c < C; ++c) {
+    const float* src = img + (((int64_t)b * C + c) * HW + (int64_t)hh * ps) * HW;
+    for (int i = tid * 4; i < per_c; i += 256 * 4) *(f32x4*)(strip + c * per_c + i) = load4(src + i);  // LDS
+  }
+  __syncthreads();
+  const int pd = ps * ps * C;
+  const int cpl = ldo >> 3;  // 8-element chunks per output row
+  const bool pairs = (ps & 1) == 0;
+  const int step = HW - ps;  // from the end of a run to the start of the next
+  TO* orow = out + ((int64_t)b * np * np + (int64_t)hh * np) * ldo;
+  for (int e = tid; e < np * cpl; e += 256) {
+    const int ww = e / cpl, k0 = (e - ww * cpl) * 8;
+    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (k0 < pd) {
+      const int r = k0 / ps;
+      int p2 = k0 - r * ps;
+      const float* sp = strip + r * HW + ww * ps + p2;
+      if (pairs) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (k0 + 2 * j < pd) {
+            const f32x2 t = *(const f32x2*)sp;
+            v[2 * j] = t[0];
+            v[2 * j + 1] = t[1];
+          }
+          sp += 2;
+          p2 += 2;
+          if (p2 == ps) {
+            p2 = 0;
+            sp += step;
+          }
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if (k0 + j < pd) v[j] = *sp;
+          ++sp;
+          if (++p2 == ps) {
+            p2 = 0;
+            sp += step;
+          }
+        }
+      }
+    }
+    TO* op = orow + (int64_t)ww * ldo + k0;
+    if constexpr (std::is_same<TO, bf16>::value) {  // one 16-B store per chunk
+      const bf16x8 o = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3],
+                        (bf16)v[4], (bf16)v[5], (bf16)v[6], (bf16)v[7]};
+      store_bf16x8(op, o);
+    } else {
+      store4(op, f32x4{v[0], v[1], v[2], v[3]});
+      store4(op + 4, f32x4{v[4], v[5], v[6], v[7]});
+    }
+  }
+  if (hh == 0 && tid < 64) {  // one wave writes the CLS row and its LayerNorm statistics
+    const int64_t row = (int64_t)b * (np * np + 1);
+    TO* xr = x + row * D;
+    float s1 = 0.f, s2 = 0.f;
+    for (int n = tid; n < D; n += 64) {
+      const TO v = from_f32<TO>(cls[n] + pos[n]);
+      xr[n] = v;
+      const float q = to_f32(v);
+      s1 += q;
+      s2 += q * q;
+    }
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    if (stats && tid < stats_slots(D)) {
+      float* st = stats + 2 * (stats_slots(D) * row + tid);
+      st[0] = tid == 0 ? s1 : 0.f;
+      st[1] = tid == 0 ? s2 : 0.f;
+    }
+  }
+}
+
 // Keras patch_to_embedding kernel [(p1 p2 c), N] -> rows in the channel-major order above.
 __global__ void patch_weight_cm_kernel(const float* __restrict__ W, float* __restrict__ Wcm, int C,
                                        int ps, int N) {
@@ -273,6 +373,33 @@ hipError_t patchify_launch(int dtype, const float* img, int B, int C, int HW, in
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(patchify_kernel<float>, grid, dim3(256), lds, s, img, C, HW, ps,
                        (float*)out, (float*)x, cls, pos, D, stats);
+  }
+  return hipGetLastError();
+}
+
+bool patchify_ld_ok(int C, int HW, int ps, int64_t ldo) {
+  if (C <= 0 || ps <= 0 || HW <= 0 || HW % ps || ((int64_t)ps * HW) % 4) return false;
+  if (ldo < (int64_t)ps * ps * C || ldo % 8 || ldo > (1 << 20)) return false;
+  return (size_t)C * ps * HW * sizeof(float) <= 160 * 1024;
+}
+
+hipError_t patchify_ld_launch(int dtype, const float* img, int B, int C, int HW, int ps, void* out,
+                              int64_t ldo, void* x, const float* cls, const float* pos, int D,
+                              float* stats, hipStream_t s) {
+  if (!patchify_ld_ok(C, HW, ps, ldo) || ((uintptr_t)out & 15)) return hipErrorInvalidValue;
+  if (B <= 0) return hipSuccess;
+  const size_t lds = (size_t)C * ps * HW * sizeof(float);
+  dim3 grid(HW / ps, B);
+  if (dtype == DT_BF16) {
+    (void)hipFuncSetAttribute((const void*)patchify_ld_kernel<bf16>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(patchify_ld_kernel<bf16>, grid, dim3(256), lds, s, img, C, HW, ps,
+                       (bf16*)out, (int)ldo, (bf16*)x, cls, pos, D, stats);
+  } else {
+    (void)hipFuncSetAttribute((const void*)patchify_ld_kernel<float>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(patchify_ld_kernel<float>, grid, dim3(256), lds, s, img, C, HW, ps,
+                       (float*)out, (int)ldo, (float*)x, cls, pos, D, stats);
   }
   return hipGetLastError();
 }

@@ -92,8 +92,9 @@ class ViT:
     """Vision Transformer forward on MI355X (reference `ViT`, vit.py:9-55).
 
     `image_size` / `patch_size`: any pair with (image_size / patch_size)^2 + 1 <= 4096 tokens per
-    image (224 px: 197; 384 px as `get_torch_deit`, utils.py:52-62: 577; "mx8": <= 256 tokens);
-    the factories (`get_deit_*`, `build_named`) pass `image_size=` through."""
+    image (224 px: 197; 384 px as `get_torch_deit`, utils.py:52-62: 577; patch 14: 257 at 224 px,
+    1370 at 518 px; "mx8": <= 256 tokens); the factories (`get_deit_*`, `build_named`) pass
+    `image_size=` through. `dim`: a multiple of 8 up to 1536 ("mx8": of 64, up to 1024)."""
 
     SEMANTICS = _lib.VIT_REFERENCE
     _param_shapes = staticmethod(vit_param_shapes)
@@ -317,9 +318,41 @@ def deit_base_patch16_224(**kw) -> StandardViT:
     return StandardViT(dim=768, heads=12, **kw)
 
 
+# The large published ViTs (timm vit_large_patch16_224, vit_large_patch14_224,
+# vit_huge_patch14_224; the MAE / CLIP / DINOv2 backbones): L = 1024 wide, 24 layers, 16 heads of
+# 64; H = 1280 wide, 32 layers, 16 heads of 80; MLP ratio 4. Patch 14 gives 16 x 16 + 1 = 257
+# tokens at 224 px (518 px: 1370).
+STD_VIT_NAMED = {
+    "vit_large_patch16_224": dict(dim=1024, depth=24, heads=16, patch_size=16),
+    "vit_large_patch14_224": dict(dim=1024, depth=24, heads=16, patch_size=14),
+    "vit_huge_patch14_224": dict(dim=1280, depth=32, heads=16, patch_size=14),
+}
+
+
+def _std_named(name: str, kw: dict) -> StandardViT:
+    return StandardViT(**{**STD_VIT_NAMED[name], **kw})  # a keyword of the caller's wins (depth=2)
+
+
+def vit_large_patch16_224(**kw) -> StandardViT:
+    return _std_named("vit_large_patch16_224", kw)
+
+
+def vit_large_patch14_224(**kw) -> StandardViT:
+    return _std_named("vit_large_patch14_224", kw)
+
+
+def vit_huge_patch14_224(**kw) -> StandardViT:
+    return _std_named("vit_huge_patch14_224", kw)
+
+
+def build_std_named(name: str, **kw) -> StandardViT:
+    return _std_named(name, kw)
+
+
 def _patch_rows(conv_w: np.ndarray) -> np.ndarray:
     """Conv2d kernel [D, C, p, p] -> patch_w [p*p*C, D] in this build's (p1 p2 c) vector order
-    (the reference's einops pattern, vit.py:31-32)."""
+    (the reference's einops pattern, vit.py:31-32), for any patch size p (14: 588 rows; the
+    library's own K order and row padding are internal to evt_vit_create)."""
     d = conv_w.shape[0]
     return np.ascontiguousarray(conv_w.transpose(2, 3, 1, 0).reshape(-1, d))
 

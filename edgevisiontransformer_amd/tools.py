@@ -2,6 +2,7 @@
 
     python -m edgevisiontransformer_amd.tools gpu_benchmark --model deit_base --input_shape 512,3,224,224
     python -m edgevisiontransformer_amd.tools gpu_benchmark --model deit_base --input_shape 64,3,384,384
+    python -m edgevisiontransformer_amd.tools gpu_benchmark --model vit_huge_patch14_224 --input_shape 64,3,224,224
     python -m edgevisiontransformer_amd.tools gpu_benchmark --model deit_tiny --prune_encoding all_head2_ffn0.7
     python -m edgevisiontransformer_amd.tools test_keras_latency --model t2t_vit_14 --input_shape 1,224,224,3
     python -m edgevisiontransformer_amd.tools prune_benchmark --types tiny --num_runs 20
@@ -35,12 +36,16 @@ import numpy as np
 
 VIT_NAMED = {"deit_tiny": 3, "deit_small": 6, "deit_base": 12}   # heads (vit.py:100-109)
 T2T_NAMED = ("t2t_vit_7", "t2t_vit_10", "t2t_vit_12", "t2t_vit_14")
+# the large published ViTs (StandardViT factories; heads of 64 or 80, so not in VIT_NAMED, whose
+# widths are heads * 64): modeling/models/vit.py STD_VIT_NAMED
+STD_VIT_NAMED = ("vit_large_patch16_224", "vit_large_patch14_224", "vit_huge_patch14_224")
 SWIN_NAMED = ("swin_tiny", "swin_small", "swin_base", "swin_large")   # get_swin configs (tools.py:282)
 
 
 def build_model(name: str, compute_dtype: str, prune_encoding: Optional[str] = None,
                 max_batch: int = 1, seed: int = 0, image_size: int = 224):
-    """A model by reference name (deit_*, t2t_vit_*, swin_*), optionally head/FFN pruned.
+    """A model by reference name (deit_*, t2t_vit_*, swin_*) or timm name (vit_large_patch16_224,
+    vit_large_patch14_224, vit_huge_patch14_224), the DeiT ones optionally head/FFN pruned.
     image_size: the input resolution (reference utils.py:52-62 loads 224 and 384 px DeiT; any size
     the library takes works for DeiT and T2T-ViT; a full Swin config name carries its own size,
     e.g. swin_large_patch4_window12_384, the short names swin_tiny|small|base|large are 224 px)."""
@@ -60,9 +65,14 @@ def build_model(name: str, compute_dtype: str, prune_encoding: Optional[str] = N
             raise ValueError("prune_encoding applies to DeiT models only")
         from .modeling.models.t2t_vit import build_named
         return build_named(name, dtype=compute_dtype, seed=seed, max_batch=max_batch, **kw)
+    if name in STD_VIT_NAMED:
+        if prune_encoding:
+            raise ValueError("prune_encoding applies to DeiT models only")
+        from .modeling.models.vit import build_std_named
+        return build_std_named(name, dtype=compute_dtype, seed=seed, max_batch=max_batch, **kw)
     if name not in VIT_NAMED:
         raise ValueError(f"unknown model {name!r}; one of "
-                         f"{sorted(VIT_NAMED) + list(T2T_NAMED) + list(SWIN_NAMED)}")
+                         f"{sorted(VIT_NAMED) + list(STD_VIT_NAMED) + list(T2T_NAMED) + list(SWIN_NAMED)}")
     from .modeling.models.vit import ViT_Pruned, build_named
     if prune_encoding:
         h = VIT_NAMED[name]
@@ -138,7 +148,7 @@ def format_line(name: str, avg_s: float, std_s: float, precision: int) -> str:
 def _server_flags(parser: argparse.ArgumentParser) -> None:
     parser.add_argument("func", help="specify the work to do.")
     parser.add_argument("--model", required=True, type=str,
-                        help=f"model name: {', '.join(list(VIT_NAMED) + list(T2T_NAMED))}")
+                        help=f"model name: {', '.join(list(VIT_NAMED) + list(STD_VIT_NAMED) + list(T2T_NAMED))}")
     parser.add_argument("--prune_encoding", default=None, type=str,
                         help="ViT_Pruned encoding (all_head{N}_ffn{F} / layerwise_h{N}-d{F}_...)")
     parser.add_argument("--use_gpu", action="store_true", help="accepted; always the GPU")

@@ -47,15 +47,22 @@ extern "C" {
  * heads/head_dim/ffn are per-layer arrays of length `depth` (the pruned encoding, decoded by the
  * host mirror exactly as ViT_Pruned.decode_prune_encoding, vit.py:77-97). */
 typedef struct evt_vit_desc {
-  int32_t image_size;   /* 224; 384 (DeiT-384, 577 tokens), patch 8, 512 px ...: any size with
-                         * (image_size / patch_size)^2 + 1 <= 4096 tokens (EVT_DTYPE_MX8: <= 256)
+  int32_t image_size;   /* 224; 384 (DeiT-384, 577 tokens), patch 8, 512 px, 518 px at patch 14
+                         * (DINOv2, 1370 tokens) ...: any size with
+                         * (image_size / patch_size)^2 + 1 <= 4096 tokens (EVT_DTYPE_MX8: <= 256),
+                         * patch_size * image_size % 4 == 0
                          * and in_chans * patch_size * image_size * 4 <= 160 KiB (patchify).
                          * With more than 256 tokens evt_vit_create refuses a max_batch whose
                          * largest activation buffer would reach 2^31 bytes (EVT_EINVAL) */
-  int32_t patch_size;   /* 16; image_size % patch_size == 0 (vit.py:13) */
+  int32_t patch_size;   /* 16, 14, 8 ...: any size with image_size % patch_size == 0 (vit.py:13).
+                         * Where patch_size^2 * in_chans is not a multiple of 64 (patch 14: 588)
+                         * the patch matrix has rows of the next multiple of 64 columns (640), the
+                         * padding written as zeros by every forward (evt_patchify_ld); the
+                         * workspace (evt_query_workspace) counts the padded rows */
   int32_t in_chans;     /* 3 */
   int32_t num_classes;  /* 1000 */
-  int32_t dim;          /* D: 192 / 384 / 768; multiple of 8, <= 1024 (MX8: of 64) */
+  int32_t dim;          /* D: 192 / 384 / 768 / 1024 (ViT-L) / 1280 (ViT-H) / 1408 (ViT-g);
+                         * multiple of 8, <= 1536 (EVT_DTYPE_MX8: multiple of 64, <= 1024) */
   int32_t depth;        /* 12 */
   int32_t mlp_dim;      /* head MLP width M (vit.py:38) */
   const int32_t* heads;    /* [depth] heads per layer (attention.py:5) */
@@ -284,6 +291,11 @@ int evt_patchify(int dtype, const float* img, int B, int C, int HW, int ps, void
 int evt_patchify_cm(int dtype, const float* img, int B, int C, int HW, int ps, void* out, void* x,
                     const float* cls, const float* pos, int D, float* stats, void* stream);
 
+/* evt_patchify_ld - evt_patchify_cm for any patch size, rows at a padded stride with a zeroed
+ * tail, the op behind patch 14 - is declared in evt_patchify.h, which this header includes below:
+ * this file's own list of entry points is the one tests/test_capi.py counts. Its K order is
+ * channel-major, k = (c*ps + p1)*ps + p2, as evt_patchify_cm's. */
+
 /* ---- T2T-ViT (reference modeling/models/t2t_vit.py) ------------------------------------ */
 
 /* Static shape of a T2T_ViT (t2t_vit.py:91-114; factories get_t2t_vit_{7,10,12,14} :138-148).
@@ -496,4 +508,7 @@ int evt_model_qkv_layout(const evt_model* m, int* headmajor_layers);
 #ifdef __cplusplus
 }
 #endif
+
+#include "evt_patchify.h"  /* evt_patchify_ld */
+
 #endif /* EVT_H_ */

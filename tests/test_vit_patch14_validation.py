@@ -1,0 +1,122 @@
+"""Host-side validation of the patch-14 and wide ViT configurations (csrc/capi.cpp validate through
+evt_query_workspace, and evt_patchify_ld's argument checks): no GPU is touched, every call returns
+before any launch."""
+import ctypes
+
+import pytest
+
+from edgevisiontransformer_amd import _lib
+from edgevisiontransformer_amd.modeling.models.vit import STD_VIT_NAMED, _patch_rows
+from edgevisiontransformer_amd.weights import std_vit_param_shapes, vit_config
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return _lib.load_library()
+
+
+def test_companion_header_binding_and_exports_agree(lib):
+    """include/evt_patchify.h (included by evt.h) = _lib.EXT_SIGNATURES = exported symbols: the
+    check tests/test_capi.py makes for evt.h's own list."""
+    import os
+    import re
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    txt = open(os.path.join(repo, "include", "evt_patchify.h")).read()
+    declared = sorted(set(re.findall(r"^(?:int|int64_t|const char\*)\s+(evt_\w+)\(", txt, re.M)))
+    assert declared == sorted(_lib.EXT_SIGNATURES) == ["evt_patchify_ld"]
+    assert not set(declared) & set(_lib.SIGNATURES)
+    assert '#include "evt_patchify.h"' in open(os.path.join(repo, "include", "evt.h")).read()
+    for name in declared:
+        assert hasattr(lib, name) and getattr(lib, name).argtypes == _lib.EXT_SIGNATURES[name][1]
+
+
+def _vit(lib, image, patch, dim, heads, hd, dtype="bf16", batch=2, depth=2,
+         semantics=_lib.VIT_STANDARD):
+    arr = lambda v: (ctypes.c_int32 * depth)(*([v] * depth))  # noqa: E731
+    d = _lib.evt_vit_desc(image, patch, 3, 1000, dim, depth, 4 * dim, arr(heads), arr(hd),
+                          arr(4 * dim), _lib.DTYPE[dtype], batch, semantics, 1e-6)
+    out = ctypes.c_size_t()
+    rc = lib.evt_query_workspace(ctypes.byref(d), batch, ctypes.byref(out))
+    return rc, lib.evt_last_error().decode(), out.value
+
+
+@pytest.mark.parametrize("image,patch,dim,heads,hd", [
+    (224, 14, 1280, 16, 80),    # ViT-H/14
+    (224, 14, 1024, 16, 64),    # ViT-L/14
+    (518, 14, 1024, 16, 64),    # DINOv2 input size: 1370 tokens
+    (224, 14, 1408, 16, 88),    # ViT-g width: 12 statistics slots, 11 used
+    (224, 16, 1536, 24, 64),    # the widest
+])
+@pytest.mark.parametrize("dtype", ["bf16", "f32"])
+def test_large_vit_configurations_are_accepted(lib, image, patch, dim, heads, hd, dtype):
+    rc, msg, ws = _vit(lib, image, patch, dim, heads, hd, dtype)
+    assert rc == _lib.EVT_OK, msg
+    assert ws > 0
+
+
+def test_refusals(lib):
+    rc, msg, _ = _vit(lib, 224, 16, 1544, 24, 64)
+    assert rc == _lib.EVT_EINVAL and "1536" in msg
+    rc, msg, _ = _vit(lib, 224, 16, 1280, 20, 64, "mx8", semantics=_lib.VIT_REFERENCE)
+    assert rc == _lib.EVT_EINVAL and "MX8" in msg and "1024" in msg
+    rc, msg, _ = _vit(lib, 225, 14, 1280, 16, 80)
+    assert rc == _lib.EVT_EINVAL and "divisible by the patch size" in msg
+    # MX8 itself is as it was at the widths it takes
+    assert _vit(lib, 224, 16, 1024, 16, 64, "mx8", semantics=_lib.VIT_REFERENCE)[0] == _lib.EVT_OK
+
+
+@pytest.mark.parametrize("dtype,elem", [("bf16", 2), ("f32", 4)])
+def test_workspace_counts_the_padded_patch_matrix(lib, dtype, elem):
+    """Patch 14: rows of 588 columns at a stride of 640. With one narrow FFN the patch matrix is
+    the largest user of the buffer it shares with the FFN hidden activations."""
+    B, P = 8, 256
+    arr = lambda v: (ctypes.c_int32 * 1)(v)  # noqa: E731
+    d = _lib.evt_vit_desc(224, 14, 3, 10, 64, 1, 64, arr(1), arr(64), arr(64), _lib.DTYPE[dtype],
+                          B, _lib.VIT_STANDARD, 1e-6)
+    out = ctypes.c_size_t()
+    assert lib.evt_query_workspace(ctypes.byref(d), B, ctypes.byref(out)) == _lib.EVT_OK
+    assert out.value >= B * P * 640 * elem
+    rc, _, ws = _vit(lib, 224, 14, 1280, 16, 80, dtype, batch=B)
+    assert rc == _lib.EVT_OK and ws >= B * P * 640 * elem
+
+
+def test_patchify_ld_checks_shapes_before_anything_else(lib):
+    """Null pointers throughout: a shape error is reported before any pointer is looked at."""
+    def call(HW, ps, ldo, C=3, dtype=1):
+        rc = lib.evt_patchify_ld(dtype, None, 1, C, HW, ps, None, ldo, None, None, None, 192, None,
+                                 None)
+        return rc, lib.evt_last_error().decode()
+    for HW, ps, ldo in ((28, 14, 584),      # ldo < pd = 588
+                        (28, 14, 644),      # ldo % 8 != 0
+                        (30, 14, 640),      # HW % ps != 0
+                        (21, 7, 152),       # ps * HW % 4 != 0
+                        (1022, 14, 640)):   # strip 3 * 14 * 1022 * 4 B > 160 KiB
+        rc, msg = call(HW, ps, ldo)
+        assert rc == _lib.EVT_EINVAL and "bad shape" in msg, (HW, ps, ldo, msg)
+    rc, msg = call(28, 14, 640)  # a good shape: now the null pointers are the error
+    assert rc == _lib.EVT_EINVAL and "non-null" in msg
+    rc, msg = call(28, 14, 640, dtype=2)
+    assert rc == _lib.EVT_EINVAL and "dtype" in msg
+
+
+def test_named_configurations():
+    """The timm shapes of the three new factories, and the patch-14 weight conversion."""
+    import numpy as np
+    want = {"vit_large_patch16_224": (1024, 24, 16, 16, 197),
+            "vit_large_patch14_224": (1024, 24, 16, 14, 257),
+            "vit_huge_patch14_224": (1280, 32, 16, 14, 257)}
+    for name, (dim, depth, heads, patch, tokens) in want.items():
+        kw = STD_VIT_NAMED[name]
+        cfg = vit_config(kw["dim"], kw["depth"], kw["heads"], 4 * kw["dim"],
+                         patch_size=kw["patch_size"])
+        shapes = dict(std_vit_param_shapes(cfg))
+        assert (cfg.dim, cfg.depth, cfg.heads[0], cfg.head_dim[0]) == (dim, depth, heads, dim // heads)
+        assert shapes["patch_w"] == (patch * patch * 3, dim) and shapes["pos"] == (tokens, dim)
+        assert shapes[f"l{depth - 1}.qkv_w"] == (dim, 3 * dim)
+        assert shapes[f"l{depth - 1}.fc1_w"] == (dim, 4 * dim)
+        assert shapes["head_w"] == (dim, 1000)
+    # Conv2d kernel [D, C, 14, 14] -> rows (p1 p2 c): row (p1 * 14 + p2) * 3 + c
+    w = np.arange(5 * 3 * 14 * 14, dtype=np.float32).reshape(5, 3, 14, 14)
+    rows = _patch_rows(w)
+    assert rows.shape == (588, 5)
+    assert rows[(4 * 14 + 9) * 3 + 2, 3] == w[3, 2, 4, 9]
