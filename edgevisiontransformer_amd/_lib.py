@@ -156,6 +156,21 @@ EXT_SIGNATURES = {
     "evt_patchify_ld": (_I, [_I, _P, _I, _I, _I, _I, _P, _I64, _P, _P, _P, _I, _P, _P]),
 }
 
+
+class evt_features_args(ctypes.Structure):
+    _fields_ = [("logits", ctypes.c_void_p), ("pooled", ctypes.c_void_p),
+                ("tokens", ctypes.c_void_p), ("n_taps", ctypes.c_int32),
+                ("tap_blocks", ctypes.POINTER(ctypes.c_int32)),
+                ("taps", ctypes.POINTER(ctypes.c_void_p)), ("tap_norm", ctypes.c_int32)]
+
+
+# the entry points of include/evt_features.h (evt.h includes it; bound like SIGNATURES)
+FEATURE_SIGNATURES = {
+    "evt_features_shape": (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "evt_tap_shape": (_I, [_P, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "evt_forward_features": (_I, [_P, _P, _I, ctypes.POINTER(evt_features_args), _P]),
+}
+
 _lib = None
 _lock = threading.Lock()
 _initialized_devices = set()
@@ -175,7 +190,8 @@ def load_library() -> ctypes.CDLL:
             # entry points added since: those stay unbound there; the in-tree library must export
             # every one (tests/test_capi.py)
             lenient = "EVT_LIB" in os.environ
-            for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES}.items():
+            for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES,
+                                      **FEATURE_SIGNATURES}.items():
                 if lenient and not hasattr(lib, name):
                     continue
                 fn = getattr(lib, name)

@@ -141,6 +141,8 @@ struct ModelCore {
   int grid[3] = {0, 0, 0};   // token grids S/4, S/8, S/16
   // Swin (family 2)
   std::vector<SwinStage> stages;
+  // norm_g / norm_b: the final LayerNorm; STANDARD ViT and T2T-ViT keep it too (their heads have
+  // it folded into the weights) for the feature outputs; null for a REFERENCE ViT (it has none)
   float *pnorm_g = nullptr, *pnorm_b = nullptr, *norm_g = nullptr, *norm_b = nullptr;
   // desc's per-layer arrays live in this core's own vectors (after every copy of a core)
   void bind_desc() {
@@ -208,6 +210,10 @@ struct evt_model : ModelCore {  // a handle: the core, its own workspace, its ow
   // lane fills the CUs a balanced grid leaves idle; measured +2.9 % on T2T-ViT-14 bs256, while
   // Swin lanes measured -1.3 % without the balancing: DESIGN.md, batch lanes)
   int no_balance = 0;
+  // evt_forward_features: the outputs of the forward in flight (null in a plain forward) and the
+  // next entry of its tap list
+  const evt_features_args* feat = nullptr;
+  int feat_next = 0;
 };
 
 namespace {
@@ -499,6 +505,25 @@ int dense(const evt_model* m, const DenseW& w, const DenseCall& c, hipStream_t s
   return EVT_OK;
 }
 
+// evt_forward_features: one stream-export launch (features.hip) of `rows` rows of width D, through
+// the final LayerNorm when `norm`; counted under EVT_PROF_HEAD
+int feat_export(evt_model* m, const void* x, int64_t ldx, int64_t row_step, float* out, bool norm,
+                int rows, int D, hipStream_t s) {
+  ProfScope ps(m, EVT_PROF_HEAD, s);
+  prof_work(m, 0.0, (double)rows * D * (elem_size(m->dtype) + 4.0));
+  EVT_HIP(export_rows_launch(m->dtype, x, ldx, row_step, out, norm ? m->norm_g : nullptr,
+                             norm ? m->norm_b : nullptr, rows, D, m->eps, s),
+          "feature export");
+  return EVT_OK;
+}
+
+// After block `block` of a features forward, its output in ws.x: the tap, if one was asked for
+int feat_tap(evt_model* m, int block, int64_t ldx, int rows, int D, hipStream_t s) {
+  const evt_features_args* a = m->feat;
+  if (!a || m->feat_next >= a->n_taps || a->tap_blocks[m->feat_next] != block) return EVT_OK;
+  return feat_export(m, m->ws.x, ldx, 1, a->taps[m->feat_next++], a->tap_norm != 0, rows, D, s);
+}
+
 // Encoder weights (11 tensors per layer, 12 with the STANDARD qkv bias; evt_vit_num_weights
 // order) for m->heads / m->ffn.
 int build_encoder(evt_model* m, const float* const* w, hipStream_t s) {
@@ -594,6 +619,7 @@ int run_encoder(evt_model* m, int B, hipStream_t s) {
   const int D = m->D, T = m->sh.T, rows = B * T;
   const float log2e = 1.4426950408889634f;
   m->hm_layers = 0;
+  int block = 0;
   for (const Layer& L : m->layers) {
     const float scale_log2 = log2e / std::sqrt((float)L.hd);  // h_k^-0.5 (attention.py:13)
     // qkv head-major ([B][heads][q | k | v][T][64], EPI_HM) where the QKV GEMM takes the
@@ -664,6 +690,7 @@ int run_encoder(evt_model* m, int B, hipStream_t s) {
       c.stats_out = m->ws.sx;
       EVT_RC(dense(m, L.fc2, c, s));
     }
+    EVT_RC(feat_tap(m, block++, D, rows, D, s));
   }
   return EVT_OK;
 }
@@ -1086,6 +1113,8 @@ int evt_vit_create(const evt_vit_desc* desc, const float* const* w, int n_weight
     if (m->standard) {  // final LayerNorm folded into the classifier (CLS rows)
       EVT_RC(make_dense(m, &m->head, w[k + 2], w[k + 3], D, desc->num_classes, s, w[k + 0],
                         w[k + 1]));
+      EVT_RC(copy_vec(m, &m->norm_g, w[k + 0], D, s));  // unfolded, for the feature outputs
+      EVT_RC(copy_vec(m, &m->norm_b, w[k + 1], D, s));
     } else {
       EVT_RC(make_dense(m, &m->head1, w[k + 0], w[k + 1], D, desc->mlp_dim, s));
       EVT_RC(make_dense(m, &m->head2, w[k + 2], w[k + 3], desc->mlp_dim, desc->num_classes, s));
@@ -1097,11 +1126,20 @@ int evt_vit_create(const evt_vit_desc* desc, const float* const* w, int n_weight
   return finish_create(m, run(), out);
 }
 
-int evt_vit_forward(evt_model* m, const float* img, int B, float* logits, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const int pre = forward_prologue(m, 0, "model is not a ViT (use evt_t2t_forward)",
-                                   evt_vit_forward, img, B, logits, s);
-  if (pre != RUN_HERE) return pre;
+// The final token map and the pooled (CLS) vector of a ViT / T2T-ViT features forward, from the
+// stream the last encoder block left in ws.x
+static int encoder_features(evt_model* m, int B, hipStream_t s) {
+  const evt_features_args* a = m->feat;
+  const int D = m->D, T = m->sh.T;
+  const bool norm = m->norm_g != nullptr;  // REFERENCE ViT: no final LayerNorm (vit.py:54)
+  if (a->tokens) EVT_RC(feat_export(m, m->ws.x, D, 1, a->tokens, norm, B * T, D, s));
+  if (a->pooled) EVT_RC(feat_export(m, m->ws.x, D, T, a->pooled, norm, B, D, s));
+  return EVT_OK;
+}
+
+// The ViT forward of B images on this handle's own workspace. In a features forward (m->feat) the
+// taps, tokens and pooled are exported along the way and logits may be NULL (no head then).
+static int vit_run(evt_model* m, const float* img, int B, float* logits, hipStream_t s) {
   const evt_vit_desc& d = m->desc;
   const Shape& sh = m->sh;
   const int D = d.dim, T = sh.T, dt = m->dtype;
@@ -1131,6 +1169,8 @@ int evt_vit_forward(evt_model* m, const float* img, int B, float* logits, void* 
     EVT_RC(dense(m, m->patch, c, s));
   }
   EVT_RC(m->mx8 ? run_encoder_mx8(m, B, s) : run_encoder(m, B, s));
+  if (m->feat) EVT_RC(encoder_features(m, B, s));
+  if (!logits) return EVT_OK;
   ProfScope ps_head(m, EVT_PROF_HEAD, s);
   if (m->standard) {  // final LayerNorm of the CLS rows folded into the Linear head
     DenseCall c;
@@ -1156,6 +1196,13 @@ int evt_vit_forward(evt_model* m, const float* img, int B, float* logits, void* 
     EVT_RC(dense_head(m, m->head2, c, s));
   }
   return EVT_OK;
+}
+
+int evt_vit_forward(evt_model* m, const float* img, int B, float* logits, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int pre = forward_prologue(m, 0, "model is not a ViT (use evt_t2t_forward)",
+                                   evt_vit_forward, img, B, logits, s);
+  return pre != RUN_HERE ? pre : vit_run(m, img, B, logits, s);
 }
 
 // ---- T2T-ViT ----------------------------------------------------------------------------
@@ -1246,6 +1293,8 @@ int evt_t2t_create(const evt_t2t_desc* desc, const float* const* w, int n_weight
     k += 11 * desc->depth;
     // final LayerNorm (t2t_vit.py:111,129) folded into the classifier (:114,134)
     EVT_RC(make_dense(m, &m->head, w[k + 2], w[k + 3], D, desc->num_classes, s, w[k + 0], w[k + 1]));
+    EVT_RC(copy_vec(m, &m->norm_g, w[k + 0], D, s));  // unfolded, for the feature outputs
+    EVT_RC(copy_vec(m, &m->norm_b, w[k + 1], D, s));
     EVT_RC(t2t_alloc_ws(m, desc->max_batch, s));
     EVT_HIP(hipStreamSynchronize(s), "create sync");
     return EVT_OK;
@@ -1253,11 +1302,8 @@ int evt_t2t_create(const evt_t2t_desc* desc, const float* const* w, int n_weight
   return finish_create(m, run(), out);
 }
 
-int evt_t2t_forward(evt_model* m, const float* img, int B, float* logits, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const int pre = forward_prologue(m, 1, "model is not a T2T-ViT (use evt_vit_forward)",
-                                   evt_t2t_forward, img, B, logits, s);
-  if (pre != RUN_HERE) return pre;
+// The T2T-ViT forward on this handle's own workspace (features forwards: as vit_run)
+static int t2t_run(evt_model* m, const float* img, int B, float* logits, hipStream_t s) {
   prof_reset(m);
   const evt_t2t_desc& d = m->tdesc;
   const int dt = d.dtype, D = d.dim, T = m->sh.T, P = m->sh.P, S = d.image_size;
@@ -1384,6 +1430,8 @@ int evt_t2t_forward(evt_model* m, const float* img, int B, float* logits, void* 
     EVT_RC(dense(m, m->project, c, s));
   }
   EVT_RC(run_encoder(m, B, s));  // :127
+  if (m->feat) EVT_RC(encoder_features(m, B, s));
+  if (!logits) return EVT_OK;
   {  // LayerNorm of the CLS rows folded into the classifier (:129-134)
     ProfScope ps(m, EVT_PROF_HEAD, s);
     DenseCall c;
@@ -1393,6 +1441,13 @@ int evt_t2t_forward(evt_model* m, const float* img, int B, float* logits, void* 
     EVT_RC(dense(m, m->head, c, s));
   }
   return EVT_OK;
+}
+
+int evt_t2t_forward(evt_model* m, const float* img, int B, float* logits, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int pre = forward_prologue(m, 1, "model is not a T2T-ViT (use evt_vit_forward)",
+                                   evt_t2t_forward, img, B, logits, s);
+  return pre != RUN_HERE ? pre : t2t_run(m, img, B, logits, s);
 }
 
 int evt_model_profile(evt_model* m, int enable) {
@@ -1649,11 +1704,8 @@ int evt_swin_create(const evt_swin_desc* desc, const float* const* w, int n_weig
   return finish_create(m, run(), out);
 }
 
-int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const int pre = forward_prologue(m, 2, "model is not a Swin Transformer", evt_swin_forward, img,
-                                   B, logits, s);
-  if (pre != RUN_HERE) return pre;
+// The Swin forward on this handle's own workspace (features forwards: as vit_run)
+static int swin_run(evt_model* m, const float* img, int B, float* logits, hipStream_t s) {
   prof_reset(m);
   const evt_swin_desc& d = m->sdesc;
   const int dt = d.dtype;
@@ -1697,6 +1749,7 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
             "patch norm");
   }
   }
+  int nblock = 0;
   for (size_t i = 0; i < m->stages.size(); ++i) {
     const SwinStage& st = m->stages[i];
     const int C = st.C, Cst = st.Cst;
@@ -1742,6 +1795,7 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
       }
     }
     for (const SwinBlock& bl : st.blocks) {
+      const int block = nblock++;  // numbered consecutively over the stages (feature taps)
       // the fused C = 96 sublayers are window-7 kernels; a window-12 stage takes the GEMM path
       const bool fuse96 = dt == DT_BF16 && C == 96 && st.H == 3 && st.w == 7 && gemm_auto();
       const double slot_rows = (double)rows * stats_slots(C) * 8;
@@ -1787,8 +1841,7 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
                          bl.fc2.w, bl.fc2.b, bl.fc1.kpad, bl.fc2.kpad, rows, stats_slots(C),
                          m->eps};
         EVT_HIP(swin_mlp96_launch(mp, s), "fused MLP");
-        continue;
-      }
+      } else {
       {  // LN2-folded FC1 + erf GELU
         ProfScope ps(m, EVT_PROF_FC1, s);
         DenseCall c;
@@ -1805,24 +1858,41 @@ int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void*
         c.resid = m->ws.xm; c.ldr = Cst; c.stats_out = m->ws.sx; c.ln_width = C;
         EVT_RC(dense(m, bl.fc2, c, s));
       }
+      }
+      EVT_RC(feat_tap(m, block, Cst, rows, C, s));  // either way the block's output is in ws.x
     }
   }
-  // final LayerNorm + mean over tokens -> head Dense (fp32 logits)
   const SwinStage& sl = m->stages.back();
-  ProfScope ps_head(m, EVT_PROF_HEAD, s);
-  prof_work(m, 0.0, (double)B * sl.R * sl.R * sl.C * es + (double)B * sl.R * sl.R * stats_slots(sl.C) * 8 +
-                        (double)B * sl.C * es);
-  EVT_HIP(ln_pool_launch(dt, m->ws.x, sl.Cst, B, sl.R * sl.R, sl.C, m->ws.sx, stats_slots(sl.C),
-                         m->norm_g, m->norm_b, m->ws.pooled, sl.Cst, s),
-          "norm + avgpool");
+  const evt_features_args* fa = m->feat;
+  if (fa && fa->tokens)  // LN(x) of the last stage, its padding columns [C, Cst) dropped
+    EVT_RC(feat_export(m, m->ws.x, sl.Cst, 1, fa->tokens, true, B * sl.R * sl.R, sl.C, s));
+  if (!logits && !(fa && fa->pooled)) return EVT_OK;
+  // final LayerNorm + mean over tokens -> head Dense (fp32 logits)
   {
-    DenseCall c;
-    c.flags = EPI_BIAS | EPI_OUT_F32;
-    c.A = m->ws.pooled; c.lda = sl.Cst; c.C = logits; c.ldc = d.num_classes; c.M = B;
-    c.N = d.num_classes;
-    EVT_RC(dense(m, m->head, c, s));
+    ProfScope ps_head(m, EVT_PROF_HEAD, s);
+    prof_work(m, 0.0, (double)B * sl.R * sl.R * sl.C * es + (double)B * sl.R * sl.R * stats_slots(sl.C) * 8 +
+                          (double)B * sl.C * es);
+    EVT_HIP(ln_pool_launch(dt, m->ws.x, sl.Cst, B, sl.R * sl.R, sl.C, m->ws.sx, stats_slots(sl.C),
+                           m->norm_g, m->norm_b, m->ws.pooled, sl.Cst, s),
+            "norm + avgpool");
+    if (logits) {
+      DenseCall c;
+      c.flags = EPI_BIAS | EPI_OUT_F32;
+      c.A = m->ws.pooled; c.lda = sl.Cst; c.C = logits; c.ldc = d.num_classes; c.M = B;
+      c.N = d.num_classes;
+      EVT_RC(dense(m, m->head, c, s));
+    }
   }
+  if (fa && fa->pooled)  // the head's operand as it stands (activation dtype) -> fp32
+    EVT_RC(feat_export(m, m->ws.pooled, sl.Cst, 1, fa->pooled, false, B, sl.C, s));
   return EVT_OK;
+}
+
+int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int pre = forward_prologue(m, 2, "model is not a Swin Transformer", evt_swin_forward, img,
+                                   B, logits, s);
+  return pre != RUN_HERE ? pre : swin_run(m, img, B, logits, s);
 }
 
 int evt_window_attention(int dtype, const void* qkv, int64_t ldq, void* out, int64_t ldo,
@@ -2135,6 +2205,84 @@ int evt_performer(int dtype, const void* kqv, int64_t ldq, int B, int T, const f
   EVT_HIP(performer_launch(dtype, kqv, ldq, B, T, pw, part, out, ldo, (hipStream_t)stream),
           "performer");
   return EVT_OK;
+}
+
+// ---- feature outputs (include/evt_features.h) ---------------------------------------------
+
+static int model_blocks(const evt_model* m) {
+  if (m->family != 2) return (int)m->layers.size();
+  int n = 0;
+  for (const SwinStage& st : m->stages) n += (int)st.blocks.size();
+  return n;
+}
+
+int evt_features_shape(const evt_model* m, int* F, int* T, int* n_blocks) {
+  if (!m) return fail(EVT_EINVAL, "model is NULL");
+  const bool swin = m->family == 2;
+  if (F) *F = swin ? m->stages.back().C : m->D;
+  if (T) *T = swin ? m->stages.back().R * m->stages.back().R : m->sh.T;
+  if (n_blocks) *n_blocks = model_blocks(m);
+  return EVT_OK;
+}
+
+int evt_tap_shape(const evt_model* m, int block, int* tokens, int* width) {
+  if (!m || !tokens || !width) return fail(EVT_EINVAL, "null argument");
+  if (block < 0 || block >= model_blocks(m))
+    return fail(EVT_EINVAL, "block must be in [0, " + std::to_string(model_blocks(m)) + ")");
+  *tokens = m->sh.T;
+  *width = m->D;
+  if (m->family == 2) {
+    for (const SwinStage& st : m->stages) {
+      if (block < (int)st.blocks.size()) {
+        *tokens = st.R * st.R;
+        *width = st.C;
+        break;
+      }
+      block -= (int)st.blocks.size();
+    }
+  }
+  return EVT_OK;
+}
+
+int evt_forward_features(evt_model* m, const float* img, int B, const evt_features_args* a,
+                         void* stream) {
+  if (!m || !img || !a) return fail(EVT_EINVAL, "model, img and args must be non-null");
+  if (a->n_taps < 0 || a->n_taps > 64) return fail(EVT_EINVAL, "n_taps must be in [0, 64]");
+  if (!a->logits && !a->pooled && !a->tokens && a->n_taps == 0)
+    return fail(EVT_EINVAL, "no output requested: logits, pooled and tokens are NULL, n_taps is 0");
+  if (B <= 0 || B > m->max_batch)
+    return fail(EVT_EINVAL, "batch must be in [1, max_batch=" + std::to_string(m->max_batch) + "]");
+  if (a->tap_norm != 0 && a->tap_norm != 1) return fail(EVT_EINVAL, "tap_norm must be 0 or 1");
+  if (a->tap_norm && (m->family == 2 || !m->norm_g))
+    return fail(EVT_EINVAL, m->family == 2
+                                ? "tap_norm: Swin stage widths differ from the final LayerNorm's"
+                                : "tap_norm: a REFERENCE ViT has no final LayerNorm");
+  uintptr_t align = (uintptr_t)a->pooled | (uintptr_t)a->tokens;  // 16-B stores (features.hip)
+  if (a->n_taps > 0) {
+    if (!a->tap_blocks || !a->taps)
+      return fail(EVT_EINVAL, "n_taps > 0 needs the tap_blocks and taps arrays");
+    if (m->mx8) return fail(EVT_EINVAL, "taps are not available on an EVT_DTYPE_MX8 model");
+    const int nb = model_blocks(m);
+    for (int i = 0; i < a->n_taps; ++i) {
+      if (a->tap_blocks[i] < 0 || a->tap_blocks[i] >= nb)
+        return fail(EVT_EINVAL, "tap block " + std::to_string(a->tap_blocks[i]) +
+                                    " is outside [0, " + std::to_string(nb) + ")");
+      if (i > 0 && a->tap_blocks[i] <= a->tap_blocks[i - 1])
+        return fail(EVT_EINVAL, "tap_blocks must be strictly increasing");
+      if (!a->taps[i]) return fail(EVT_EINVAL, "tap pointer " + std::to_string(i) + " is NULL");
+      align |= (uintptr_t)a->taps[i];
+    }
+  }
+  if (align & 15) return fail(EVT_EINVAL, "feature outputs must be 16-byte aligned");
+  // one lane, on this handle's own workspace, whatever its lane count (as a profiled forward)
+  hipStream_t s = (hipStream_t)stream;
+  m->feat = a;
+  m->feat_next = 0;
+  const int rc = m->family == 0   ? vit_run(m, img, B, a->logits, s)
+                 : m->family == 1 ? t2t_run(m, img, B, a->logits, s)
+                                  : swin_run(m, img, B, a->logits, s);
+  m->feat = nullptr;
+  return rc;
 }
 
 }  // extern "C"

@@ -128,6 +128,13 @@ hipError_t layernorm_launch(int dtype, const float* x, int64_t ldx, void* y, int
                             const float* gamma, const float* beta, int rows, int D, float eps,
                             hipStream_t s);
 
+// Stream export (features.hip): out[r][0:D] = fp32 of x[r * row_step * ldx + 0:D] (x in `dtype`),
+// through LayerNorm(gamma, beta, eps) when gamma is non-null; out contiguous [rows, D].
+// D % 8 == 0, D <= 1536, ldx % 8 == 0, x and out 16-byte aligned (hipErrorInvalidValue otherwise).
+hipError_t export_rows_launch(int dtype, const void* x, int64_t ldx, int64_t row_step, float* out,
+                              const float* gamma, const float* beta, int rows, int D, float eps,
+                              hipStream_t s);
+
 // Number of statistics slots of a LayerNorm of width D: one per 128-column slab of a 256-padded
 // row (both GEMM tile shapes number their slabs n0 / 128).
 __host__ __device__ inline int stats_slots(int D) { return 2 * ((D + 255) / 256); }

@@ -1,0 +1,158 @@
+"""Feature outputs of the model mirrors: the binding of include/evt_features.h.
+
+The models of this package are mostly used as backbones; besides `model(img)` (logits) every
+mirror class offers
+
+    emb = model.forward_features(img)                  # [B, F]: what the classifier reads
+    out = model.features(img, tokens=True, taps=(3, 7, -1))
+    out["pooled"], out["tokens"], out["taps"]          # [B, F], [B, T, F], list of [B, T_i, C_i]
+    model.features_into(img, pooled=p, tokens=t)       # preallocated device tensors, no allocation
+
+`forward_features` is the reference name and meaning (`T2T_ViT.forward_features`, reference
+t2t_vit.py:120-130: LayerNorm then the CLS token; microsoft `SwinTransformer.forward_features`:
+LayerNorm, token mean). Per family (the table in include/evt_features.h): a REFERENCE `ViT` has no
+final LayerNorm, so its pooled / tokens are the last block's output as it stands; `StandardViT`
+and `T2T_ViT` give LN(x); Swin gives the token mean of LN(x) and the last stage's LN(x) map.
+A tap is the residual stream after a block (negative indices count from the last one);
+`tap_norm=True` passes the taps through the final LayerNorm (StandardViT and T2T_ViT only).
+Everything comes back fp32, whatever the model's dtype.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict, List, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from ... import _lib
+
+MAX_TAPS = 64  # include/evt_features.h: n_taps 0..64
+
+
+def resolve_taps(taps: Sequence[int], num_blocks: int, *, tap_norm: bool = False,
+                 tap_norm_ok: bool = True) -> List[int]:
+    """Block indices of a `taps=` argument, in the order given (host only, no device call).
+
+    Negative indices count from the last block. ValueError: an index outside [-num_blocks,
+    num_blocks), a block named twice, more than 64 taps, or `tap_norm` on a model whose taps
+    cannot take the final LayerNorm (`tap_norm_ok` False: REFERENCE ViT, Swin)."""
+    if tap_norm and not tap_norm_ok:
+        raise ValueError("tap_norm=True needs a final LayerNorm of the taps' width: StandardViT and "
+                         "T2T_ViT have one; a reference ViT has none, Swin stage widths differ")
+    out = []
+    for t in taps:
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)):
+            raise ValueError(f"tap indices must be integers, got {t!r}")
+        i = int(t) + num_blocks if t < 0 else int(t)
+        if not 0 <= i < num_blocks:
+            raise ValueError(f"tap {int(t)} is outside the model's {num_blocks} blocks")
+        if i in out:
+            raise ValueError(f"block {i} is tapped twice")
+        out.append(i)
+    if len(out) > MAX_TAPS:
+        raise ValueError(f"at most {MAX_TAPS} taps per call")
+    return out
+
+
+class FeatureOutputs:
+    """Mixed into ViT, T2T_ViT and SwinTransformer. The host class provides `_feature_geometry()`
+    -> (F, T, [(tokens, width) per block]), `_image_dims()` -> the [1:] shape of its input,
+    `_TAP_NORM_OK`, and the handle plumbing (`_handle`, `_build`, `_max_batch`, `device`)."""
+
+    _TAP_NORM_OK = False
+
+    @property
+    def feature_dim(self) -> int:
+        """F: the width of `forward_features(img)` and of the final token map."""
+        return self._feature_geometry()[0]
+
+    @property
+    def num_blocks(self) -> int:
+        """Blocks a tap can name (Swin: numbered consecutively over the stages)."""
+        return len(self._feature_geometry()[2])
+
+    def tap_shape(self, block: int) -> Tuple[int, int]:
+        """(tokens per image, width) of the tap after `block` (negative: from the last)."""
+        return self._feature_geometry()[2][resolve_taps((block,), self.num_blocks)[0]]
+
+    def _checked_image(self, img):
+        from .vit import _to_device_image
+        x, was_numpy = _to_device_image(img, self.device)
+        if x.dim() != 4 or tuple(x.shape[1:]) != tuple(self._image_dims()):
+            raise ValueError(f"expected [B, {', '.join(map(str, self._image_dims()))}], "
+                             f"got {tuple(x.shape)}")
+        return x, was_numpy
+
+    def _feature_tensor(self, name: str, t, shape) -> int:
+        if t is None:
+            return 0
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() \
+                or t.device != self.device or tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} must be a contiguous float32 tensor of shape {tuple(shape)} "
+                             f"on {self.device}")
+        return t.data_ptr()
+
+    def features_into(self, img: torch.Tensor, *, pooled: torch.Tensor = None,
+                      tokens: torch.Tensor = None, logits: torch.Tensor = None,
+                      taps: Sequence[int] = (), tap_tensors: Sequence[torch.Tensor] = (),
+                      tap_norm: bool = False) -> None:
+        """Enqueue one forward of a device-resident batch that fills the given fp32 device tensors
+        (`pooled` [B, F], `tokens` [B, T, F], `logits` [B, num_classes], `tap_tensors[i]` the tap
+        after block `taps[i]`); no allocation, no synchronisation (evt_forward_features)."""
+        blocks = resolve_taps(taps, self.num_blocks, tap_norm=tap_norm,
+                              tap_norm_ok=self._TAP_NORM_OK)
+        if len(tap_tensors) != len(blocks):
+            raise ValueError("tap_tensors needs one tensor per tap")
+        b = img.shape[0]
+        f, t, geo = self._feature_geometry()
+        a = _lib.evt_features_args()
+        a.pooled = self._feature_tensor("pooled", pooled, (b, f))
+        a.tokens = self._feature_tensor("tokens", tokens, (b, t, f))
+        a.logits = self._feature_tensor("logits", logits, (b, self.num_classes))
+        order = sorted(range(len(blocks)), key=blocks.__getitem__)  # the C ABI wants them rising
+        ptrs = [self._feature_tensor(f"tap_tensors[{i}]", tap_tensors[i], (b, *geo[blocks[i]]))
+                for i in order]
+        if not (a.pooled or a.tokens or a.logits or blocks):
+            raise ValueError("no output requested")
+        idx = (ctypes.c_int32 * max(1, len(blocks)))(*[blocks[i] for i in order])
+        arr = (ctypes.c_void_p * max(1, len(blocks)))(*ptrs)
+        a.n_taps, a.tap_norm = len(blocks), int(bool(tap_norm))
+        if blocks:
+            a.tap_blocks, a.taps = idx, arr
+        if b > self._max_batch:
+            self._build(b)
+        _lib.check(_lib.load_library().evt_forward_features(
+            ctypes.c_void_p(self._handle), ctypes.c_void_p(img.data_ptr()), b, ctypes.byref(a),
+            ctypes.c_void_p(_lib.stream_ptr(self.device))))
+
+    def features(self, img, *, tokens: bool = False, taps: Sequence[int] = (),
+                 tap_norm: bool = False, logits: bool = False) -> Dict[str, object]:
+        """{"pooled": [B, F]} plus the requested "tokens" [B, T, F], "logits" and "taps" (a list in
+        the order given). numpy in, numpy out; a device tensor gives device tensors."""
+        blocks = resolve_taps(taps, self.num_blocks, tap_norm=tap_norm,
+                              tap_norm_ok=self._TAP_NORM_OK)
+        x, was_numpy = self._checked_image(img)
+        b = x.shape[0]
+        f, t, geo = self._feature_geometry()
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)  # noqa: E731
+        out: Dict[str, object] = {"pooled": new(b, f)}
+        if tokens:
+            out["tokens"] = new(b, t, f)
+        if logits:
+            out["logits"] = new(b, self.num_classes)
+        if blocks:
+            out["taps"] = [new(b, *geo[i]) for i in blocks]
+        with torch.cuda.device(self.device):
+            self.features_into(x, pooled=out["pooled"], tokens=out.get("tokens"),
+                               logits=out.get("logits"), taps=blocks,
+                               tap_tensors=out.get("taps", ()), tap_norm=tap_norm)
+        if was_numpy:  # .cpu() waits for the stream, as __call__ does
+            out = {k: [v.cpu().numpy() for v in val] if isinstance(val, list) else val.cpu().numpy()
+                   for k, val in out.items()}
+        return out
+
+    def forward_features(self, img):
+        """Pooled features [B, F]: the vector the classifier reads (reference
+        `T2T_ViT.forward_features`, microsoft `SwinTransformer.forward_features`)."""
+        return self.features(img)["pooled"]

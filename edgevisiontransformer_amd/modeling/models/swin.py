@@ -33,10 +33,11 @@ import torch
 
 from ... import _lib
 from ...weights import SwinConfig, make_swin_params, swin_config, swin_param_shapes
+from .features import FeatureOutputs
 from .vit import _capture_graph, _replay_graph, _to_device_image
 
 
-class SwinTransformer:
+class SwinTransformer(FeatureOutputs):
     """Swin Transformer forward on MI355X (microsoft `SwinTransformer`, built by reference
     `utils.py:28-43`). Stage widths (embed_dim * 2^i) up to 1536: Swin-T / S / B / L."""
 
@@ -174,6 +175,18 @@ class SwinTransformer:
         return logits.cpu().numpy() if was_numpy else logits
 
     forward = __call__
+
+    # -- feature outputs (features.py): forward_features = mean over tokens of LN(x) ----------
+    def _feature_geometry(self):
+        c = self.cfg
+        last = c.num_stages - 1
+        return c.num_features, c.res(last) ** 2, [(c.res(i) ** 2, c.dim(i))
+                                                  for i in range(c.num_stages)
+                                                  for _ in range(c.depths[i])]
+
+    def _image_dims(self):
+        c = self.cfg
+        return c.in_chans, c.image_size, c.image_size
 
 
 _CONFIG_RE = re.compile(r"swin_(tiny|small|base|large)_patch(\d+)_window(\d+)_(\d+)"

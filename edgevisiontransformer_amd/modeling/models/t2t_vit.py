@@ -25,10 +25,11 @@ import torch
 
 from ... import _lib
 from ...weights import T2TConfig, make_t2t_params, t2t_config, t2t_param_shapes
+from .features import FeatureOutputs
 from .vit import _capture_graph, _replay_graph, _to_device_image
 
 
-class T2T_ViT:
+class T2T_ViT(FeatureOutputs):
     """Tokens-to-Token ViT forward on MI355X (reference `T2T_ViT`, t2t_vit.py:91-135).
     `image_size`: a multiple of 16 with (image_size / 16)^2 + 1 <= 4096 tokens."""
 
@@ -149,6 +150,17 @@ class T2T_ViT:
         return logits.cpu().numpy() if was_numpy else logits
 
     call = __call__
+
+    # -- feature outputs (features.py): forward_features = LN(x)[:, 0], t2t_vit.py:120-130 ------
+    _TAP_NORM_OK = True
+
+    def _feature_geometry(self):
+        c = self.cfg
+        return c.dim, c.tokens, [(c.tokens, c.dim)] * c.depth
+
+    def _image_dims(self):
+        c = self.cfg
+        return c.image_size, c.image_size, c.in_chans
 
 
 def get_t2t_vit_7(**kw) -> T2T_ViT:

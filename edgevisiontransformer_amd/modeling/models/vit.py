@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from ... import _lib
+from .features import FeatureOutputs
 from ...weights import (ViTConfig, make_std_vit_params, make_vit_params, std_vit_param_shapes,
                         vit_config, vit_param_shapes)
 
@@ -88,7 +89,7 @@ def _replay_graph(model) -> None:
         ctypes.c_void_p(model._handle), ctypes.c_void_p(_lib.stream_ptr(model.device))))
 
 
-class ViT:
+class ViT(FeatureOutputs):
     """Vision Transformer forward on MI355X (reference `ViT`, vit.py:9-55).
 
     `image_size` / `patch_size`: any pair with (image_size / patch_size)^2 + 1 <= 4096 tokens per
@@ -235,6 +236,17 @@ class ViT:
 
     call = __call__
 
+    # -- feature outputs (features.py: forward_features, features, features_into) -------------
+    _TAP_NORM_OK = False  # no final LayerNorm (vit.py:54); StandardViT has one
+
+    def _feature_geometry(self):
+        c = self.cfg
+        return c.dim, c.tokens, [(c.tokens, c.dim)] * c.depth
+
+    def _image_dims(self):
+        c = self.cfg
+        return c.in_chans, c.image_size, c.image_size
+
 
 class ViT_Pruned(ViT):
     """Head/FFN-pruned ViT (reference `ViT_Pruned`, vit.py:58-75)."""
@@ -296,6 +308,7 @@ class StandardViT(ViT):
     Load real checkpoints with `params_from_timm_state_dict` / `params_from_hf_state_dict`."""
 
     SEMANTICS = _lib.VIT_STANDARD
+    _TAP_NORM_OK = True
     _param_shapes = staticmethod(std_vit_param_shapes)
     _make_params = staticmethod(make_std_vit_params)
 

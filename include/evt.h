@@ -510,5 +510,6 @@ int evt_model_qkv_layout(const evt_model* m, int* headmajor_layers);
 #endif
 
 #include "evt_patchify.h"  /* evt_patchify_ld */
+#include "evt_features.h"  /* evt_forward_features, evt_features_shape, evt_tap_shape */
 
 #endif /* EVT_H_ */
