@@ -9,3 +9,5 @@ classes is lazy so that host-only utilities (weights, prune encodings, CLI parsi
 GPU.
 """
 __version__ = "0.4.0"
+
+from .images import IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD, Uint8Images  # noqa: E402,F401

@@ -171,6 +171,17 @@ FEATURE_SIGNATURES = {
     "evt_forward_features": (_I, [_P, _P, _I, ctypes.POINTER(evt_features_args), _P]),
 }
 
+from .images import evt_image_args  # noqa: E402  (the struct of include/evt_image.h)
+
+# the entry points of include/evt_image.h (evt.h includes it; bound like SIGNATURES)
+IMAGE_SIGNATURES = {
+    "evt_forward_image": (_I, [_P, ctypes.POINTER(evt_image_args), _I,
+                               ctypes.POINTER(evt_features_args), _P]),
+    "evt_graph_capture_image": (_I, [_P, ctypes.POINTER(evt_image_args), _I, _P, _P]),
+    "evt_patchify_u8": (_I, [_I, _P, _I, _I, _I, _I, _P, _I64, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "evt_unfold_u8": (_I, [_I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P]),
+}
+
 _lib = None
 _lock = threading.Lock()
 _initialized_devices = set()
@@ -190,8 +201,8 @@ def load_library() -> ctypes.CDLL:
             # entry points added since: those stay unbound there; the in-tree library must export
             # every one (tests/test_capi.py)
             lenient = "EVT_LIB" in os.environ
-            for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES,
-                                      **FEATURE_SIGNATURES}.items():
+            for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **FEATURE_SIGNATURES,
+                                      **IMAGE_SIGNATURES}.items():
                 if lenient and not hasattr(lib, name):
                     continue
                 fn = getattr(lib, name)

@@ -21,7 +21,8 @@ SOURCES = ["gemm.hip", "attention.hip", "norm.hip", "t2t.hip", "swin.hip", "mx8.
            "features.hip", "capi.cpp"]
 HEADERS = ["common.h", "evt_internal.h", os.path.join("..", "..", "include", "evt.h"),
            os.path.join("..", "..", "include", "evt_patchify.h"),
-           os.path.join("..", "..", "include", "evt_features.h")]
+           os.path.join("..", "..", "include", "evt_features.h"),
+           os.path.join("..", "..", "include", "evt_image.h")]
 ARCH = os.environ.get("EVT_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result",
          "-ffp-contract=on"]  # contraction only within one source expression: same result on

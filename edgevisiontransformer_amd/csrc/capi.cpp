@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -214,6 +215,10 @@ struct evt_model : ModelCore {  // a handle: the core, its own workspace, its ow
   // next entry of its tap list
   const evt_features_args* feat = nullptr;
   int feat_next = 0;
+  // evt_forward_image: the uint8 NHWC batch of the forward in flight (null: the fp32 `img`
+  // argument of the run functions) and its per-channel affine
+  const uint8_t* img8 = nullptr;
+  ImgAffine aff{};
 };
 
 namespace {
@@ -1001,8 +1006,11 @@ static int swin_alloc_ws(evt_model* m, int B, hipStream_t s);  // (the Swin sect
 // [B i / k, B (i + 1) / k) on its own stream, forked from and joined to s by events (a HIP graph
 // capture on s records the lanes as parallel branches)
 typedef int (*ForwardFn)(evt_model*, const float*, int, float*, void*);
+static int run_family(evt_model* m, const float* img, int B, float* logits, hipStream_t s);
+// img8: a uint8 batch (evt_forward_image) instead of img, split at byte offsets b0 * img_elems
 static int lanes_forward(evt_model* m, ForwardFn fwd, const float* img, int B, float* logits,
-                         hipStream_t s) {
+                         hipStream_t s, const uint8_t* img8 = nullptr,
+                         const ImgAffine* aff = nullptr) {
   // the joins go onto s after every lane's work: a lane stream that shares s's hardware queue
   // would otherwise queue its kernels behind s's wait for the previous lane (measured: lanes
   // serialised in part)
@@ -1012,9 +1020,18 @@ static int lanes_forward(evt_model* m, ForwardFn fwd, const float* img, int B, f
     EVT_HIP(hipStreamWaitEvent(m->lane_s[i], m->lane_ev[0], 0), "lane fork wait");
   for (int i = 0; i < k; ++i) {
     const int b0 = (int)((int64_t)B * i / k), b1 = (int)((int64_t)B * (i + 1) / k);
-    if (b1 > b0)
+    if (b1 > b0 && img8) {
+      evt_model* c = m->lanes[i];
+      c->img8 = img8 + (size_t)b0 * m->img_elems;  // 1 byte per element
+      c->aff = *aff;
+      const int rc = run_family(c, nullptr, b1 - b0, logits + (size_t)b0 * m->num_classes,
+                                m->lane_s[i]);
+      c->img8 = nullptr;
+      EVT_RC(rc);
+    } else if (b1 > b0) {
       EVT_RC(fwd(m->lanes[i], img + (size_t)b0 * m->img_elems, b1 - b0,
                  logits + (size_t)b0 * m->num_classes, m->lane_s[i]));
+    }
     EVT_HIP(hipEventRecord(m->lane_ev[1 + i], m->lane_s[i]), "lane done");
   }
   for (int i = 0; i < k; ++i)
@@ -1147,10 +1164,15 @@ static int vit_run(evt_model* m, const float* img, int B, float* logits, hipStre
   // patch embedding (vit.py:45-51): rearrange -> Dense(D) + pos, CLS row = cls + pos[0]
   {
     ProfScope ps(m, EVT_PROF_PATCHIFY, s);
-    prof_work(m, 0.0, (double)B * d.in_chans * d.image_size * d.image_size * 4 +
+    prof_work(m, 0.0, (double)B * d.in_chans * d.image_size * d.image_size * (m->img8 ? 1 : 4) +
                           (double)B * (sh.P * sh.pdst + D) * elem_size(dt) +
                           (double)B * stats_slots(D) * 8);  // image read, patch rows + CLS rows
-    if (m->patch_ld)
+    if (m->img8)  // uint8 NHWC (evt_forward_image): channel-major rows at stride pdst
+      EVT_HIP(patchify_u8_launch(dt, m->img8, B, d.in_chans, d.image_size, d.patch_size,
+                                 m->ws.apatch, sh.pdst, m->ws.x, m->cls, m->pos, D, m->ws.sx,
+                                 m->aff, s),
+              "patchify (uint8)");
+    else if (m->patch_ld)
       EVT_HIP(patchify_ld_launch(dt, img, B, d.in_chans, d.image_size, d.patch_size, m->ws.apatch,
                                  sh.pdst, m->ws.x, m->cls, m->pos, D, m->ws.sx, s),
               "patchify");
@@ -1317,8 +1339,13 @@ static int t2t_run(evt_model* m, const float* img, int B, float* logits, hipStre
   const Performer& P1 = m->perf[0];
   {
     ProfScope ps(m, EVT_PROF_T2T_UNFOLD, s);
-    prof_work(m, 0.0, (double)B * S * S * d.in_chans * 4 + (double)B * t1 * P1.din * es +
-                          (double)B * t1 * stats_slots(P1.din) * 8);
+    prof_work(m, 0.0, (double)B * S * S * d.in_chans * (m->img8 ? 1 : 4) +
+                          (double)B * t1 * P1.din * es + (double)B * t1 * stats_slots(P1.din) * 8);
+    if (m->img8)
+      EVT_HIP(unfold_u8_launch(dt, m->img8, B, S, S, d.in_chans, 7, 4, 2, m->ws.u, P1.dpad,
+                               m->ws.su, stats_slots(P1.din), m->aff, s),
+              "soft_split0 (uint8)");
+    else
     EVT_HIP(unfold_launch(dt, 1, img, B, S, S, d.in_chans, 7, 4, 2, m->ws.u, P1.dpad, m->ws.su,
                           stats_slots(P1.din), s),
             "soft_split0");
@@ -1561,7 +1588,8 @@ int evt_model_profile_work(evt_model* m, double* gflop, double* gbytes) {
   return EVT_OK;
 }
 
-int evt_graph_capture(evt_model* m, const float* img, int batch, float* logits, void* stream) {
+// Capture what `enqueue` puts on `stream` as the model's graph (evt_graph_capture[_image])
+static int graph_capture(evt_model* m, void* stream, const std::function<int()>& enqueue) {
   if (!m || !stream) return fail(EVT_EINVAL, "graph capture needs a model and a non-NULL stream");
   if (m->prof)  // the events would be captured into the graph, never recorded on the stream
     return fail(EVT_EINVAL, "graph capture while profiling is enabled (evt_model_profile(m, 0) first)");
@@ -1575,9 +1603,7 @@ int evt_graph_capture(evt_model* m, const float* img, int batch, float* logits, 
     m->graph = nullptr;
   }
   EVT_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal), "begin capture");
-  const int rc = m->family == 0   ? evt_vit_forward(m, img, batch, logits, stream)
-                 : m->family == 1 ? evt_t2t_forward(m, img, batch, logits, stream)
-                                  : evt_swin_forward(m, img, batch, logits, stream);
+  const int rc = enqueue();
   hipGraph_t g = nullptr;
   const hipError_t e = hipStreamEndCapture(s, &g);
   if (rc) {
@@ -1594,6 +1620,14 @@ int evt_graph_capture(evt_model* m, const float* img, int batch, float* logits, 
   m->graph = g;
   m->graph_exec = ge;
   return EVT_OK;
+}
+
+int evt_graph_capture(evt_model* m, const float* img, int batch, float* logits, void* stream) {
+  return graph_capture(m, stream, [&]() {
+    return m->family == 0   ? evt_vit_forward(m, img, batch, logits, stream)
+           : m->family == 1 ? evt_t2t_forward(m, img, batch, logits, stream)
+                            : evt_swin_forward(m, img, batch, logits, stream);
+  });
 }
 
 int evt_graph_launch(evt_model* m, void* stream) {
@@ -1721,18 +1755,23 @@ static int swin_run(evt_model* m, const float* img, int B, float* logits, hipStr
   if (stem96) {  // Conv2d + embedding LayerNorm in one kernel (swin.hip, swin_embed96_kernel)
     ProfScope ps(m, EVT_PROF_PATCH_EMBED, s);
     prof_work(m, 2.0 * rows * 96 * 48,
-              (double)B * 3 * d.image_size * d.image_size * 4 + (double)rows * 96 * es +
-                  (double)rows * stats_slots(96) * 8);
+              (double)B * 3 * d.image_size * d.image_size * (m->img8 ? 1 : 4) +
+                  (double)rows * 96 * es + (double)rows * stats_slots(96) * 8);
     SwinEmbedParams ep;
-    ep.img = img; ep.w = m->patch.w; ep.ldw = m->patch.kpad; ep.bias = m->patch.b;
+    ep.img = img; ep.img8 = m->img8; ep.aff = m->aff; ep.w = m->patch.w; ep.ldw = m->patch.kpad; ep.bias = m->patch.b;
     ep.gamma = m->pnorm_g; ep.beta = m->pnorm_b; ep.x = m->ws.x; ep.stats = m->ws.sx;
     ep.B = B; ep.S = d.image_size; ep.nslots = stats_slots(96); ep.eps = 1e-5f;
     EVT_HIP(swin_embed96_launch(ep, s), "fused patch embedding");
   } else {
   {
     ProfScope ps(m, EVT_PROF_PATCHIFY, s);
-    prof_work(m, 0.0, (double)B * d.in_chans * d.image_size * d.image_size * 4 +
+    prof_work(m, 0.0, (double)B * d.in_chans * d.image_size * d.image_size * (m->img8 ? 1 : 4) +
                           (double)rows * d.in_chans * d.patch_size * d.patch_size * es);
+    if (m->img8)
+      EVT_HIP(swin_patch_u8_launch(dt, m->img8, B, d.in_chans, d.image_size, d.patch_size,
+                                   m->ws.hbuf, pdst, m->aff, s),
+              "patch im2col (uint8)");
+    else
     EVT_HIP(swin_patch_launch(dt, img, B, d.in_chans, d.image_size, d.patch_size, m->ws.hbuf, pdst,
                               s),
             "patch im2col");
@@ -2244,9 +2283,8 @@ int evt_tap_shape(const evt_model* m, int block, int* tokens, int* width) {
   return EVT_OK;
 }
 
-int evt_forward_features(evt_model* m, const float* img, int B, const evt_features_args* a,
-                         void* stream) {
-  if (!m || !img || !a) return fail(EVT_EINVAL, "model, img and args must be non-null");
+// What evt_forward_features checks of (model, outputs, batch); evt_forward_image shares it
+static int validate_features(const evt_model* m, const evt_features_args* a, int B) {
   if (a->n_taps < 0 || a->n_taps > 64) return fail(EVT_EINVAL, "n_taps must be in [0, 64]");
   if (!a->logits && !a->pooled && !a->tokens && a->n_taps == 0)
     return fail(EVT_EINVAL, "no output requested: logits, pooled and tokens are NULL, n_taps is 0");
@@ -2274,15 +2312,164 @@ int evt_forward_features(evt_model* m, const float* img, int B, const evt_featur
     }
   }
   if (align & 15) return fail(EVT_EINVAL, "feature outputs must be 16-byte aligned");
+  return EVT_OK;
+}
+
+static int run_family(evt_model* m, const float* img, int B, float* logits, hipStream_t s) {
+  return m->family == 0   ? vit_run(m, img, B, logits, s)
+         : m->family == 1 ? t2t_run(m, img, B, logits, s)
+                          : swin_run(m, img, B, logits, s);
+}
+
+int evt_forward_features(evt_model* m, const float* img, int B, const evt_features_args* a,
+                         void* stream) {
+  if (!m || !img || !a) return fail(EVT_EINVAL, "model, img and args must be non-null");
+  EVT_RC(validate_features(m, a, B));
   // one lane, on this handle's own workspace, whatever its lane count (as a profiled forward)
   hipStream_t s = (hipStream_t)stream;
   m->feat = a;
   m->feat_next = 0;
-  const int rc = m->family == 0   ? vit_run(m, img, B, a->logits, s)
-                 : m->family == 1 ? t2t_run(m, img, B, a->logits, s)
-                                  : swin_run(m, img, B, a->logits, s);
+  const int rc = run_family(m, img, B, a->logits, s);
   m->feat = nullptr;
   return rc;
+}
+
+// ---- uint8 image input (include/evt_image.h) ------------------------------------------------
+
+static int affine_from(const float* scale, const float* shift, int C, ImgAffine* aff,
+                       const char* what) {
+  if (C < 1 || C > 4) return fail(EVT_EINVAL, std::string(what) + ": uint8 images have 1 to 4 channels");
+  if (!scale || !shift) return fail(EVT_EINVAL, std::string(what) + ": scale and shift must be non-null");
+  *aff = ImgAffine{};
+  for (int c = 0; c < C; ++c) {
+    if (!std::isfinite(scale[c]) || !std::isfinite(shift[c]))
+      return fail(EVT_EINVAL, std::string(what) + ": scale and shift must be finite");
+    aff->scale[c] = scale[c];
+    aff->shift[c] = shift[c];
+  }
+  return EVT_OK;
+}
+
+// The descriptor alone (no model needed), then what the model adds for EVT_IMG_U8_NHWC
+static int validate_image(const evt_model* m, const evt_image_args* in, ImgAffine* aff) {
+  if (!in) return fail(EVT_EINVAL, "image descriptor is NULL");
+  if (!in->data) return fail(EVT_EINVAL, "image data is NULL");
+  if (in->format != EVT_IMG_F32 && in->format != EVT_IMG_U8_NHWC)
+    return fail(EVT_EINVAL, "unknown image format " + std::to_string(in->format));
+  if (!m) return fail(EVT_EINVAL, "model is NULL");
+  if (in->format == EVT_IMG_F32) return EVT_OK;
+  const int C = m->family == 0 ? m->desc.in_chans : m->family == 1 ? m->tdesc.in_chans
+                                                                   : m->sdesc.in_chans;
+  const int S = m->family == 0 ? m->desc.image_size : m->family == 1 ? m->tdesc.image_size
+                                                                     : m->sdesc.image_size;
+  if (C > 4) return fail(EVT_EINVAL, "uint8 input: in_chans must be <= 4");
+  EVT_RC(affine_from(in->scale, in->shift, C, aff, "uint8 input"));
+  const uintptr_t a = (uintptr_t)in->data;
+  if (m->family == 1) return (C == 4 && (a & 3)) ? fail(EVT_EINVAL, "uint8 input: data must be 4-byte aligned") : EVT_OK;
+  const int ps = m->family == 0 ? m->desc.patch_size : m->sdesc.patch_size;
+  if (((int64_t)ps * S * C) % 4)
+    return fail(EVT_EINVAL, "uint8 input: patch_size*image_size*in_chans must be a multiple of 4");
+  if (m->family == 0 && !m->patch_cm && !m->patch_ld)
+    return fail(EVT_EINVAL, "uint8 input: this ViT's patch vectors are not channel-major "
+                            "(patch_size % 8 != 0 with patch_size^2*in_chans % 64 == 0)");
+  // lanes start at multiples of S*S*C bytes: a multiple of 4 (and of 16 for the fused stem)
+  const bool stem96 = m->family == 2 && m->dtype == DT_BF16 && C == 3 && ps == 4 &&
+                      m->stages[0].C == 96 && S % 16 == 0 && S <= 256 && m->stages[0].w == 7;
+  if (a & (stem96 ? 15 : 3))
+    return fail(EVT_EINVAL, stem96 ? "uint8 input: data must be 16-byte aligned (fused Swin stem)"
+                                   : "uint8 input: data must be 4-byte aligned");
+  return EVT_OK;
+}
+
+// A logits-only forward of a uint8 batch, over the handle's lanes like evt_*_forward
+static int image_forward_logits(evt_model* m, const uint8_t* data, const ImgAffine& aff, int B,
+                                float* logits, hipStream_t s) {
+  if (!m->lanes.empty() && !m->prof && B >= (int)m->lanes.size())  // profiling: one lane
+    return lanes_forward(m, nullptr, nullptr, B, logits, s, data, &aff);
+  m->img8 = data;
+  m->aff = aff;
+  const int rc = run_family(m, nullptr, B, logits, s);
+  m->img8 = nullptr;
+  return rc;
+}
+
+int evt_forward_image(evt_model* m, const evt_image_args* in, int B, const evt_features_args* a,
+                      void* stream) {
+  ImgAffine aff;
+  if (!a) return fail(EVT_EINVAL, "image descriptor, outputs and model must be non-null");
+  EVT_RC(validate_image(m, in, &aff));
+  const bool logits_only = a->logits && !a->pooled && !a->tokens && a->n_taps == 0;
+  if (in->format == EVT_IMG_F32) {
+    if (!logits_only) return evt_forward_features(m, (const float*)in->data, B, a, stream);
+    EVT_RC(validate_features(m, a, B));
+    return m->family == 0   ? evt_vit_forward(m, (const float*)in->data, B, a->logits, stream)
+           : m->family == 1 ? evt_t2t_forward(m, (const float*)in->data, B, a->logits, stream)
+                            : evt_swin_forward(m, (const float*)in->data, B, a->logits, stream);
+  }
+  EVT_RC(validate_features(m, a, B));
+  hipStream_t s = (hipStream_t)stream;
+  if (logits_only) return image_forward_logits(m, (const uint8_t*)in->data, aff, B, a->logits, s);
+  m->feat = a;  // one lane, as evt_forward_features
+  m->feat_next = 0;
+  m->img8 = (const uint8_t*)in->data;
+  m->aff = aff;
+  const int rc = run_family(m, nullptr, B, a->logits, s);
+  m->img8 = nullptr;
+  m->feat = nullptr;
+  return rc;
+}
+
+int evt_graph_capture_image(evt_model* m, const evt_image_args* in, int B, float* logits,
+                            void* stream) {
+  ImgAffine aff;
+  EVT_RC(validate_image(m, in, &aff));
+  if (in->format == EVT_IMG_F32)
+    return evt_graph_capture(m, (const float*)in->data, B, logits, stream);
+  if (!logits || !stream)
+    return fail(EVT_EINVAL, "graph capture needs logits and a non-NULL stream");
+  if (B <= 0 || B > m->max_batch)
+    return fail(EVT_EINVAL, "batch must be in [1, max_batch=" + std::to_string(m->max_batch) + "]");
+  const uint8_t* data = (const uint8_t*)in->data;
+  return graph_capture(m, stream, [&]() {
+    return image_forward_logits(m, data, aff, B, logits, (hipStream_t)stream);
+  });
+}
+
+int evt_patchify_u8(int dtype, const uint8_t* img, int B, int C, int HW, int ps, void* out,
+                    int64_t ldo, void* x, const float* cls, const float* pos, int D, float* stats,
+                    const float* scale, const float* shift, void* stream) {
+  if (dtype != EVT_DTYPE_F32 && dtype != EVT_DTYPE_BF16)
+    return fail(EVT_EINVAL, "patchify_u8: dtype must be EVT_DTYPE_F32 or EVT_DTYPE_BF16");
+  ImgAffine aff;
+  EVT_RC(affine_from(scale, shift, C, &aff, "patchify_u8"));
+  if (B < 0 || D <= 0 || !patchify_u8_ok(C, HW, ps, ldo))
+    return fail(EVT_EINVAL, "patchify_u8: bad shape (C <= 4, HW % ps == 0, ps*HW % 4 == 0, "
+                            "ps*HW*C % 4 == 0, ldo >= ps*ps*C, ldo % 8 == 0, C*ps*HW*4 <= 160 KiB)");
+  if (!img || !out || !x || !cls || !pos || ((uintptr_t)out & 15) || ((uintptr_t)img & 3))
+    return fail(EVT_EINVAL, "patchify_u8: img, out, x, cls, pos must be non-null, out 16-B and img "
+                            "4-B aligned");
+  EVT_HIP(patchify_u8_launch(dtype, img, B, C, HW, ps, out, ldo, x, cls, pos, D, stats, aff,
+                             (hipStream_t)stream),
+          "patchify_u8");
+  return EVT_OK;
+}
+
+int evt_unfold_u8(int dtype, const uint8_t* in, int B, int H, int W, int C, int k, int stride,
+                  int pad, void* out, int ldo, float* stats, int nslots, const float* scale,
+                  const float* shift, void* stream) {
+  if (dtype != EVT_DTYPE_F32 && dtype != EVT_DTYPE_BF16)
+    return fail(EVT_EINVAL, "unfold_u8: dtype must be EVT_DTYPE_F32 or EVT_DTYPE_BF16");
+  ImgAffine aff;
+  EVT_RC(affine_from(scale, shift, C, &aff, "unfold_u8"));
+  if (!in || !out || B < 0 || H <= 0 || W <= 0 || k <= 0 || stride <= 0 || pad < 0 ||
+      H + 2 * pad < k || W + 2 * pad < k || ldo < k * k * C || (stats && nslots <= 0) ||
+      ldo > ((C % 4 == 0 && ldo % 4 == 0) ? 1024 : (ldo % 2 == 0 ? 512 : 256)) ||
+      (C == 4 && ((uintptr_t)in & 3)))
+    return fail(EVT_EINVAL, "unfold_u8: bad shape (as evt_unfold; C <= 4, C == 4: in 4-B aligned)");
+  EVT_HIP(unfold_u8_launch(dtype, in, B, H, W, C, k, stride, pad, out, ldo, stats, nslots, aff,
+                           (hipStream_t)stream),
+          "unfold_u8");
+  return EVT_OK;
 }
 
 }  // extern "C"

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "evt_internal.h"  // ImgAffine
+
 namespace evt {
 
 typedef __bf16 bf16;
@@ -25,6 +27,53 @@ template <typename T> __device__ __forceinline__ T from_f32(float x);
 template <> __device__ __forceinline__ float from_f32<float>(float x) { return x; }
 // plain cast: hipcc -O3 emits v_cvt_pk_bf16_f32 (round-to-nearest-even, NaN preserved)
 template <> __device__ __forceinline__ bf16 from_f32<bf16>(float x) { return (bf16)x; }
+
+// ---- uint8 image input (include/evt_image.h) -----------------------------------------------
+// Per-channel affine of a uint8 pixel, by value in the kernel arguments (no device allocation):
+// v = fmaf((float)u, scale[c], shift[c]), one rounding, so the value is the fp32 nearest to the
+// exact u * scale + shift whatever the compiler's contraction setting.
+__device__ __forceinline__ float affine_sel(const float (&a)[4], int c) {
+  return c == 0 ? a[0] : c == 1 ? a[1] : c == 2 ? a[2] : a[3];
+}
+__device__ __forceinline__ float u8_norm(unsigned u, int c, const ImgAffine& a) {
+  return __fmaf_rn((float)u, affine_sel(a.scale, c), affine_sel(a.shift, c));
+}
+// The 4 bytes of w are elements (pix, c), (pix, c + 1), ... of an interleaved [pixels][C] span;
+// each goes, normalised, to the planar fp32 strip [C][per_c] at strip[c * per_c + pix]. c and pix
+// are left at the element after the word. P: float* (generic) or EVT_LDS float*.
+template <typename P>
+__device__ __forceinline__ void deposit_u8x4(P strip, unsigned w, int& c, int& pix, int C,
+                                             int per_c, const ImgAffine& a) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    strip[c * per_c + pix] = u8_norm((w >> (8 * k)) & 255u, c, a);
+    if (++c == C) {
+      c = 0;
+      ++pix;
+    }
+  }
+}
+// Stage `span` interleaved bytes (span = per_c * C, a multiple of 4; src 4-B aligned, 16-B aligned
+// and span % 16 == 0 when vec16) into the planar fp32 strip [C][per_c]; 256 threads.
+__device__ __forceinline__ void stage_u8_strip(float* strip, const uint8_t* __restrict__ src,
+                                               int span, int C, int per_c, bool vec16,
+                                               const ImgAffine& a) {
+  const int tid = threadIdx.x;
+  if (vec16) {
+    for (int i0 = tid * 16; i0 < span; i0 += 256 * 16) {
+      const u32x4 w = *(const u32x4*)(src + i0);
+      int pix = i0 / C, c = i0 - pix * C;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) deposit_u8x4(strip, w[k], c, pix, C, per_c, a);
+    }
+  } else {
+    for (int i0 = tid * 4; i0 < span; i0 += 256 * 4) {
+      const unsigned w = *(const unsigned*)(src + i0);
+      int pix = i0 / C, c = i0 - pix * C;
+      deposit_u8x4(strip, w, c, pix, C, per_c, a);
+    }
+  }
+}
 
 // Load 4 consecutive elements as fp32 (16 B for f32, 8 B for bf16).
 __device__ __forceinline__ f32x4 load4(const float* p) { return *(const f32x4*)p; }

@@ -8,6 +8,12 @@ namespace evt {
 
 enum Dtype : int { DT_F32 = 0, DT_BF16 = 1 };
 
+// uint8 image input (include/evt_image.h): per-channel scale / shift of v = fmaf(u, scale, shift),
+// passed by value in the kernel arguments of every uint8 image reader
+struct ImgAffine {
+  float scale[4], shift[4];
+};
+
 // Epilogue flags of the token-matrix GEMM (see gemm.hip header for the LayerNorm folding).
 enum : int {
   EPI_BIAS = 1,      // + bias[n]
@@ -155,6 +161,13 @@ bool patchify_ld_ok(int C, int HW, int ps, int64_t ldo);
 hipError_t patchify_ld_launch(int dtype, const float* img, int B, int C, int HW, int ps, void* out,
                               int64_t ldo, void* x, const float* cls, const float* pos, int D,
                               float* stats, hipStream_t s);
+// patchify_ld_launch for uint8 NHWC images [B][HW][HW][C] (include/evt_image.h): the same output
+// bytes as patchify_ld_launch on the normalised fp32 NCHW image. patchify_u8_ok: C <= 4,
+// patchify_ld_ok and ps*HW*C % 4 == 0; img 4-B aligned (16-B loads when img and ps*HW*C allow).
+bool patchify_u8_ok(int C, int HW, int ps, int64_t ldo);
+hipError_t patchify_u8_launch(int dtype, const uint8_t* img, int B, int C, int HW, int ps,
+                              void* out, int64_t ldo, void* x, const float* cls, const float* pos,
+                              int D, float* stats, const ImgAffine& aff, hipStream_t s);
 // Keras patch_to_embedding kernel W [(p1 p2 c), N] -> Wcm [(c p1 p2), N] (rows permuted).
 hipError_t patch_weight_cm(const float* W, float* Wcm, int C, int ps, int N, hipStream_t s);
 
@@ -174,6 +187,11 @@ struct PerformerWeights {  // fp32 device pointers, Keras layouts
 hipError_t unfold_launch(int dtype, int in_f32, const void* in, int B, int H, int W, int C, int k,
                          int s, int p, void* out, int ldo, float* stats, int nslots,
                          hipStream_t st);
+// unfold_launch(dtype, in_f32 = 1, ...) for a uint8 NHWC image (C <= 4): the same kernel choice,
+// element order and statistics order, reading v = fmaf(u, scale[c], shift[c]); padding stays 0.
+hipError_t unfold_u8_launch(int dtype, const uint8_t* in, int B, int H, int W, int C, int k, int s,
+                            int p, void* out, int ldo, float* stats, int nslots,
+                            const ImgAffine& aff, hipStream_t st);
 size_t performer_part_floats(int B, int ntok);
 // kqv_perm (bf16): the kqv columns are in the permuted order kqv_permute_launch gives the model's
 // kqv weights (t2t.hip kqv_col: 16-B row pieces per lane); false: the reference order
@@ -203,6 +221,9 @@ struct SwinAttnParams {
 };
 hipError_t swin_patch_launch(int dtype, const float* img, int B, int C, int S, int ps, void* out,
                              int ldo, hipStream_t s);
+// swin_patch_launch for a uint8 NHWC image (C <= 4, ps*S*C % 4 == 0, img 4-B aligned)
+hipError_t swin_patch_u8_launch(int dtype, const uint8_t* img, int B, int C, int S, int ps,
+                                void* out, int ldo, const ImgAffine& aff, hipStream_t s);
 hipError_t ln_rows_launch(int dtype, const void* x, int64_t ld, void* y, const float* gamma,
                           const float* beta, int rows, int D, float eps, float* stats, int nslots,
                           hipStream_t s);
@@ -260,6 +281,8 @@ hipError_t merge_stats_launch(const float* src, int ns, int B, int R, float* dst
 // fused Swin stem (swin.hip): Conv2d(3, 96, k = s = 4) + LayerNorm(96) -> bf16 stream + stats
 struct SwinEmbedParams {
   const float* img;        // [B][3][S][S] fp32 NCHW
+  const uint8_t* img8 = nullptr;  // or (img null) [B][S][S][3] uint8 NHWC, 16-B aligned, with
+  ImgAffine aff{};         //   v = fmaf(u, aff.scale[c], aff.shift[c])
   const void* w;           // packed patch weights [>= 96][ldw] bf16, k = (c, kh, kw), zero past 48
   int64_t ldw;
   const float* bias;       // [96]

@@ -211,23 +211,16 @@ __global__ __launch_bounds__(256) void patchify_cm_kernel(const float* __restric
 // (bf16) or two (f32), the zero tail included. Even ps: k, pd and every run start are even, so the
 // chunk is four 8-B LDS reads (a pair never crosses a run end or pd); odd ps: eight 4-B reads.
 // grid (HW/ps, B); ldo % 8 == 0, ldo >= pd, out 16-B aligned.
+// The gather half, from the staged fp32 strip [C][ps][HW] (shared by the fp32 and uint8 loaders).
 template <typename TO>
-__global__ __launch_bounds__(256) void patchify_ld_kernel(const float* __restrict__ img, int C,
-                                                          int HW, int ps, TO* __restrict__ out,
-                                                          int ldo, TO* __restrict__ x,
-                                                          const float* __restrict__ cls,
-                                                          const float* __restrict__ pos, int D,
-                                                          float* __restrict__ stats) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* strip = (float*)smem;
+__device__ __forceinline__ void patchify_ld_gather(const float* strip, int C, int HW, int ps,
+                                                   TO* __restrict__ out, int ldo,
+                                                   TO* __restrict__ x,
+                                                   const float* __restrict__ cls,
+                                                   const float* __restrict__ pos, int D,
+                                                   float* __restrict__ stats) {
   const int hh = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int np = HW / ps;
-  const int per_c = ps * HW;  // multiple of 4 (checked on the host)
-  for (int c = 0; c < C; ++c) {
-    const float* src = img + (((int64_t)b * C + c) * HW + (int64_t)hh * ps) * HW;
-    for (int i = tid * 4; i < per_c; i += 256 * 4) *(f32x4*)(strip + c * per_c + i) = load4(src + i);  // LDS
-  }
-  __syncthreads();
   const int pd = ps * ps * C;
   const int cpl = ldo >> 3;  // 8-element chunks per output row
   const bool pairs = (ps & 1) == 0;
@@ -296,6 +289,49 @@ __global__ __launch_bounds__(256) void patchify_ld_kernel(const float* __restric
       st[1] = tid == 0 ? s2 : 0.f;
     }
   }
+}
+
+template <typename TO>
+__global__ __launch_bounds__(256) void patchify_ld_kernel(const float* __restrict__ img, int C,
+                                                          int HW, int ps, TO* __restrict__ out,
+                                                          int ldo, TO* __restrict__ x,
+                                                          const float* __restrict__ cls,
+                                                          const float* __restrict__ pos, int D,
+                                                          float* __restrict__ stats) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* strip = (float*)smem;
+  const int hh = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int per_c = ps * HW;  // multiple of 4 (checked on the host)
+  for (int c = 0; c < C; ++c) {
+    const float* src = img + (((int64_t)b * C + c) * HW + (int64_t)hh * ps) * HW;
+    for (int i = tid * 4; i < per_c; i += 256 * 4) *(f32x4*)(strip + c * per_c + i) = load4(src + i);  // LDS
+  }
+  __syncthreads();
+  patchify_ld_gather<TO>(strip, C, HW, ps, out, ldo, x, cls, pos, D, stats);
+}
+
+// patchify_ld_kernel for uint8 NHWC images (include/evt_image.h): rows hh ps .. hh ps + ps - 1 of
+// image b are one contiguous span of ps HW C bytes, read with 16-B loads (vec16: span and image
+// base 16-B aligned) or 4-B loads, normalised (u8_norm, one fmaf per element) and de-interleaved on
+// the way into the same fp32 strip [C][ps][HW]; the gather, the zero tail, the CLS row and its
+// statistics are patchify_ld_gather, so with the same fp32 values in the strip the output bytes are
+// those of patchify_ld_kernel (and of patchify_cm_kernel when ldo == pd).
+template <typename TO>
+__global__ __launch_bounds__(256) void patchify_u8_kernel(const uint8_t* __restrict__ img, int C,
+                                                          int HW, int ps, TO* __restrict__ out,
+                                                          int ldo, TO* __restrict__ x,
+                                                          const float* __restrict__ cls,
+                                                          const float* __restrict__ pos, int D,
+                                                          float* __restrict__ stats, int vec16,
+                                                          ImgAffine aff) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* strip = (float*)smem;
+  const int hh = blockIdx.x, b = blockIdx.y;
+  const int per_c = ps * HW, span = per_c * C;
+  stage_u8_strip(strip, img + ((int64_t)b * HW + (int64_t)hh * ps) * HW * C, span, C, per_c,
+                 vec16 != 0, aff);
+  __syncthreads();
+  patchify_ld_gather<TO>(strip, C, HW, ps, out, ldo, x, cls, pos, D, stats);
 }
 
 // Keras patch_to_embedding kernel [(p1 p2 c), N] -> rows in the channel-major order above.
@@ -400,6 +436,33 @@ hipError_t patchify_ld_launch(int dtype, const float* img, int B, int C, int HW,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(patchify_ld_kernel<float>, grid, dim3(256), lds, s, img, C, HW, ps,
                        (float*)out, (int)ldo, (float*)x, cls, pos, D, stats);
+  }
+  return hipGetLastError();
+}
+
+bool patchify_u8_ok(int C, int HW, int ps, int64_t ldo) {
+  return C <= 4 && patchify_ld_ok(C, HW, ps, ldo) && ((int64_t)ps * HW * C) % 4 == 0;
+}
+
+hipError_t patchify_u8_launch(int dtype, const uint8_t* img, int B, int C, int HW, int ps,
+                              void* out, int64_t ldo, void* x, const float* cls, const float* pos,
+                              int D, float* stats, const ImgAffine& aff, hipStream_t s) {
+  if (!patchify_u8_ok(C, HW, ps, ldo) || ((uintptr_t)out & 15) || ((uintptr_t)img & 3))
+    return hipErrorInvalidValue;
+  if (B <= 0) return hipSuccess;
+  const size_t lds = (size_t)C * ps * HW * sizeof(float);
+  const int vec16 = ((uintptr_t)img & 15) == 0 && ((int64_t)ps * HW * C) % 16 == 0;
+  dim3 grid(HW / ps, B);
+  if (dtype == DT_BF16) {
+    (void)hipFuncSetAttribute((const void*)patchify_u8_kernel<bf16>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(patchify_u8_kernel<bf16>, grid, dim3(256), lds, s, img, C, HW, ps,
+                       (bf16*)out, (int)ldo, (bf16*)x, cls, pos, D, stats, vec16, aff);
+  } else {
+    (void)hipFuncSetAttribute((const void*)patchify_u8_kernel<float>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(patchify_u8_kernel<float>, grid, dim3(256), lds, s, img, C, HW, ps,
+                       (float*)out, (int)ldo, (float*)x, cls, pos, D, stats, vec16, aff);
   }
   return hipGetLastError();
 }

@@ -37,19 +37,12 @@ constexpr float kLog2e = 1.4426950408889634f;
 // One block per (patch row py, image b): the [C][ps][S] fp32 strip of the image is staged in LDS
 // with coalesced 16-B loads, then the S/ps output rows (c, kh, kw) leave as 16-B chunks of 8
 // (coalesced row-contiguous stores), zero padded to ldo.
+// The gather half, from the staged strip (shared by the fp32 and uint8 loaders).
 template <typename TO>
-__global__ __launch_bounds__(256) void swin_patch_kernel(const float* __restrict__ img, int C,
-                                                         int S, int ps, TO* __restrict__ out,
-                                                         int ldo) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* strip = (float*)smem;
+__device__ __forceinline__ void swin_patch_gather(const float* strip, int C, int S, int ps,
+                                                  TO* __restrict__ out, int ldo) {
   const int py = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int np = S / ps, per_c = ps * S, pd = C * ps * ps;
-  for (int c = 0; c < C; ++c) {
-    const float* src = img + (((int64_t)b * C + c) * S + (int64_t)py * ps) * S;
-    for (int i = tid * 4; i < per_c; i += 256 * 4) *(f32x4*)(strip + c * per_c + i) = load4(src + i);  // LDS
-  }
-  __syncthreads();
   TO* orow = out + ((int64_t)b * np + py) * np * ldo;
   const int cpr = ldo / 8;  // 8-element chunks per output row
   for (int e = tid; e < np * cpr; e += 256) {
@@ -68,6 +61,38 @@ __global__ __launch_bounds__(256) void swin_patch_kernel(const float* __restrict
     store4(op, f32x4{v[0], v[1], v[2], v[3]});
     store4(op + 4, f32x4{v[4], v[5], v[6], v[7]});
   }
+}
+
+template <typename TO>
+__global__ __launch_bounds__(256) void swin_patch_kernel(const float* __restrict__ img, int C,
+                                                         int S, int ps, TO* __restrict__ out,
+                                                         int ldo) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* strip = (float*)smem;
+  const int py = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int per_c = ps * S;
+  for (int c = 0; c < C; ++c) {
+    const float* src = img + (((int64_t)b * C + c) * S + (int64_t)py * ps) * S;
+    for (int i = tid * 4; i < per_c; i += 256 * 4) *(f32x4*)(strip + c * per_c + i) = load4(src + i);  // LDS
+  }
+  __syncthreads();
+  swin_patch_gather<TO>(strip, C, S, ps, out, ldo);
+}
+
+// The same for a uint8 NHWC image (include/evt_image.h): the strip of patch row py is ps S C
+// contiguous bytes, normalised and de-interleaved into the same fp32 strip (stage_u8_strip).
+template <typename TO>
+__global__ __launch_bounds__(256) void swin_patch_u8_kernel(const uint8_t* __restrict__ img, int C,
+                                                            int S, int ps, TO* __restrict__ out,
+                                                            int ldo, int vec16, ImgAffine aff) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* strip = (float*)smem;
+  const int py = blockIdx.x, b = blockIdx.y;
+  const int per_c = ps * S;
+  stage_u8_strip(strip, img + ((int64_t)b * S + (int64_t)py * ps) * S * C, per_c * C, C, per_c,
+                 vec16 != 0, aff);
+  __syncthreads();
+  swin_patch_gather<TO>(strip, C, S, ps, out, ldo);
 }
 
 // ---- LayerNorm rows (act dtype in / out) + statistics of the stored output -----------------
@@ -1393,6 +1418,12 @@ constexpr int EMB96_WROW = 144;  // W rows: 64 bf16 (48 + zero pad) + 16 B again
 constexpr int EMB96_XROW = 208;  // staged x rows: 96 bf16 + pad
 constexpr int EMB96_PF = 3;      // strip float4 per thread in flight (12 rows x S/4 <= 768)
 
+// U8: the image is uint8 NHWC (p.img8, include/evt_image.h): the strip of a patch row is 12 S
+// contiguous bytes, one 16-B chunk per thread (3 S / 4 <= 192 chunks), held in registers across the
+// compute of the current row like pf[], then normalised (u8_norm) and de-interleaved into the same
+// [12][S] fp32 strip: chunk byte i is pixel i / 3 of the [4][S] rows, channel i % 3, i.e.
+// strip[(i % 3) 4 S + i / 3]. Everything after the strip is the same code.
+template <bool U8>
 __global__ __launch_bounds__(256) void swin_embed96_kernel(SwinEmbedParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int S = p.S, R = S / 4, q4 = S / 4;
@@ -1409,7 +1440,13 @@ __global__ __launch_bounds__(256) void swin_embed96_kernel(SwinEmbedParams p) {
         *(const u32x4*)((const bf16*)p.w + (int64_t)n * p.ldw + 8 * c);
   }
   f32x4 pf[EMB96_PF];
+  u32x4 pf8 = {0u, 0u, 0u, 0u};
+  const int nch8 = 3 * q4;  // 16-B chunks of a uint8 strip (12 S bytes)
   auto fetch = [&](int pr) {  // strip of patch row pr: row (c, kh) = img[b][c][4 py + kh][0 .. S)
+    if constexpr (U8) {
+      if (tid < nch8) pf8 = *(const u32x4*)(p.img8 + (int64_t)pr * 12 * S + 16 * tid);
+      return;
+    }
     const int b = pr / R, py = pr - b * R;
 #pragma unroll
     for (int k = 0; k < EMB96_PF; ++k) {
@@ -1425,10 +1462,18 @@ __global__ __launch_bounds__(256) void swin_embed96_kernel(SwinEmbedParams p) {
   const int ntt = (R + 15) / 16;
   for (int pr = blockIdx.x; pr < nrow; pr += gridDim.x) {
     __syncthreads();  // the previous row's strip / staging readers are done
+    if constexpr (U8) {
+      if (tid < nch8) {
+        int pix = (16 * tid) / 3, c = 16 * tid - 3 * pix;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) deposit_u8x4(strip, pf8[k], c, pix, 3, 4 * S, p.aff);
+      }
+    } else {
 #pragma unroll
     for (int k = 0; k < EMB96_PF; ++k) {
       const int e = tid + 256 * k;
       if (e < 12 * q4) *(EVT_LDS f32x4*)(strip + 4 * e) = pf[k];  // [r][S] = e / q4, 4 (e % q4)
+    }
     }
     __syncthreads();
     if (pr + (int)gridDim.x < nrow) fetch(pr + gridDim.x);  // lands during this row's compute
@@ -1558,6 +1603,25 @@ hipError_t swin_patch_launch(int dtype, const float* img, int B, int C, int S, i
   else
     hipLaunchKernelGGL(swin_patch_kernel<float>, grid, dim3(256), lds, s, img, C, S, ps,
                        (float*)out, ldo);
+  return hipGetLastError();
+}
+
+hipError_t swin_patch_u8_launch(int dtype, const uint8_t* img, int B, int C, int S, int ps,
+                                void* out, int ldo, const ImgAffine& aff, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  if (S % ps || C * ps * ps > ldo || ldo % 8 || (ps * S) % 4 || C > 4 || (ps * S * C) % 4 ||
+      ((uintptr_t)img & 3))
+    return hipErrorInvalidValue;
+  const size_t lds = (size_t)C * ps * S * sizeof(float);
+  if (lds > 64 * 1024) return hipErrorInvalidValue;
+  const int vec16 = ((uintptr_t)img & 15) == 0 && (ps * S * C) % 16 == 0;
+  const dim3 grid(S / ps, B);
+  if (dtype == DT_BF16)
+    hipLaunchKernelGGL(swin_patch_u8_kernel<bf16>, grid, dim3(256), lds, s, img, C, S, ps,
+                       (bf16*)out, ldo, vec16, aff);
+  else
+    hipLaunchKernelGGL(swin_patch_u8_kernel<float>, grid, dim3(256), lds, s, img, C, S, ps,
+                       (float*)out, ldo, vec16, aff);
   return hipGetLastError();
 }
 
@@ -1693,7 +1757,14 @@ hipError_t swin_embed96_launch(const SwinEmbedParams& p, hipStream_t s) {
   }
   const size_t lds = (size_t)96 * EMB96_WROW + 12 * p.S * 4 + 64 * EMB96_XROW;
   const int rows = p.B * (p.S / 4);
-  hipLaunchKernelGGL(swin_embed96_kernel, dim3(std::min(rows, 4 * ncu)), dim3(256), lds, s, p);
+  if (p.img8) {
+    if ((uintptr_t)p.img8 & 15) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(swin_embed96_kernel<true>, dim3(std::min(rows, 4 * ncu)), dim3(256), lds, s,
+                       p);
+  } else {
+    hipLaunchKernelGGL(swin_embed96_kernel<false>, dim3(std::min(rows, 4 * ncu)), dim3(256), lds, s,
+                       p);
+  }
   return hipGetLastError();
 }
 

@@ -82,17 +82,23 @@ __device__ __forceinline__ float token_sum(float v) {
 // (VW = 4: 4 channels of one pixel, C % 4 == 0; VW = 2: an element pair, which may straddle a
 // pixel, ldo even; VW = 1 otherwise), decomposed into (kh, kw, c) once per lane; per row only the
 // window origin changes. At most 4 accesses per lane (ldo <= 256 * VW).
+// TI = uint8_t (a uint8 image, include/evt_image.h): every element is normalised on the way in,
+// v = fmaf(u, scale[c], shift[c]) with its channel c = r2 - kw C decomposed once per lane like
+// ekh / ekw (its scale / shift held in registers); aff is null for every other TI. Padding and the
+// columns past k k C stay 0, and the (s1, s2) accumulation order is the same for every TI.
 template <typename TI, typename TO, int VW>
-__global__ __launch_bounds__(256) void unfold_kernel(const TI* __restrict__ in, int B, int H, int W,
-                                                     int C, int k, int s, int p, int OH, int OW,
-                                                     TO* __restrict__ out, int ldo,
-                                                     float* __restrict__ stats, int nslots,
-                                                     int rpw) {
+__device__ __forceinline__ void unfold_rows(const TI* __restrict__ in, int B, int H, int W, int C,
+                                            int k, int s, int p, int OH, int OW,
+                                            TO* __restrict__ out, int ldo,
+                                            float* __restrict__ stats, int nslots, int rpw,
+                                            const ImgAffine* aff) {
   constexpr int NE = VW == 4 ? 1 : VW;  // independently decomposed elements per access
+  constexpr bool U8 = std::is_same<TI, uint8_t>::value;
   const int lane = threadIdx.x & 63;
   const int kc = k * C, kk = k * kc;
   int rel[4][NE], ekh[4][NE], ekw[4][NE];
   bool inw[4][NE], col[4];
+  float esc[4][NE], esh[4][NE];  // U8: scale / shift of the element's channel
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     col[i] = (lane + 64 * i) * VW < ldo;
@@ -104,6 +110,10 @@ __global__ __launch_bounds__(256) void unfold_kernel(const TI* __restrict__ in, 
       ekh[i][j] = kh;
       ekw[i][j] = kw;
       rel[i][j] = (kh * W + kw) * C + (r2 - kw * C);
+      if constexpr (U8) {
+        esc[i][j] = affine_sel(aff->scale, r2 - kw * C);
+        esh[i][j] = affine_sel(aff->shift, r2 - kw * C);
+      }
     }
   }
   const int rows = B * OH * OW;  // < 2^31 (checked on the host)
@@ -135,7 +145,16 @@ __global__ __launch_bounds__(256) void unfold_kernel(const TI* __restrict__ in, 
       for (int j = 0; j < NE; ++j) {
         const int ih = ih0 + ekh[i][j], iw = iw0 + ekw[i][j];
         const bool ok = inw[i][j] && ih >= 0 && ih < H && iw >= 0 && iw < W;
-        if constexpr (VW == 4) {
+        if constexpr (U8 && VW == 4) {  // C = 4: the 4 channels of one pixel
+          if (ok) {
+            const unsigned w = *(const unsigned*)(win + rel[i][j]);
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              v[q] = __fmaf_rn((float)((w >> (8 * q)) & 255u), aff->scale[q], aff->shift[q]);
+          }
+        } else if constexpr (U8) {
+          v[j] = ok ? __fmaf_rn((float)win[rel[i][j]], esc[i][j], esh[i][j]) : 0.f;
+        } else if constexpr (VW == 4) {
           if (ok) v = load4(win + rel[i][j]);
         } else {
           v[j] = ok ? to_f32(win[rel[i][j]]) : 0.f;
@@ -170,6 +189,24 @@ __global__ __launch_bounds__(256) void unfold_kernel(const TI* __restrict__ in, 
       }
     }
   }
+}
+
+template <typename TI, typename TO, int VW>
+__global__ __launch_bounds__(256) void unfold_kernel(const TI* __restrict__ in, int B, int H, int W,
+                                                     int C, int k, int s, int p, int OH, int OW,
+                                                     TO* __restrict__ out, int ldo,
+                                                     float* __restrict__ stats, int nslots,
+                                                     int rpw) {
+  unfold_rows<TI, TO, VW>(in, B, H, W, C, k, s, p, OH, OW, out, ldo, stats, nslots, rpw, nullptr);
+}
+
+template <typename TO, int VW>
+__global__ __launch_bounds__(256) void unfold_u8_kernel(const uint8_t* __restrict__ in, int B, int H,
+                                                        int W, int C, int k, int s, int p, int OH,
+                                                        int OW, TO* __restrict__ out, int ldo,
+                                                        float* __restrict__ stats, int nslots,
+                                                        int rpw, ImgAffine aff) {
+  unfold_rows<uint8_t, TO, VW>(in, B, H, W, C, k, s, p, OH, OW, out, ldo, stats, nslots, rpw, &aff);
 }
 
 // kp = prm_exp(k) of one 16-token tile from the random-feature fragments fw (2 m tiles x 4 k
@@ -722,11 +759,13 @@ __global__ __launch_bounds__(64) void cls_rows_kernel(T* __restrict__ x, int nto
 // row (one pixel's 147-vector, zero padded to ldo) leaves as 16-B chunks of 8 elements, 32 lanes
 // per row (ldo / 8 <= 32 chunks); row statistics by shuffles within the 32 lanes. The generic
 // kernel above gathers 4-B elements from 7 image rows per row (1.6 TB/s measured).
-template <typename TO>
-__global__ __launch_bounds__(256) void unfold_k7s4c3_kernel(const float* __restrict__ in, int H,
-                                                            int W, int OW, TO* __restrict__ out,
-                                                            int ldo, float* __restrict__ stats,
-                                                            int nslots) {
+// TI = float, or uint8_t with v = fmaf(u, scale[c], shift[c]) (aff; null for float): the loader of
+// the band is the only difference, the padding stays 0 either way.
+template <typename TI, typename TO>
+__device__ __forceinline__ void unfold_k7s4c3_rows(const TI* __restrict__ in, int H, int W, int OW,
+                                                   TO* __restrict__ out, int ldo,
+                                                   float* __restrict__ stats, int nslots,
+                                                   const ImgAffine* aff) {
   extern __shared__ __attribute__((aligned(16))) float band[];  // [7][Wp][3]
   const int oh = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int Wp = W + 8;  // staged columns: iw = -2 .. W + 5 (zero outside [0, W))
@@ -735,10 +774,16 @@ __global__ __launch_bounds__(256) void unfold_k7s4c3_kernel(const float* __restr
     const int kh = e / Wp, cw = e - kh * Wp, ih = ih0 + kh, iw = cw - 2;
     float v0 = 0.f, v1 = 0.f, v2 = 0.f;
     if (ih >= 0 && ih < H && iw >= 0 && iw < W) {
-      const float* src = in + (((int64_t)b * H + ih) * W + iw) * 3;
-      v0 = src[0];
-      v1 = src[1];
-      v2 = src[2];
+      const TI* src = in + (((int64_t)b * H + ih) * W + iw) * 3;
+      if constexpr (std::is_same<TI, uint8_t>::value) {
+        v0 = __fmaf_rn((float)src[0], aff->scale[0], aff->shift[0]);
+        v1 = __fmaf_rn((float)src[1], aff->scale[1], aff->shift[1]);
+        v2 = __fmaf_rn((float)src[2], aff->scale[2], aff->shift[2]);
+      } else {
+        v0 = src[0];
+        v1 = src[1];
+        v2 = src[2];
+      }
     }
     float* d = band + (kh * Wp + cw) * 3;
     d[0] = v0;
@@ -798,19 +843,41 @@ __global__ __launch_bounds__(256) void unfold_k7s4c3_kernel(const float* __restr
   }
 }
 
+template <typename TO>
+__global__ __launch_bounds__(256) void unfold_k7s4c3_kernel(const float* __restrict__ in, int H,
+                                                            int W, int OW, TO* __restrict__ out,
+                                                            int ldo, float* __restrict__ stats,
+                                                            int nslots) {
+  unfold_k7s4c3_rows<float, TO>(in, H, W, OW, out, ldo, stats, nslots, nullptr);
+}
+
+template <typename TO>
+__global__ __launch_bounds__(256) void unfold_k7s4c3_u8_kernel(const uint8_t* __restrict__ in, int H,
+                                                               int W, int OW, TO* __restrict__ out,
+                                                               int ldo, float* __restrict__ stats,
+                                                               int nslots, ImgAffine aff) {
+  unfold_k7s4c3_rows<uint8_t, TO>(in, H, W, OW, out, ldo, stats, nslots, &aff);
+}
+
+// aff: the uint8 image's affine (TI = uint8_t, which takes every path the fp32 image takes)
 template <typename TI, typename TO>
 hipError_t unfold_t(const void* in, int B, int H, int W, int C, int k, int s, int p, void* out,
-                    int ldo, float* stats, int nslots, hipStream_t st) {
+                    int ldo, float* stats, int nslots, hipStream_t st,
+                    const ImgAffine* aff = nullptr) {
   const int OH = (H + 2 * p - k) / s + 1, OW = (W + 2 * p - k) / s + 1;
   const int64_t rows = (int64_t)B * OH * OW;
   if (rows >= (int64_t)1 << 31) return hipErrorInvalidValue;
-  if constexpr (std::is_same<TI, float>::value) {
+  if constexpr (std::is_same<TI, float>::value || std::is_same<TI, uint8_t>::value) {
     if (k == 7 && s == 4 && p == 2 && C == 3 && ldo % 8 == 0 && ldo <= 256 && nslots <= 32 &&
         (OH - 1) * 4 - 2 + 7 <= H + 6) {
       const size_t lds = (size_t)7 * (W + 8) * 3 * sizeof(float);
       if (lds <= 64 * 1024) {
-        hipLaunchKernelGGL(unfold_k7s4c3_kernel<TO>, dim3(OH, B), dim3(256), lds, st, (const float*)in,
-                           H, W, OW, (TO*)out, ldo, stats, nslots);
+        if constexpr (std::is_same<TI, uint8_t>::value)
+          hipLaunchKernelGGL(unfold_k7s4c3_u8_kernel<TO>, dim3(OH, B), dim3(256), lds, st,
+                             (const uint8_t*)in, H, W, OW, (TO*)out, ldo, stats, nslots, *aff);
+        else
+          hipLaunchKernelGGL(unfold_k7s4c3_kernel<TO>, dim3(OH, B), dim3(256), lds, st, (const float*)in,
+                             H, W, OW, (TO*)out, ldo, stats, nslots);
         return hipGetLastError();
       }
     }
@@ -819,14 +886,25 @@ hipError_t unfold_t(const void* in, int B, int H, int W, int C, int k, int s, in
   if (ldo > 256 * vw) return hipErrorInvalidValue;  // <= 4 accesses per lane
   const int rpw = 4;
   const dim3 grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
+  if constexpr (std::is_same<TI, uint8_t>::value) {
+#define EVT_UNFOLD8(V)                                                                            \
+  hipLaunchKernelGGL((unfold_u8_kernel<TO, V>), grid, dim3(256), 0, st, (const uint8_t*)in, B, H, \
+                     W, C, k, s, p, OH, OW, (TO*)out, ldo, stats, nslots, rpw, *aff)
+    if (vw == 4) EVT_UNFOLD8(4);
+    else if (vw == 2) EVT_UNFOLD8(2);
+    else EVT_UNFOLD8(1);
+#undef EVT_UNFOLD8
+    return hipGetLastError();
+  } else {
 #define EVT_UNFOLD(V)                                                                          \
   hipLaunchKernelGGL((unfold_kernel<TI, TO, V>), grid, dim3(256), 0, st, (const TI*)in, B, H, W, \
                      C, k, s, p, OH, OW, (TO*)out, ldo, stats, nslots, rpw)
-  if (vw == 4) EVT_UNFOLD(4);
-  else if (vw == 2) EVT_UNFOLD(2);
-  else EVT_UNFOLD(1);
+    if (vw == 4) EVT_UNFOLD(4);
+    else if (vw == 2) EVT_UNFOLD(2);
+    else EVT_UNFOLD(1);
 #undef EVT_UNFOLD
-  return hipGetLastError();
+    return hipGetLastError();
+  }
 }
 
 constexpr size_t PF_OUT_LDS = (size_t)(PF_M * 64 + 4 * 64 * 64 + 6 * 64) * sizeof(float);
@@ -879,6 +957,18 @@ hipError_t unfold_launch(int dtype, int in_f32, const void* in, int B, int H, in
     return in_f32 ? unfold_t<float, bf16>(in, B, H, W, C, k, s, p, out, ldo, stats, nslots, st)
                   : unfold_t<bf16, bf16>(in, B, H, W, C, k, s, p, out, ldo, stats, nslots, st);
   return unfold_t<float, float>(in, B, H, W, C, k, s, p, out, ldo, stats, nslots, st);
+}
+
+hipError_t unfold_u8_launch(int dtype, const uint8_t* in, int B, int H, int W, int C, int k, int s,
+                            int p, void* out, int ldo, float* stats, int nslots,
+                            const ImgAffine& aff, hipStream_t st) {
+  if (B <= 0) return hipSuccess;
+  if (k <= 0 || s <= 0 || p < 0 || H + 2 * p < k || W + 2 * p < k || ldo < k * k * C || C > 4 ||
+      (C == 4 && ((uintptr_t)in & 3)))
+    return hipErrorInvalidValue;
+  return dtype == DT_BF16
+             ? unfold_t<uint8_t, bf16>(in, B, H, W, C, k, s, p, out, ldo, stats, nslots, st, &aff)
+             : unfold_t<uint8_t, float>(in, B, H, W, C, k, s, p, out, ldo, stats, nslots, st, &aff);
 }
 
 // token chunks of the kv pass: >= 4 workgroups per image even at 28 x 28 tokens (stage 2)

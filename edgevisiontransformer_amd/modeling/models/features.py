@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from ... import _lib
+from ...images import Uint8Images
 
 MAX_TAPS = 64  # include/evt_features.h: n_taps 0..64
 
@@ -77,11 +78,10 @@ class FeatureOutputs:
         return self._feature_geometry()[2][resolve_taps((block,), self.num_blocks)[0]]
 
     def _checked_image(self, img):
-        from .vit import _to_device_image
+        from .vit import _check_image_shape, _to_device_image
         x, was_numpy = _to_device_image(img, self.device)
-        if x.dim() != 4 or tuple(x.shape[1:]) != tuple(self._image_dims()):
-            raise ValueError(f"expected [B, {', '.join(map(str, self._image_dims()))}], "
-                             f"got {tuple(x.shape)}")
+        c, s = self.cfg.in_chans, self.cfg.image_size
+        _check_image_shape(x, self._image_dims(), (s, s, c))  # a Uint8Images is NHWC everywhere
         return x, was_numpy
 
     def _feature_tensor(self, name: str, t, shape) -> int:
@@ -122,6 +122,12 @@ class FeatureOutputs:
             a.tap_blocks, a.taps = idx, arr
         if b > self._max_batch:
             self._build(b)
+        if isinstance(img, Uint8Images):  # device-resident uint8 NHWC (include/evt_image.h)
+            ia = img.image_args()
+            _lib.check(_lib.load_library().evt_forward_image(
+                ctypes.c_void_p(self._handle), ctypes.byref(ia), b, ctypes.byref(a),
+                ctypes.c_void_p(_lib.stream_ptr(self.device))))
+            return
         _lib.check(_lib.load_library().evt_forward_features(
             ctypes.c_void_p(self._handle), ctypes.c_void_p(img.data_ptr()), b, ctypes.byref(a),
             ctypes.c_void_p(_lib.stream_ptr(self.device))))

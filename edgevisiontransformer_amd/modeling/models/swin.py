@@ -34,7 +34,9 @@ import torch
 from ... import _lib
 from ...weights import SwinConfig, make_swin_params, swin_config, swin_param_shapes
 from .features import FeatureOutputs
-from .vit import _capture_graph, _replay_graph, _to_device_image
+from ...images import Uint8Images
+from .vit import (_capture_graph, _check_image_shape, _forward_u8_into, _replay_graph,
+                  _to_device_image)
 
 
 class SwinTransformer(FeatureOutputs):
@@ -148,7 +150,10 @@ class SwinTransformer(FeatureOutputs):
 
     # -- forward ------------------------------------------------------------------------------
     def forward_into(self, img: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
-        """Enqueue the forward of a device-resident fp32 NCHW batch into `logits`."""
+        """Enqueue the forward of a device-resident fp32 NCHW batch (or a device-resident
+        `Uint8Images`, uint8 NHWC) into `logits`."""
+        if isinstance(img, Uint8Images):
+            return _forward_u8_into(self, img, logits)
         b = img.shape[0]
         if b > self._max_batch:
             self._build(b)
@@ -166,9 +171,8 @@ class SwinTransformer(FeatureOutputs):
     def __call__(self, img: Union[torch.Tensor, np.ndarray]):
         x, was_numpy = _to_device_image(img, self.device)
         c = self.cfg
-        if x.dim() != 4 or tuple(x.shape[1:]) != (c.in_chans, c.image_size, c.image_size):
-            raise ValueError(f"expected NCHW [B, {c.in_chans}, {c.image_size}, {c.image_size}], "
-                             f"got {tuple(x.shape)}")
+        _check_image_shape(x, (c.in_chans, c.image_size, c.image_size),
+                           (c.image_size, c.image_size, c.in_chans))
         logits = torch.empty((x.shape[0], c.num_classes), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             self.forward_into(x, logits)

@@ -26,7 +26,9 @@ import torch
 from ... import _lib
 from ...weights import T2TConfig, make_t2t_params, t2t_config, t2t_param_shapes
 from .features import FeatureOutputs
-from .vit import _capture_graph, _replay_graph, _to_device_image
+from ...images import Uint8Images
+from .vit import (_capture_graph, _check_image_shape, _forward_u8_into, _replay_graph,
+                  _to_device_image)
 
 
 class T2T_ViT(FeatureOutputs):
@@ -121,7 +123,10 @@ class T2T_ViT(FeatureOutputs):
             pass
 
     def forward_into(self, img: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
-        """Enqueue the forward of a device-resident fp32 NHWC batch into `logits`."""
+        """Enqueue the forward of a device-resident fp32 NHWC batch (or a device-resident
+        `Uint8Images`) into `logits`."""
+        if isinstance(img, Uint8Images):
+            return _forward_u8_into(self, img, logits)
         b = img.shape[0]
         if b > self._max_batch:
             self._build(b)
@@ -141,9 +146,8 @@ class T2T_ViT(FeatureOutputs):
     def __call__(self, img: Union[torch.Tensor, np.ndarray]):
         x, was_numpy = _to_device_image(img, self.device)
         c = self.cfg
-        if x.dim() != 4 or tuple(x.shape[1:]) != (c.image_size, c.image_size, c.in_chans):
-            raise ValueError(f"expected NHWC [B, {c.image_size}, {c.image_size}, {c.in_chans}], "
-                             f"got {tuple(x.shape)}")
+        _check_image_shape(x, (c.image_size, c.image_size, c.in_chans),
+                           (c.image_size, c.image_size, c.in_chans))
         logits = torch.empty((x.shape[0], c.num_classes), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             self.forward_into(x, logits)

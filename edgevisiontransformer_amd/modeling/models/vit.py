@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from ... import _lib
+from ...images import Uint8Images
 from .features import FeatureOutputs
 from ...weights import (ViTConfig, make_std_vit_params, make_vit_params, std_vit_param_shapes,
                         vit_config, vit_param_shapes)
@@ -54,7 +55,11 @@ def decode_prune_encoding(prune_encoding: str):
     return prune_setting, num_heads_list, ffn_threshold_list
 
 
-def _to_device_image(img, device) -> Tuple[torch.Tensor, bool]:
+def _to_device_image(img, device):
+    """(device batch, input was numpy). A `Uint8Images` stays one (its bytes moved to the device):
+    the forward then goes through evt_forward_image, which normalises in its first kernel."""
+    if isinstance(img, Uint8Images):
+        return img.to(device), img.is_numpy
     if isinstance(img, np.ndarray):
         return torch.from_numpy(np.ascontiguousarray(img, dtype=np.float32)).to(device), True
     if not isinstance(img, torch.Tensor):
@@ -66,7 +71,30 @@ def _to_device_image(img, device) -> Tuple[torch.Tensor, bool]:
     return img.contiguous(), False
 
 
-def _capture_graph(model, img: torch.Tensor, logits: torch.Tensor) -> None:
+def _check_image_shape(x, native_dims, nhwc_dims) -> None:
+    """ValueError unless x is [B, *native_dims] (fp32) or, a Uint8Images, [B, *nhwc_dims]."""
+    u8 = isinstance(x, Uint8Images)
+    want = tuple(nhwc_dims) if u8 else tuple(native_dims)
+    if len(x.shape) != 4 or tuple(x.shape[1:]) != want:
+        raise ValueError(f"expected {'uint8 NHWC ' if u8 else ''}[B, {', '.join(map(str, want))}], "
+                         f"got {tuple(x.shape)}")
+
+
+def _forward_u8_into(model, img: Uint8Images, logits: torch.Tensor) -> torch.Tensor:
+    """`forward_into` of a device-resident Uint8Images (evt_forward_image, logits only: the batch
+    runs over the handle's lanes like the fp32 forward)."""
+    b = img.shape[0]
+    if b > model._max_batch:
+        model._build(b)
+    args, out = img.image_args(), _lib.evt_features_args()
+    out.logits = logits.data_ptr()
+    _lib.check(_lib.load_library().evt_forward_image(
+        ctypes.c_void_p(model._handle), ctypes.byref(args), b, ctypes.byref(out),
+        ctypes.c_void_p(_lib.stream_ptr(model.device))))
+    return logits
+
+
+def _capture_graph(model, img, logits: torch.Tensor) -> None:
     b = img.shape[0]
     if b > model._max_batch:
         model._build(b)
@@ -74,10 +102,17 @@ def _capture_graph(model, img: torch.Tensor, logits: torch.Tensor) -> None:
     stream = torch.cuda.Stream(model.device)  # capture needs a non-default stream
     stream.wait_stream(torch.cuda.current_stream(model.device))
     with torch.cuda.stream(stream):
-        _lib.check(lib.evt_graph_capture(ctypes.c_void_p(model._handle),
-                                         ctypes.c_void_p(img.data_ptr()), b,
-                                         ctypes.c_void_p(logits.data_ptr()),
-                                         ctypes.c_void_p(stream.cuda_stream)))
+        if isinstance(img, Uint8Images):  # refill img.data in place between replays
+            args = img.image_args()
+            _lib.check(lib.evt_graph_capture_image(ctypes.c_void_p(model._handle),
+                                                   ctypes.byref(args), b,
+                                                   ctypes.c_void_p(logits.data_ptr()),
+                                                   ctypes.c_void_p(stream.cuda_stream)))
+        else:
+            _lib.check(lib.evt_graph_capture(ctypes.c_void_p(model._handle),
+                                             ctypes.c_void_p(img.data_ptr()), b,
+                                             ctypes.c_void_p(logits.data_ptr()),
+                                             ctypes.c_void_p(stream.cuda_stream)))
     torch.cuda.current_stream(model.device).wait_stream(stream)
     model._graph_io = (img, logits, b)  # keep the captured buffers alive
 
@@ -202,7 +237,10 @@ class ViT(FeatureOutputs):
 
     # -- forward ------------------------------------------------------------------------------
     def forward_into(self, img: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
-        """Enqueue the forward of a device-resident fp32 NCHW batch into `logits` (no allocation)."""
+        """Enqueue the forward of a device-resident fp32 NCHW batch (or a device-resident
+        `Uint8Images`, uint8 NHWC) into `logits` (no allocation)."""
+        if isinstance(img, Uint8Images):
+            return _forward_u8_into(self, img, logits)
         b = img.shape[0]
         if b > self._max_batch:
             self._build(b)
@@ -224,9 +262,8 @@ class ViT(FeatureOutputs):
     def __call__(self, img: Union[torch.Tensor, np.ndarray]):
         x, was_numpy = _to_device_image(img, self.device)
         c = self.cfg
-        if x.dim() != 4 or tuple(x.shape[1:]) != (c.in_chans, c.image_size, c.image_size):
-            raise ValueError(f"expected NCHW [B, {c.in_chans}, {c.image_size}, {c.image_size}], "
-                             f"got {tuple(x.shape)}")
+        _check_image_shape(x, (c.in_chans, c.image_size, c.image_size),
+                           (c.image_size, c.image_size, c.in_chans))
         logits = torch.empty((x.shape[0], c.num_classes), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             self.forward_into(x, logits)

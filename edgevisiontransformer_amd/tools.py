@@ -12,8 +12,9 @@ Reference conventions kept (so existing `run.sh`-style sweeps and log scrapers w
   * `sys.argv[1]` selects the sub-command (reference tools.py:1011-1086);
   * `gpu_benchmark` takes the `server_benchmark` flag set (tools.py:7-67): --model, --num_runs (50),
     --warmup_runs (50), --top (average of the K shortest), --precision (2..6), --input_shape
-    (comma list), --io_binding, and accepts --use_gpu / --intra_op_threads / --dtype float32 as
-    no-ops; latency is `timeit.default_timer` around one call, host-synchronised, and the line is
+    (comma list), --io_binding, --dtype (float32, or uint8: seeded random NHWC bytes through
+    `Uint8Images`; --input_shape keeps the family's fp32 meaning), and accepts --use_gpu /
+    --intra_op_threads as no-ops; latency is `timeit.default_timer` around one call, host-synchronised, and the line is
     printed exactly as tools.py:116 does: "{name}  Avg latency: {ms} ms, Std: {ms} ms.";
   * `test_keras_latency` (tools.py:170-213): --test_times + 1 calls, the first dropped,
     "Avg latency: {ms}ms";
@@ -40,6 +41,7 @@ T2T_NAMED = ("t2t_vit_7", "t2t_vit_10", "t2t_vit_12", "t2t_vit_14")
 # widths are heads * 64): modeling/models/vit.py STD_VIT_NAMED
 STD_VIT_NAMED = ("vit_large_patch16_224", "vit_large_patch14_224", "vit_huge_patch14_224")
 SWIN_NAMED = ("swin_tiny", "swin_small", "swin_base", "swin_large")   # get_swin configs (tools.py:282)
+INPUT_DTYPES = ("float32", "uint8")   # --dtype, the reference's "input data type" (tools.py:34)
 
 
 def build_model(name: str, compute_dtype: str, prune_encoding: Optional[str] = None,
@@ -99,14 +101,26 @@ def _image_size(name: str, shape: List[int]) -> int:
     return h
 
 
+def uint8_shape(name: str, shape: List[int]) -> List[int]:
+    """The uint8 NHWC shape of an --input_shape given in the family's fp32 layout."""
+    return list(shape) if name in T2T_NAMED else [shape[0], shape[2], shape[3], shape[1]]
+
+
 def latency_samples(model, shape: List[int], num_runs: int, warmup_runs: int,
-                    io_binding: bool, seed: int = 0, graph: bool = False) -> List[float]:
+                    io_binding: bool, seed: int = 0, graph: bool = False,
+                    uint8: bool = False) -> List[float]:
     """Seconds per call, `timeit.default_timer` around one host-synchronised forward
-    (graph: replay of a captured HIP graph of the device-resident forward)."""
+    (graph: replay of a captured HIP graph of the device-resident forward). uint8: `shape` is
+    [B, S, S, C] and the input a `Uint8Images` of seeded random bytes (ImageNet mean / std)."""
     import torch
     rng = np.random.default_rng(seed)
-    host = rng.standard_normal(shape, dtype=np.float32)   # tools.py:204 / utils.py:482 style
-    dev = torch.from_numpy(host).to(model.device)
+    if uint8:
+        from .images import Uint8Images
+        host = Uint8Images(rng.integers(0, 256, size=shape, dtype=np.uint8))
+        dev = host.to(model.device)
+    else:
+        host = rng.standard_normal(shape, dtype=np.float32)   # tools.py:204 / utils.py:482 style
+        dev = torch.from_numpy(host).to(model.device)
     logits = torch.empty((shape[0], model.num_classes), dtype=torch.float32, device=model.device)
 
     if graph:
@@ -154,7 +168,9 @@ def _server_flags(parser: argparse.ArgumentParser) -> None:
     parser.add_argument("--use_gpu", action="store_true", help="accepted; always the GPU")
     parser.add_argument("--num_runs", type=int, default=50)
     parser.add_argument("--warmup_runs", type=int, default=50)
-    parser.add_argument("--dtype", default="float32", type=str, help="input data type (float32)")
+    parser.add_argument("--dtype", default="float32", type=str,
+                        help="input data type: float32, or uint8 (NHWC bytes, normalised with the "
+                             "ImageNet mean / std inside the forward's first kernel)")
     parser.add_argument("--compute_dtype", default="bf16", choices=["bf16", "f32", "mx8"],
                         help="mx8: MXFP8 encoder Dense layers (ViT family; the quantization axis)")
     parser.add_argument("--intra_op_threads", type=int, default=1, help="accepted; unused")
@@ -167,17 +183,24 @@ def _server_flags(parser: argparse.ArgumentParser) -> None:
     parser.add_argument("--input_shape", default=None, type=str, help="input_shape")
 
 
-def gpu_benchmark(argv: Optional[List[str]] = None) -> str:
+def parse_server_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
+    """The `gpu_benchmark` / `server_benchmark` flag set (host only)."""
     parser = argparse.ArgumentParser()
     _server_flags(parser)
     args = parser.parse_args(argv)
-    if args.dtype != "float32":
-        raise ValueError("input dtype must be float32 (the reference forward's input)")
-    shape = _input_shape(args.model, args.input_shape)
+    if args.dtype not in INPUT_DTYPES:
+        raise ValueError(f"input dtype must be one of {INPUT_DTYPES}")
+    return args
+
+
+def gpu_benchmark(argv: Optional[List[str]] = None) -> str:
+    args = parse_server_args(argv)
+    shape = _input_shape(args.model, args.input_shape)  # the family's fp32 layout either way
     model = build_model(args.model, args.compute_dtype, args.prune_encoding, max_batch=shape[0],
                         image_size=_image_size(args.model, shape))
-    lat = latency_samples(model, shape, args.num_runs, args.warmup_runs, args.io_binding,
-                          graph=args.graph)
+    u8 = args.dtype == "uint8"
+    lat = latency_samples(model, uint8_shape(args.model, shape) if u8 else shape, args.num_runs,
+                          args.warmup_runs, args.io_binding, graph=args.graph, uint8=u8)
     avg, std = summarize(lat, args.top)
     name = args.model + (f"_{args.prune_encoding}" if args.prune_encoding else "")
     line = format_line(name, avg, std, args.precision)
