@@ -211,17 +211,33 @@ struct evt_model : ModelCore {  // a handle: the core, its own workspace, its ow
   // lane fills the CUs a balanced grid leaves idle; measured +2.9 % on T2T-ViT-14 bs256, while
   // Swin lanes measured -1.3 % without the balancing: DESIGN.md, batch lanes)
   int no_balance = 0;
-  // evt_forward_features: the outputs of the forward in flight (null in a plain forward) and the
-  // next entry of its tap list
-  const evt_features_args* feat = nullptr;
-  int feat_next = 0;
-  // evt_forward_image: the uint8 NHWC batch of the forward in flight (null: the fp32 `img`
-  // argument of the run functions) and its per-channel affine
-  const uint8_t* img8 = nullptr;
-  ImgAffine aff{};
 };
 
 namespace {
+
+// The arguments of one forward. The entry points build one and the run functions read it; nothing
+// of a call is kept on the handle (hm_layers, which evt_model_qkv_layout reads later, aside).
+struct ForwardCall {
+  const float* img = nullptr;     // the fp32 batch, or null with
+  const uint8_t* img8 = nullptr;  // a uint8 NHWC batch (evt_forward_image) and
+  ImgAffine aff{};                // its per-channel affine
+  int B = 0;
+  float* logits = nullptr;        // may be null in a features forward (no head then)
+  const evt_features_args* feat = nullptr;  // evt_forward_features outputs (null: plain forward)
+  int feat_next = 0;              // the next entry of feat's tap list
+  hipStream_t s = nullptr;
+  // images [b0, b1) of a logits-only call, on stream `lane`: the input advances by whole images
+  // (4 bytes per element of an fp32 batch, 1 of a uint8 one), the logits by rows
+  ForwardCall slice(int b0, int b1, size_t img_elems, int num_classes, hipStream_t lane) const {
+    ForwardCall c = *this;
+    if (img) c.img += (size_t)b0 * img_elems;
+    if (img8) c.img8 += (size_t)b0 * img_elems;
+    c.B = b1 - b0;
+    c.logits += (size_t)b0 * num_classes;
+    c.s = lane;
+    return c;
+  }
+};
 
 // evt_model_profile: a pair of events around each launch of a forward (profiling forwards only)
 struct ProfScope {
@@ -523,10 +539,11 @@ int feat_export(evt_model* m, const void* x, int64_t ldx, int64_t row_step, floa
 }
 
 // After block `block` of a features forward, its output in ws.x: the tap, if one was asked for
-int feat_tap(evt_model* m, int block, int64_t ldx, int rows, int D, hipStream_t s) {
-  const evt_features_args* a = m->feat;
-  if (!a || m->feat_next >= a->n_taps || a->tap_blocks[m->feat_next] != block) return EVT_OK;
-  return feat_export(m, m->ws.x, ldx, 1, a->taps[m->feat_next++], a->tap_norm != 0, rows, D, s);
+int feat_tap(evt_model* m, ForwardCall& call, int block, int64_t ldx, int rows, int D) {
+  const evt_features_args* a = call.feat;
+  if (!a || call.feat_next >= a->n_taps || a->tap_blocks[call.feat_next] != block) return EVT_OK;
+  return feat_export(m, m->ws.x, ldx, 1, a->taps[call.feat_next++], a->tap_norm != 0, rows, D,
+                     call.s);
 }
 
 // Encoder weights (11 tensors per layer, 12 with the STANDARD qkv bias; evt_vit_num_weights
@@ -620,8 +637,9 @@ int dense_head(const evt_model* m, const DenseW& w, const DenseCall& c, hipStrea
 }
 
 // Encoder layers (transformer_encoder.py:13-18 / :26-34) on the token stream m->ws.x (+ stats sx).
-int run_encoder(evt_model* m, int B, hipStream_t s) {
-  const int D = m->D, T = m->sh.T, rows = B * T;
+int run_encoder(evt_model* m, ForwardCall& call) {
+  const int B = call.B, D = m->D, T = m->sh.T, rows = B * T;
+  hipStream_t s = call.s;
   const float log2e = 1.4426950408889634f;
   m->hm_layers = 0;
   int block = 0;
@@ -695,7 +713,7 @@ int run_encoder(evt_model* m, int B, hipStream_t s) {
       c.stats_out = m->ws.sx;
       EVT_RC(dense(m, L.fc2, c, s));
     }
-    EVT_RC(feat_tap(m, block++, D, rows, D, s));
+    EVT_RC(feat_tap(m, call, block++, D, rows, D));
   }
   return EVT_OK;
 }
@@ -705,8 +723,9 @@ int run_encoder(evt_model* m, int B, hipStream_t s) {
 // MFMA, the residual LN(x) (norm.py:11-12 + residual.py:9) re-formed in the out-proj / FC2
 // epilogues from x and those statistics; the attention and FC1 (GELU) outputs are quantized in
 // their producing kernels' epilogues.
-int run_encoder_mx8(evt_model* m, int B, hipStream_t s) {
-  const int D = m->D, T = m->sh.T, rows = B * T;
+int run_encoder_mx8(evt_model* m, ForwardCall& call) {
+  const int B = call.B, D = m->D, T = m->sh.T, rows = B * T;
+  hipStream_t s = call.s;
   const float log2e = 1.4426950408889634f;
   const int dpad = (int)round_up(D, 128);
   for (const Layer& L : m->layers) {
@@ -1005,32 +1024,21 @@ static int swin_alloc_ws(evt_model* m, int B, hipStream_t s);  // (the Swin sect
 // A forward of B images over the model's lanes (evt_model_set_lanes): lane i takes images
 // [B i / k, B (i + 1) / k) on its own stream, forked from and joined to s by events (a HIP graph
 // capture on s records the lanes as parallel branches)
-typedef int (*ForwardFn)(evt_model*, const float*, int, float*, void*);
-static int run_family(evt_model* m, const float* img, int B, float* logits, hipStream_t s);
-// img8: a uint8 batch (evt_forward_image) instead of img, split at byte offsets b0 * img_elems
-static int lanes_forward(evt_model* m, ForwardFn fwd, const float* img, int B, float* logits,
-                         hipStream_t s, const uint8_t* img8 = nullptr,
-                         const ImgAffine* aff = nullptr) {
+static int run_family(evt_model* m, ForwardCall& call);
+static int lanes_forward(evt_model* m, const ForwardCall& call) {
   // the joins go onto s after every lane's work: a lane stream that shares s's hardware queue
   // would otherwise queue its kernels behind s's wait for the previous lane (measured: lanes
   // serialised in part)
-  const int k = (int)m->lanes.size();
+  const int k = (int)m->lanes.size(), B = call.B;
+  hipStream_t s = call.s;
   EVT_HIP(hipEventRecord(m->lane_ev[0], s), "lanes fork");
   for (int i = 0; i < k; ++i)
     EVT_HIP(hipStreamWaitEvent(m->lane_s[i], m->lane_ev[0], 0), "lane fork wait");
   for (int i = 0; i < k; ++i) {
     const int b0 = (int)((int64_t)B * i / k), b1 = (int)((int64_t)B * (i + 1) / k);
-    if (b1 > b0 && img8) {
-      evt_model* c = m->lanes[i];
-      c->img8 = img8 + (size_t)b0 * m->img_elems;  // 1 byte per element
-      c->aff = *aff;
-      const int rc = run_family(c, nullptr, b1 - b0, logits + (size_t)b0 * m->num_classes,
-                                m->lane_s[i]);
-      c->img8 = nullptr;
-      EVT_RC(rc);
-    } else if (b1 > b0) {
-      EVT_RC(fwd(m->lanes[i], img + (size_t)b0 * m->img_elems, b1 - b0,
-                 logits + (size_t)b0 * m->num_classes, m->lane_s[i]));
+    if (b1 > b0) {
+      ForwardCall lane = call.slice(b0, b1, m->img_elems, m->num_classes, m->lane_s[i]);
+      EVT_RC(run_family(m->lanes[i], lane));
     }
     EVT_HIP(hipEventRecord(m->lane_ev[1 + i], m->lane_s[i]), "lane done");
   }
@@ -1040,18 +1048,30 @@ static int lanes_forward(evt_model* m, ForwardFn fwd, const float* img, int B, f
   return EVT_OK;
 }
 
-// What the three forwards (`fwd`: the caller itself) open with: the argument checks, then the lane
-// dispatch. RUN_HERE (no error code is positive): the caller runs the forward on this handle.
-constexpr int RUN_HERE = 1;
-static int forward_prologue(evt_model* m, int family, const char* wrong_family, ForwardFn fwd,
-                            const float* img, int B, float* logits, hipStream_t s) {
-  if (!m || !img || !logits) return fail(EVT_EINVAL, "model, img and logits must be non-null");
-  if (m->family != family) return fail(EVT_EINVAL, wrong_family);
+static int check_batch(const evt_model* m, int B) {
   if (B <= 0 || B > m->max_batch)
     return fail(EVT_EINVAL, "batch must be in [1, max_batch=" + std::to_string(m->max_batch) + "]");
-  if (!m->lanes.empty() && !m->prof && B >= (int)m->lanes.size())  // profiling: one lane
-    return lanes_forward(m, fwd, img, B, logits, s);
-  return RUN_HERE;
+  return EVT_OK;
+}
+
+// Every forward, eager or captured: over the lanes when the caller asked for them (logits-only
+// forwards do), the handle has lanes, is not profiling (profiling: one lane) and every lane gets
+// an image; on this handle's own workspace otherwise.
+static int forward(evt_model* m, ForwardCall& call, bool use_lanes) {
+  EVT_RC(check_batch(m, call.B));
+  if (use_lanes && !m->lanes.empty() && !m->prof && call.B >= (int)m->lanes.size())
+    return lanes_forward(m, call);
+  return run_family(m, call);
+}
+
+// What evt_{vit,t2t,swin}_forward are: the argument checks, then the forward of an fp32 batch
+static int family_forward(evt_model* m, int family, const char* wrong_family, const float* img,
+                          int B, float* logits, void* stream) {
+  if (!m || !img || !logits) return fail(EVT_EINVAL, "model, img and logits must be non-null");
+  if (m->family != family) return fail(EVT_EINVAL, wrong_family);
+  ForwardCall call;
+  call.img = img; call.B = B; call.logits = logits; call.s = (hipStream_t)stream;
+  return forward(m, call, true);
 }
 
 // The ViT workspace for B images (activation buffers only; lanes allocate their own)
@@ -1145,32 +1165,37 @@ int evt_vit_create(const evt_vit_desc* desc, const float* const* w, int n_weight
 
 // The final token map and the pooled (CLS) vector of a ViT / T2T-ViT features forward, from the
 // stream the last encoder block left in ws.x
-static int encoder_features(evt_model* m, int B, hipStream_t s) {
-  const evt_features_args* a = m->feat;
-  const int D = m->D, T = m->sh.T;
+static int encoder_features(evt_model* m, const ForwardCall& call) {
+  const evt_features_args* a = call.feat;
+  const int B = call.B, D = m->D, T = m->sh.T;
+  hipStream_t s = call.s;
   const bool norm = m->norm_g != nullptr;  // REFERENCE ViT: no final LayerNorm (vit.py:54)
   if (a->tokens) EVT_RC(feat_export(m, m->ws.x, D, 1, a->tokens, norm, B * T, D, s));
   if (a->pooled) EVT_RC(feat_export(m, m->ws.x, D, T, a->pooled, norm, B, D, s));
   return EVT_OK;
 }
 
-// The ViT forward of B images on this handle's own workspace. In a features forward (m->feat) the
-// taps, tokens and pooled are exported along the way and logits may be NULL (no head then).
-static int vit_run(evt_model* m, const float* img, int B, float* logits, hipStream_t s) {
+// The ViT forward of call.B images on this handle's own workspace. In a features forward
+// (call.feat) the taps, tokens and pooled are exported along the way and logits may be NULL (no
+// head then).
+static int vit_run(evt_model* m, ForwardCall& call) {
   const evt_vit_desc& d = m->desc;
   const Shape& sh = m->sh;
-  const int D = d.dim, T = sh.T, dt = m->dtype;
+  const int B = call.B, D = d.dim, T = sh.T, dt = m->dtype;
+  const float* img = call.img;
+  float* logits = call.logits;
+  hipStream_t s = call.s;
   prof_reset(m);
   // patch embedding (vit.py:45-51): rearrange -> Dense(D) + pos, CLS row = cls + pos[0]
   {
     ProfScope ps(m, EVT_PROF_PATCHIFY, s);
-    prof_work(m, 0.0, (double)B * d.in_chans * d.image_size * d.image_size * (m->img8 ? 1 : 4) +
+    prof_work(m, 0.0, (double)B * d.in_chans * d.image_size * d.image_size * (call.img8 ? 1 : 4) +
                           (double)B * (sh.P * sh.pdst + D) * elem_size(dt) +
                           (double)B * stats_slots(D) * 8);  // image read, patch rows + CLS rows
-    if (m->img8)  // uint8 NHWC (evt_forward_image): channel-major rows at stride pdst
-      EVT_HIP(patchify_u8_launch(dt, m->img8, B, d.in_chans, d.image_size, d.patch_size,
+    if (call.img8)  // uint8 NHWC (evt_forward_image): channel-major rows at stride pdst
+      EVT_HIP(patchify_u8_launch(dt, call.img8, B, d.in_chans, d.image_size, d.patch_size,
                                  m->ws.apatch, sh.pdst, m->ws.x, m->cls, m->pos, D, m->ws.sx,
-                                 m->aff, s),
+                                 call.aff, s),
               "patchify (uint8)");
     else if (m->patch_ld)
       EVT_HIP(patchify_ld_launch(dt, img, B, d.in_chans, d.image_size, d.patch_size, m->ws.apatch,
@@ -1190,8 +1215,8 @@ static int vit_run(evt_model* m, const float* img, int B, float* logits, hipStre
     c.resid = m->pos_h; c.ldr = m->pos_h ? D : 0;  // bf16 table for the persistent kernel
     EVT_RC(dense(m, m->patch, c, s));
   }
-  EVT_RC(m->mx8 ? run_encoder_mx8(m, B, s) : run_encoder(m, B, s));
-  if (m->feat) EVT_RC(encoder_features(m, B, s));
+  EVT_RC(m->mx8 ? run_encoder_mx8(m, call) : run_encoder(m, call));
+  if (call.feat) EVT_RC(encoder_features(m, call));
   if (!logits) return EVT_OK;
   ProfScope ps_head(m, EVT_PROF_HEAD, s);
   if (m->standard) {  // final LayerNorm of the CLS rows folded into the Linear head
@@ -1221,10 +1246,7 @@ static int vit_run(evt_model* m, const float* img, int B, float* logits, hipStre
 }
 
 int evt_vit_forward(evt_model* m, const float* img, int B, float* logits, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const int pre = forward_prologue(m, 0, "model is not a ViT (use evt_t2t_forward)",
-                                   evt_vit_forward, img, B, logits, s);
-  return pre != RUN_HERE ? pre : vit_run(m, img, B, logits, s);
+  return family_forward(m, 0, "model is not a ViT (use evt_t2t_forward)", img, B, logits, stream);
 }
 
 // ---- T2T-ViT ----------------------------------------------------------------------------
@@ -1325,10 +1347,12 @@ int evt_t2t_create(const evt_t2t_desc* desc, const float* const* w, int n_weight
 }
 
 // The T2T-ViT forward on this handle's own workspace (features forwards: as vit_run)
-static int t2t_run(evt_model* m, const float* img, int B, float* logits, hipStream_t s) {
+static int t2t_run(evt_model* m, ForwardCall& call) {
   prof_reset(m);
   const evt_t2t_desc& d = m->tdesc;
-  const int dt = d.dtype, D = d.dim, T = m->sh.T, P = m->sh.P, S = d.image_size;
+  const int B = call.B, dt = d.dtype, D = d.dim, T = m->sh.T, P = m->sh.P, S = d.image_size;
+  float* logits = call.logits;
+  hipStream_t s = call.s;
   const int g1 = m->grid[0], g2 = m->grid[1];
   const int t1 = g1 * g1, t2 = g2 * g2;
   // iteration 1: soft_split0 (k7 s4 p2) of the NHWC image -> TokenPerformer    (t2t_vit.py:66-68)
@@ -1339,16 +1363,16 @@ static int t2t_run(evt_model* m, const float* img, int B, float* logits, hipStre
   const Performer& P1 = m->perf[0];
   {
     ProfScope ps(m, EVT_PROF_T2T_UNFOLD, s);
-    prof_work(m, 0.0, (double)B * S * S * d.in_chans * (m->img8 ? 1 : 4) +
+    prof_work(m, 0.0, (double)B * S * S * d.in_chans * (call.img8 ? 1 : 4) +
                           (double)B * t1 * P1.din * es + (double)B * t1 * stats_slots(P1.din) * 8);
-    if (m->img8)
-      EVT_HIP(unfold_u8_launch(dt, m->img8, B, S, S, d.in_chans, 7, 4, 2, m->ws.u, P1.dpad,
-                               m->ws.su, stats_slots(P1.din), m->aff, s),
+    if (call.img8)
+      EVT_HIP(unfold_u8_launch(dt, call.img8, B, S, S, d.in_chans, 7, 4, 2, m->ws.u, P1.dpad,
+                               m->ws.su, stats_slots(P1.din), call.aff, s),
               "soft_split0 (uint8)");
     else
-    EVT_HIP(unfold_launch(dt, 1, img, B, S, S, d.in_chans, 7, 4, 2, m->ws.u, P1.dpad, m->ws.su,
-                          stats_slots(P1.din), s),
-            "soft_split0");
+      EVT_HIP(unfold_launch(dt, 1, call.img, B, S, S, d.in_chans, 7, 4, 2, m->ws.u, P1.dpad,
+                            m->ws.su, stats_slots(P1.din), s),
+              "soft_split0");
   }
   {
     ProfScope ps(m, EVT_PROF_T2T_KQV, s);
@@ -1456,8 +1480,8 @@ static int t2t_run(evt_model* m, const float* img, int B, float* logits, hipStre
     c.pos = m->pos; c.ldp = D; c.P = P; c.stats_out = m->ws.sx;
     EVT_RC(dense(m, m->project, c, s));
   }
-  EVT_RC(run_encoder(m, B, s));  // :127
-  if (m->feat) EVT_RC(encoder_features(m, B, s));
+  EVT_RC(run_encoder(m, call));  // :127
+  if (call.feat) EVT_RC(encoder_features(m, call));
   if (!logits) return EVT_OK;
   {  // LayerNorm of the CLS rows folded into the classifier (:129-134)
     ProfScope ps(m, EVT_PROF_HEAD, s);
@@ -1471,10 +1495,8 @@ static int t2t_run(evt_model* m, const float* img, int B, float* logits, hipStre
 }
 
 int evt_t2t_forward(evt_model* m, const float* img, int B, float* logits, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const int pre = forward_prologue(m, 1, "model is not a T2T-ViT (use evt_vit_forward)",
-                                   evt_t2t_forward, img, B, logits, s);
-  return pre != RUN_HERE ? pre : t2t_run(m, img, B, logits, s);
+  return family_forward(m, 1, "model is not a T2T-ViT (use evt_vit_forward)", img, B, logits,
+                        stream);
 }
 
 int evt_model_profile(evt_model* m, int enable) {
@@ -1623,10 +1645,8 @@ static int graph_capture(evt_model* m, void* stream, const std::function<int()>&
 }
 
 int evt_graph_capture(evt_model* m, const float* img, int batch, float* logits, void* stream) {
-  return graph_capture(m, stream, [&]() {
-    return m->family == 0   ? evt_vit_forward(m, img, batch, logits, stream)
-           : m->family == 1 ? evt_t2t_forward(m, img, batch, logits, stream)
-                            : evt_swin_forward(m, img, batch, logits, stream);
+  return graph_capture(m, stream, [&]() {  // any family: the handle's own
+    return family_forward(m, m->family, "", img, batch, logits, stream);
   });
 }
 
@@ -1739,10 +1759,12 @@ int evt_swin_create(const evt_swin_desc* desc, const float* const* w, int n_weig
 }
 
 // The Swin forward on this handle's own workspace (features forwards: as vit_run)
-static int swin_run(evt_model* m, const float* img, int B, float* logits, hipStream_t s) {
+static int swin_run(evt_model* m, ForwardCall& call) {
   prof_reset(m);
   const evt_swin_desc& d = m->sdesc;
-  const int dt = d.dtype;
+  const int B = call.B, dt = d.dtype;
+  float* logits = call.logits;
+  hipStream_t s = call.s;
   const SwinStage& s0 = m->stages[0];
   const int pdst = (int)round_up(d.in_chans * d.patch_size * d.patch_size, PAD_K);
   const float scale_log2 = 0.17677669529663687f * 1.4426950408889634f;  // 32^-0.5 * log2(e)
@@ -1755,26 +1777,27 @@ static int swin_run(evt_model* m, const float* img, int B, float* logits, hipStr
   if (stem96) {  // Conv2d + embedding LayerNorm in one kernel (swin.hip, swin_embed96_kernel)
     ProfScope ps(m, EVT_PROF_PATCH_EMBED, s);
     prof_work(m, 2.0 * rows * 96 * 48,
-              (double)B * 3 * d.image_size * d.image_size * (m->img8 ? 1 : 4) +
+              (double)B * 3 * d.image_size * d.image_size * (call.img8 ? 1 : 4) +
                   (double)rows * 96 * es + (double)rows * stats_slots(96) * 8);
     SwinEmbedParams ep;
-    ep.img = img; ep.img8 = m->img8; ep.aff = m->aff; ep.w = m->patch.w; ep.ldw = m->patch.kpad; ep.bias = m->patch.b;
+    ep.img = call.img; ep.img8 = call.img8; ep.aff = call.aff;
+    ep.w = m->patch.w; ep.ldw = m->patch.kpad; ep.bias = m->patch.b;
     ep.gamma = m->pnorm_g; ep.beta = m->pnorm_b; ep.x = m->ws.x; ep.stats = m->ws.sx;
     ep.B = B; ep.S = d.image_size; ep.nslots = stats_slots(96); ep.eps = 1e-5f;
     EVT_HIP(swin_embed96_launch(ep, s), "fused patch embedding");
   } else {
   {
     ProfScope ps(m, EVT_PROF_PATCHIFY, s);
-    prof_work(m, 0.0, (double)B * d.in_chans * d.image_size * d.image_size * (m->img8 ? 1 : 4) +
+    prof_work(m, 0.0, (double)B * d.in_chans * d.image_size * d.image_size * (call.img8 ? 1 : 4) +
                           (double)rows * d.in_chans * d.patch_size * d.patch_size * es);
-    if (m->img8)
-      EVT_HIP(swin_patch_u8_launch(dt, m->img8, B, d.in_chans, d.image_size, d.patch_size,
-                                   m->ws.hbuf, pdst, m->aff, s),
+    if (call.img8)
+      EVT_HIP(swin_patch_u8_launch(dt, call.img8, B, d.in_chans, d.image_size, d.patch_size,
+                                   m->ws.hbuf, pdst, call.aff, s),
               "patch im2col (uint8)");
     else
-    EVT_HIP(swin_patch_launch(dt, img, B, d.in_chans, d.image_size, d.patch_size, m->ws.hbuf, pdst,
-                              s),
-            "patch im2col");
+      EVT_HIP(swin_patch_launch(dt, call.img, B, d.in_chans, d.image_size, d.patch_size,
+                                m->ws.hbuf, pdst, s),
+              "patch im2col");
   }
   {
     ProfScope ps(m, EVT_PROF_PATCH_EMBED, s);
@@ -1898,11 +1921,11 @@ static int swin_run(evt_model* m, const float* img, int B, float* logits, hipStr
         EVT_RC(dense(m, bl.fc2, c, s));
       }
       }
-      EVT_RC(feat_tap(m, block, Cst, rows, C, s));  // either way the block's output is in ws.x
+      EVT_RC(feat_tap(m, call, block, Cst, rows, C));  // either way the block's output is in ws.x
     }
   }
   const SwinStage& sl = m->stages.back();
-  const evt_features_args* fa = m->feat;
+  const evt_features_args* fa = call.feat;
   if (fa && fa->tokens)  // LN(x) of the last stage, its padding columns [C, Cst) dropped
     EVT_RC(feat_export(m, m->ws.x, sl.Cst, 1, fa->tokens, true, B * sl.R * sl.R, sl.C, s));
   if (!logits && !(fa && fa->pooled)) return EVT_OK;
@@ -1928,10 +1951,7 @@ static int swin_run(evt_model* m, const float* img, int B, float* logits, hipStr
 }
 
 int evt_swin_forward(evt_model* m, const float* img, int B, float* logits, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const int pre = forward_prologue(m, 2, "model is not a Swin Transformer", evt_swin_forward, img,
-                                   B, logits, s);
-  return pre != RUN_HERE ? pre : swin_run(m, img, B, logits, s);
+  return family_forward(m, 2, "model is not a Swin Transformer", img, B, logits, stream);
 }
 
 int evt_window_attention(int dtype, const void* qkv, int64_t ldq, void* out, int64_t ldo,
@@ -2288,8 +2308,7 @@ static int validate_features(const evt_model* m, const evt_features_args* a, int
   if (a->n_taps < 0 || a->n_taps > 64) return fail(EVT_EINVAL, "n_taps must be in [0, 64]");
   if (!a->logits && !a->pooled && !a->tokens && a->n_taps == 0)
     return fail(EVT_EINVAL, "no output requested: logits, pooled and tokens are NULL, n_taps is 0");
-  if (B <= 0 || B > m->max_batch)
-    return fail(EVT_EINVAL, "batch must be in [1, max_batch=" + std::to_string(m->max_batch) + "]");
+  EVT_RC(check_batch(m, B));  // (here, ahead of forward's own: the order the checks fire in)
   if (a->tap_norm != 0 && a->tap_norm != 1) return fail(EVT_EINVAL, "tap_norm must be 0 or 1");
   if (a->tap_norm && (m->family == 2 || !m->norm_g))
     return fail(EVT_EINVAL, m->family == 2
@@ -2315,23 +2334,18 @@ static int validate_features(const evt_model* m, const evt_features_args* a, int
   return EVT_OK;
 }
 
-static int run_family(evt_model* m, const float* img, int B, float* logits, hipStream_t s) {
-  return m->family == 0   ? vit_run(m, img, B, logits, s)
-         : m->family == 1 ? t2t_run(m, img, B, logits, s)
-                          : swin_run(m, img, B, logits, s);
+static int run_family(evt_model* m, ForwardCall& call) {
+  return m->family == 0 ? vit_run(m, call) : m->family == 1 ? t2t_run(m, call) : swin_run(m, call);
 }
 
 int evt_forward_features(evt_model* m, const float* img, int B, const evt_features_args* a,
                          void* stream) {
   if (!m || !img || !a) return fail(EVT_EINVAL, "model, img and args must be non-null");
   EVT_RC(validate_features(m, a, B));
+  ForwardCall call;
+  call.img = img; call.B = B; call.logits = a->logits; call.feat = a; call.s = (hipStream_t)stream;
   // one lane, on this handle's own workspace, whatever its lane count (as a profiled forward)
-  hipStream_t s = (hipStream_t)stream;
-  m->feat = a;
-  m->feat_next = 0;
-  const int rc = run_family(m, img, B, a->logits, s);
-  m->feat = nullptr;
-  return rc;
+  return forward(m, call, false);
 }
 
 // ---- uint8 image input (include/evt_image.h) ------------------------------------------------
@@ -2381,58 +2395,40 @@ static int validate_image(const evt_model* m, const evt_image_args* in, ImgAffin
   return EVT_OK;
 }
 
-// A logits-only forward of a uint8 batch, over the handle's lanes like evt_*_forward
-static int image_forward_logits(evt_model* m, const uint8_t* data, const ImgAffine& aff, int B,
-                                float* logits, hipStream_t s) {
-  if (!m->lanes.empty() && !m->prof && B >= (int)m->lanes.size())  // profiling: one lane
-    return lanes_forward(m, nullptr, nullptr, B, logits, s, data, &aff);
-  m->img8 = data;
-  m->aff = aff;
-  const int rc = run_family(m, nullptr, B, logits, s);
-  m->img8 = nullptr;
-  return rc;
+// A call of B images from a validated image descriptor (aff: validate_image's; uint8 only reads it)
+static ForwardCall image_call(const evt_image_args* in, const ImgAffine& aff, int B, float* logits,
+                              void* stream) {
+  ForwardCall call;
+  if (in->format == EVT_IMG_F32) call.img = (const float*)in->data;
+  else call.img8 = (const uint8_t*)in->data;
+  call.aff = aff; call.B = B; call.logits = logits; call.s = (hipStream_t)stream;
+  return call;
 }
 
 int evt_forward_image(evt_model* m, const evt_image_args* in, int B, const evt_features_args* a,
                       void* stream) {
-  ImgAffine aff;
+  ImgAffine aff{};
   if (!a) return fail(EVT_EINVAL, "image descriptor, outputs and model must be non-null");
   EVT_RC(validate_image(m, in, &aff));
-  const bool logits_only = a->logits && !a->pooled && !a->tokens && a->n_taps == 0;
-  if (in->format == EVT_IMG_F32) {
-    if (!logits_only) return evt_forward_features(m, (const float*)in->data, B, a, stream);
-    EVT_RC(validate_features(m, a, B));
-    return m->family == 0   ? evt_vit_forward(m, (const float*)in->data, B, a->logits, stream)
-           : m->family == 1 ? evt_t2t_forward(m, (const float*)in->data, B, a->logits, stream)
-                            : evt_swin_forward(m, (const float*)in->data, B, a->logits, stream);
-  }
   EVT_RC(validate_features(m, a, B));
-  hipStream_t s = (hipStream_t)stream;
-  if (logits_only) return image_forward_logits(m, (const uint8_t*)in->data, aff, B, a->logits, s);
-  m->feat = a;  // one lane, as evt_forward_features
-  m->feat_next = 0;
-  m->img8 = (const uint8_t*)in->data;
-  m->aff = aff;
-  const int rc = run_family(m, nullptr, B, a->logits, s);
-  m->img8 = nullptr;
-  m->feat = nullptr;
-  return rc;
+  // logits alone: over the handle's lanes, like evt_*_forward; anything more: a features forward
+  const bool logits_only = a->logits && !a->pooled && !a->tokens && a->n_taps == 0;
+  ForwardCall call = image_call(in, aff, B, a->logits, stream);
+  if (!logits_only) call.feat = a;
+  return forward(m, call, logits_only);
 }
 
 int evt_graph_capture_image(evt_model* m, const evt_image_args* in, int B, float* logits,
                             void* stream) {
-  ImgAffine aff;
+  ImgAffine aff{};
   EVT_RC(validate_image(m, in, &aff));
   if (in->format == EVT_IMG_F32)
     return evt_graph_capture(m, (const float*)in->data, B, logits, stream);
   if (!logits || !stream)
     return fail(EVT_EINVAL, "graph capture needs logits and a non-NULL stream");
-  if (B <= 0 || B > m->max_batch)
-    return fail(EVT_EINVAL, "batch must be in [1, max_batch=" + std::to_string(m->max_batch) + "]");
-  const uint8_t* data = (const uint8_t*)in->data;
-  return graph_capture(m, stream, [&]() {
-    return image_forward_logits(m, data, aff, B, logits, (hipStream_t)stream);
-  });
+  EVT_RC(check_batch(m, B));  // ahead of the capture's own checks, and of the previous graph's end
+  ForwardCall call = image_call(in, aff, B, logits, stream);
+  return graph_capture(m, stream, [&]() { return forward(m, call, true); });
 }
 
 int evt_patchify_u8(int dtype, const uint8_t* img, int B, int C, int HW, int ps, void* out,

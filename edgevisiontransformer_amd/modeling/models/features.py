@@ -27,6 +27,7 @@ import torch
 
 from ... import _lib
 from ...images import Uint8Images
+from ._handle import ModelHandle
 
 MAX_TAPS = 64  # include/evt_features.h: n_taps 0..64
 
@@ -56,10 +57,10 @@ def resolve_taps(taps: Sequence[int], num_blocks: int, *, tap_norm: bool = False
     return out
 
 
-class FeatureOutputs:
-    """Mixed into ViT, T2T_ViT and SwinTransformer. The host class provides `_feature_geometry()`
-    -> (F, T, [(tokens, width) per block]), `_image_dims()` -> the [1:] shape of its input,
-    `_TAP_NORM_OK`, and the handle plumbing (`_handle`, `_build`, `_max_batch`, `device`)."""
+class FeatureOutputs(ModelHandle):
+    """What ViT, T2T_ViT and SwinTransformer derive from: the feature outputs on top of the handle
+    plumbing (_handle.py). The model class provides `_feature_geometry()` -> (F, T, [(tokens,
+    width) per block]), `_image_dims()` -> the [1:] shape of its input, and `_TAP_NORM_OK`."""
 
     _TAP_NORM_OK = False
 
@@ -76,13 +77,6 @@ class FeatureOutputs:
     def tap_shape(self, block: int) -> Tuple[int, int]:
         """(tokens per image, width) of the tap after `block` (negative: from the last)."""
         return self._feature_geometry()[2][resolve_taps((block,), self.num_blocks)[0]]
-
-    def _checked_image(self, img):
-        from .vit import _check_image_shape, _to_device_image
-        x, was_numpy = _to_device_image(img, self.device)
-        c, s = self.cfg.in_chans, self.cfg.image_size
-        _check_image_shape(x, self._image_dims(), (s, s, c))  # a Uint8Images is NHWC everywhere
-        return x, was_numpy
 
     def _feature_tensor(self, name: str, t, shape) -> int:
         if t is None:
@@ -120,17 +114,11 @@ class FeatureOutputs:
         a.n_taps, a.tap_norm = len(blocks), int(bool(tap_norm))
         if blocks:
             a.tap_blocks, a.taps = idx, arr
-        if b > self._max_batch:
-            self._build(b)
         if isinstance(img, Uint8Images):  # device-resident uint8 NHWC (include/evt_image.h)
-            ia = img.image_args()
-            _lib.check(_lib.load_library().evt_forward_image(
-                ctypes.c_void_p(self._handle), ctypes.byref(ia), b, ctypes.byref(a),
-                ctypes.c_void_p(_lib.stream_ptr(self.device))))
-            return
+            return self._forward_image(img, a)
+        self._fit(img)
         _lib.check(_lib.load_library().evt_forward_features(
-            ctypes.c_void_p(self._handle), ctypes.c_void_p(img.data_ptr()), b, ctypes.byref(a),
-            ctypes.c_void_p(_lib.stream_ptr(self.device))))
+            self._ptr(), ctypes.c_void_p(img.data_ptr()), b, ctypes.byref(a), self._stream()))
 
     def features(self, img, *, tokens: bool = False, taps: Sequence[int] = (),
                  tap_norm: bool = False, logits: bool = False) -> Dict[str, object]:

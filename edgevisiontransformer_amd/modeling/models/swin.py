@@ -24,9 +24,8 @@ reference's clamp) is not 7 or 12 or does not divide its resolution.
 """
 from __future__ import annotations
 
-import ctypes
 import re
-from typing import Dict, List, Optional, Sequence, Union
+from typing import Dict, Optional
 
 import numpy as np
 import torch
@@ -34,9 +33,6 @@ import torch
 from ... import _lib
 from ...weights import SwinConfig, make_swin_params, swin_config, swin_param_shapes
 from .features import FeatureOutputs
-from ...images import Uint8Images
-from .vit import (_capture_graph, _check_image_shape, _forward_u8_into, _replay_graph,
-                  _to_device_image)
 
 
 class SwinTransformer(FeatureOutputs):
@@ -70,27 +66,19 @@ class SwinTransformer(FeatureOutputs):
                                  f"{window_size} (window {w}; windows are 7 or 12)")
         self.num_classes = num_classes
         self.num_features = self.cfg.num_features
-        if dtype not in _lib.DTYPE:
-            raise ValueError(f"dtype must be one of {sorted(_lib.DTYPE)}")
-        self.dtype = dtype
-        self.device = torch.device(device) if device is not None else torch.device(
-            "cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
-        _lib.ensure_device(self.device.index or 0)
+        self._open_device(dtype, device)
         params = weights if weights is not None else make_swin_params(self.cfg, seed=seed)
-        self._weights: List[torch.Tensor] = []
         for name, shape in swin_param_shapes(self.cfg):
             a = np.asarray(params[name], dtype=np.float32)
             if tuple(a.shape) != tuple(shape):
                 raise ValueError(f"weight {name}: shape {a.shape}, expected {shape}")
             self._weights.append(torch.from_numpy(np.ascontiguousarray(a)).to(self.device))
-        self._handle: Optional[int] = None
-        self._max_batch = 0
-        # batch lanes (evt_model_set_lanes): None = _lib.default_lanes
-        self._lanes = lanes
-        if max_batch:
-            self._build(max_batch)
+        self._open_handle(lanes, max_batch)
 
-    # -- C ABI plumbing ---------------------------------------------------------------------
+    # -- C ABI plumbing (the handle itself: _handle.py) ----------------------------------------
+    _C_NUM_WEIGHTS, _C_CREATE = "evt_swin_num_weights", "evt_swin_create"
+    _C_FORWARD, _C_QUERY_WORKSPACE = "evt_swin_forward", "evt_swin_query_workspace"
+
     def _desc(self, max_batch: int) -> _lib.evt_swin_desc:
         c = self.cfg
         d = _lib.evt_swin_desc()
@@ -103,82 +91,7 @@ class SwinTransformer(FeatureOutputs):
         d.dtype, d.max_batch = _lib.DTYPE[self.dtype], max_batch
         return d
 
-    def _build(self, max_batch: int) -> None:
-        lib = _lib.load_library()
-        self.close()
-        self._graph_io = None
-        desc = self._desc(max_batch)
-        n = lib.evt_swin_num_weights(ctypes.byref(desc))
-        if n != len(self._weights):
-            raise RuntimeError(f"library expects {n} weights, mirror has {len(self._weights)}")
-        ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in self._weights])
-        out = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(lib.evt_swin_create(ctypes.byref(desc), ptrs, n,
-                                           ctypes.c_void_p(_lib.stream_ptr(self.device)),
-                                           ctypes.byref(out)))
-        self._handle = out.value
-        self._max_batch = max_batch
-        with torch.cuda.device(self.device):
-            self._lane_streams = _lib.set_lanes(
-                self._handle, self._lanes if self._lanes is not None
-                else _lib.default_lanes(self.dtype, max_batch), self.device)
-
-    def lanes(self) -> int:
-        """Batch lanes of the handle (include/evt.h evt_model_set_lanes; 1 = none)."""
-        out = ctypes.c_int()
-        _lib.check(_lib.load_library().evt_model_lanes(ctypes.c_void_p(self._handle),
-                                                       ctypes.byref(out)))
-        return out.value
-
-    def workspace_bytes(self, batch: int) -> int:
-        out = ctypes.c_size_t()
-        _lib.check(_lib.load_library().evt_swin_query_workspace(
-            ctypes.byref(self._desc(batch)), batch, ctypes.byref(out)))
-        return out.value
-
-    def close(self) -> None:
-        if getattr(self, "_handle", None):
-            _lib.load_library().evt_model_destroy(ctypes.c_void_p(self._handle))
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    # -- forward ------------------------------------------------------------------------------
-    def forward_into(self, img: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
-        """Enqueue the forward of a device-resident fp32 NCHW batch (or a device-resident
-        `Uint8Images`, uint8 NHWC) into `logits`."""
-        if isinstance(img, Uint8Images):
-            return _forward_u8_into(self, img, logits)
-        b = img.shape[0]
-        if b > self._max_batch:
-            self._build(b)
-        _lib.check(_lib.load_library().evt_swin_forward(
-            ctypes.c_void_p(self._handle), ctypes.c_void_p(img.data_ptr()), b,
-            ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(_lib.stream_ptr(self.device))))
-        return logits
-
-    def capture_graph(self, img: torch.Tensor, logits: torch.Tensor) -> None:
-        _capture_graph(self, img, logits)
-
-    def replay_graph(self) -> None:
-        _replay_graph(self)
-
-    def __call__(self, img: Union[torch.Tensor, np.ndarray]):
-        x, was_numpy = _to_device_image(img, self.device)
-        c = self.cfg
-        _check_image_shape(x, (c.in_chans, c.image_size, c.image_size),
-                           (c.image_size, c.image_size, c.in_chans))
-        logits = torch.empty((x.shape[0], c.num_classes), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            self.forward_into(x, logits)
-        return logits.cpu().numpy() if was_numpy else logits
-
-    forward = __call__
+    forward = FeatureOutputs.__call__  # the microsoft name
 
     # -- feature outputs (features.py): forward_features = mean over tokens of LN(x) ----------
     def _feature_geometry(self):

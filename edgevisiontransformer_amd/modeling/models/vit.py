@@ -19,13 +19,12 @@ Differences that are deliberate and documented:
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, List, Optional, Sequence, Tuple, Union
+from typing import Dict, Optional
 
 import numpy as np
 import torch
 
 from ... import _lib
-from ...images import Uint8Images
 from .features import FeatureOutputs
 from ...weights import (ViTConfig, make_std_vit_params, make_vit_params, std_vit_param_shapes,
                         vit_config, vit_param_shapes)
@@ -55,75 +54,6 @@ def decode_prune_encoding(prune_encoding: str):
     return prune_setting, num_heads_list, ffn_threshold_list
 
 
-def _to_device_image(img, device):
-    """(device batch, input was numpy). A `Uint8Images` stays one (its bytes moved to the device):
-    the forward then goes through evt_forward_image, which normalises in its first kernel."""
-    if isinstance(img, Uint8Images):
-        return img.to(device), img.is_numpy
-    if isinstance(img, np.ndarray):
-        return torch.from_numpy(np.ascontiguousarray(img, dtype=np.float32)).to(device), True
-    if not isinstance(img, torch.Tensor):
-        raise TypeError("img must be a torch.Tensor or numpy.ndarray")
-    if img.dtype != torch.float32:
-        img = img.float()
-    if img.device != device:
-        img = img.to(device)
-    return img.contiguous(), False
-
-
-def _check_image_shape(x, native_dims, nhwc_dims) -> None:
-    """ValueError unless x is [B, *native_dims] (fp32) or, a Uint8Images, [B, *nhwc_dims]."""
-    u8 = isinstance(x, Uint8Images)
-    want = tuple(nhwc_dims) if u8 else tuple(native_dims)
-    if len(x.shape) != 4 or tuple(x.shape[1:]) != want:
-        raise ValueError(f"expected {'uint8 NHWC ' if u8 else ''}[B, {', '.join(map(str, want))}], "
-                         f"got {tuple(x.shape)}")
-
-
-def _forward_u8_into(model, img: Uint8Images, logits: torch.Tensor) -> torch.Tensor:
-    """`forward_into` of a device-resident Uint8Images (evt_forward_image, logits only: the batch
-    runs over the handle's lanes like the fp32 forward)."""
-    b = img.shape[0]
-    if b > model._max_batch:
-        model._build(b)
-    args, out = img.image_args(), _lib.evt_features_args()
-    out.logits = logits.data_ptr()
-    _lib.check(_lib.load_library().evt_forward_image(
-        ctypes.c_void_p(model._handle), ctypes.byref(args), b, ctypes.byref(out),
-        ctypes.c_void_p(_lib.stream_ptr(model.device))))
-    return logits
-
-
-def _capture_graph(model, img, logits: torch.Tensor) -> None:
-    b = img.shape[0]
-    if b > model._max_batch:
-        model._build(b)
-    lib = _lib.load_library()
-    stream = torch.cuda.Stream(model.device)  # capture needs a non-default stream
-    stream.wait_stream(torch.cuda.current_stream(model.device))
-    with torch.cuda.stream(stream):
-        if isinstance(img, Uint8Images):  # refill img.data in place between replays
-            args = img.image_args()
-            _lib.check(lib.evt_graph_capture_image(ctypes.c_void_p(model._handle),
-                                                   ctypes.byref(args), b,
-                                                   ctypes.c_void_p(logits.data_ptr()),
-                                                   ctypes.c_void_p(stream.cuda_stream)))
-        else:
-            _lib.check(lib.evt_graph_capture(ctypes.c_void_p(model._handle),
-                                             ctypes.c_void_p(img.data_ptr()), b,
-                                             ctypes.c_void_p(logits.data_ptr()),
-                                             ctypes.c_void_p(stream.cuda_stream)))
-    torch.cuda.current_stream(model.device).wait_stream(stream)
-    model._graph_io = (img, logits, b)  # keep the captured buffers alive
-
-
-def _replay_graph(model) -> None:
-    if not getattr(model, "_graph_io", None):
-        raise RuntimeError("no captured graph: call capture_graph(img, logits) first")
-    _lib.check(_lib.load_library().evt_graph_launch(
-        ctypes.c_void_p(model._handle), ctypes.c_void_p(_lib.stream_ptr(model.device))))
-
-
 class ViT(FeatureOutputs):
     """Vision Transformer forward on MI355X (reference `ViT`, vit.py:9-55).
 
@@ -150,14 +80,8 @@ class ViT(FeatureOutputs):
         self.cfg = _cfg
         self.image_size, self.patch_size = image_size, patch_size
         self.num_classes, self.dim, self.depth, self.mlp_dim = num_classes, dim, depth, mlp_dim
-        if dtype not in _lib.DTYPE:
-            raise ValueError(f"dtype must be one of {sorted(_lib.DTYPE)}")
-        self.dtype = dtype
-        self.device = torch.device(device) if device is not None else torch.device(
-            "cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
-        _lib.ensure_device(self.device.index or 0)
+        self._open_device(dtype, device)
         params = weights if weights is not None else self._make_params(self.cfg, seed=seed)
-        self._weights: List[torch.Tensor] = []
         for name, shape in self._param_shapes(self.cfg):
             a = np.asarray(params[name], dtype=np.float32)
             if tuple(a.shape) != tuple(shape):
@@ -166,15 +90,14 @@ class ViT(FeatureOutputs):
                 else:
                     raise ValueError(f"weight {name}: shape {a.shape}, expected {shape}")
             self._weights.append(torch.from_numpy(np.ascontiguousarray(a)).to(self.device))
-        self._handle: Optional[int] = None
-        self._max_batch = 0
         self._arrays = None
-        # batch lanes (evt_model_set_lanes): None = _lib.default_lanes
-        self._lanes = lanes
-        if max_batch:
-            self._build(max_batch)
+        self._open_handle(lanes, max_batch)
 
-    # -- C ABI plumbing ---------------------------------------------------------------------
+    # -- C ABI plumbing (the handle itself: _handle.py) ----------------------------------------
+    _C_NUM_WEIGHTS, _C_CREATE = "evt_vit_num_weights", "evt_vit_create"
+    _C_FORWARD, _C_QUERY_WORKSPACE = "evt_vit_forward", "evt_query_workspace"
+    _DEFAULT_LANES_KW = {"vit": True}
+
     def _desc(self, max_batch: int):
         c = self.cfg
         arr = lambda v: (ctypes.c_int32 * max(1, len(v)))(*v)  # noqa: E731
@@ -184,94 +107,12 @@ class ViT(FeatureOutputs):
                                  c.depth, c.mlp_dim, heads, hd, ffn, _lib.DTYPE[self.dtype],
                                  max_batch, self.SEMANTICS, self.layer_norm_eps)
 
-    def _build(self, max_batch: int) -> None:
-        lib = _lib.load_library()
-        self.close()
-        self._graph_io = None
-        desc = self._desc(max_batch)
-        n = lib.evt_vit_num_weights(ctypes.byref(desc))
-        ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in self._weights])
-        out = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            stream = _lib.stream_ptr(self.device)
-            _lib.check(lib.evt_vit_create(ctypes.byref(desc), ptrs, n, ctypes.c_void_p(stream),
-                                          ctypes.byref(out)))
-        self._handle = out.value
-        self._max_batch = max_batch
-        with torch.cuda.device(self.device):
-            self._lane_streams = _lib.set_lanes(
-                self._handle, self._lanes if self._lanes is not None
-                else _lib.default_lanes(self.dtype, max_batch, vit=True), self.device)
-
-    def lanes(self) -> int:
-        """Batch lanes of the handle (include/evt.h evt_model_set_lanes; 1 = none)."""
-        out = ctypes.c_int()
-        _lib.check(_lib.load_library().evt_model_lanes(ctypes.c_void_p(self._handle),
-                                                       ctypes.byref(out)))
-        return out.value
-
     def qkv_headmajor_layers(self) -> int:
         """Encoder layers whose QKV output was stored head-major in the last forward
         (evt_model_qkv_layout; diagnostics for the layout-equality tests)."""
         out = ctypes.c_int()
-        _lib.check(_lib.load_library().evt_model_qkv_layout(ctypes.c_void_p(self._handle),
-                                                             ctypes.byref(out)))
+        _lib.check(_lib.load_library().evt_model_qkv_layout(self._ptr(), ctypes.byref(out)))
         return out.value
-
-    def workspace_bytes(self, batch: int) -> int:
-        lib = _lib.load_library()
-        out = ctypes.c_size_t()
-        _lib.check(lib.evt_query_workspace(ctypes.byref(self._desc(batch)), batch, ctypes.byref(out)))
-        return out.value
-
-    def close(self) -> None:
-        if self._handle:
-            _lib.load_library().evt_model_destroy(ctypes.c_void_p(self._handle))
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    # -- forward ------------------------------------------------------------------------------
-    def forward_into(self, img: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
-        """Enqueue the forward of a device-resident fp32 NCHW batch (or a device-resident
-        `Uint8Images`, uint8 NHWC) into `logits` (no allocation)."""
-        if isinstance(img, Uint8Images):
-            return _forward_u8_into(self, img, logits)
-        b = img.shape[0]
-        if b > self._max_batch:
-            self._build(b)
-        lib = _lib.load_library()
-        _lib.check(lib.evt_vit_forward(ctypes.c_void_p(self._handle), ctypes.c_void_p(img.data_ptr()),
-                                       b, ctypes.c_void_p(logits.data_ptr()),
-                                       ctypes.c_void_p(_lib.stream_ptr(self.device))))
-        return logits
-
-    # -- HIP graph ----------------------------------------------------------------------------
-    def capture_graph(self, img: torch.Tensor, logits: torch.Tensor) -> None:
-        """Record one forward of the device buffers (img, logits) as a HIP graph
-        (evt_graph_capture); replay_graph() re-runs it after the caller refills img in place."""
-        _capture_graph(self, img, logits)
-
-    def replay_graph(self) -> None:
-        _replay_graph(self)
-
-    def __call__(self, img: Union[torch.Tensor, np.ndarray]):
-        x, was_numpy = _to_device_image(img, self.device)
-        c = self.cfg
-        _check_image_shape(x, (c.in_chans, c.image_size, c.image_size),
-                           (c.image_size, c.image_size, c.in_chans))
-        logits = torch.empty((x.shape[0], c.num_classes), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            self.forward_into(x, logits)
-        # stream-ordered, as every torch op: a numpy input gets numpy logits (.cpu() waits for
-        # them), a device tensor gets device logits without a host sync
-        return logits.cpu().numpy() if was_numpy else logits
-
-    call = __call__
 
     # -- feature outputs (features.py: forward_features, features, features_into) -------------
     _TAP_NORM_OK = False  # no final LayerNorm (vit.py:54); StandardViT has one
