@@ -10,4 +10,5 @@ GPU.
 """
 __version__ = "0.4.0"
 
-from .images import IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD, Uint8Images  # noqa: E402,F401
+from .images import (IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD, EvalTransform,  # noqa: E402,F401
+                     Uint8Images)

@@ -182,6 +182,25 @@ IMAGE_SIGNATURES = {
     "evt_unfold_u8": (_I, [_I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P]),
 }
 
+
+
+class evt_resize_item(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p), ("pitch", ctypes.c_int64), ("plan", ctypes.c_void_p)]
+
+
+# include/evt_preprocess.h constants
+RESIZE_BILINEAR, RESIZE_BICUBIC = 2, 3
+RESIZE_MAX_SIDE, RESIZE_LDS_BYTES, RESIZE_CHUNK = 32768, 65536, 64
+_PI, _PI32 = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int32)
+# the entry points of include/evt_preprocess.h (evt.h includes it; bound like SIGNATURES)
+PREPROCESS_SIGNATURES = {
+    "evt_resize_geometry": (_I, [_I, _I, _I, _I, _I, _PI, _PI, _PI, _PI, _PI, _PI]),
+    "evt_resize_coefficients": (_I, [_I, _I, _I, _I, _I, _PI32, _PI32]),
+    "evt_resize_plan_create": (_I, [_I, _I, _I, _I, _I, _I, ctypes.POINTER(_P)]),
+    "evt_resize_plan_destroy": (_I, [_P]),
+    "evt_resize_crop_u8": (_I, [ctypes.POINTER(evt_resize_item), _I, _I, _I, _P, _P]),
+}
+
 _lib = None
 _lock = threading.Lock()
 _initialized_devices = set()
@@ -202,7 +221,7 @@ def load_library() -> ctypes.CDLL:
             # every one (tests/test_capi.py)
             lenient = "EVT_LIB" in os.environ
             for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **FEATURE_SIGNATURES,
-                                      **IMAGE_SIGNATURES}.items():
+                                      **IMAGE_SIGNATURES, **PREPROCESS_SIGNATURES}.items():
                 if lenient and not hasattr(lib, name):
                     continue
                 fn = getattr(lib, name)

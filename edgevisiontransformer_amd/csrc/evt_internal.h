@@ -328,4 +328,25 @@ hipError_t ln_mx8_launch(const void* x, int rows, int D, int Kpad, const float* 
                          const float* beta, float eps, float* stats, void* q, uint32_t* s,
                          hipStream_t st);
 
+// ---- uint8 resize + centre crop (include/evt_preprocess.h, preprocess.hip) -------------------
+// One image of a launch. tab: the plan's device tables, int32
+//   [S][2] horizontal (xmin, n) | [S][ksh] horizontal kk | [S][2] vertical (ymin, n) | [S][ksv] kk
+// for the S columns / rows of the crop window. The image's workgroups are blk0 .. blk0+ceil(S/tr)-1,
+// each a band of tr output rows.
+struct ResizeDesc {
+  const uint8_t* src;
+  int64_t pitch;
+  const int32_t* tab;
+  int32_t ksh, ksv, tr, blk0;
+};
+constexpr int RESIZE_CHUNK = 64;  // EVT_RESIZE_CHUNK: 16 + 64 * 40 bytes of kernel arguments
+struct ResizeArgs {
+  uint8_t* out;     // image 0 of this launch: dense [n][S][S][C]
+  int32_t S, n;     // crop size, images in d[]
+  ResizeDesc d[RESIZE_CHUNK];
+};
+// blocks: the sum of the images' band counts; lds: the largest band of the launch in bytes
+// (rows * round_up(S*C, 16)), at most 64 KiB
+hipError_t resize_crop_launch(const ResizeArgs& a, int C, int blocks, size_t lds, hipStream_t s);
+
 }  // namespace evt

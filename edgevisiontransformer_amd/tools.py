@@ -13,7 +13,8 @@ Reference conventions kept (so existing `run.sh`-style sweeps and log scrapers w
   * `gpu_benchmark` takes the `server_benchmark` flag set (tools.py:7-67): --model, --num_runs (50),
     --warmup_runs (50), --top (average of the K shortest), --precision (2..6), --input_shape
     (comma list), --io_binding, --dtype (float32, or uint8: seeded random NHWC bytes through
-    `Uint8Images`; --input_shape keeps the family's fp32 meaning), and accepts --use_gpu /
+    `Uint8Images`; --input_shape keeps the family's fp32 meaning; with --raw_shape H,W every timed
+    step first resizes and centre-crops a resident batch of H x W images), and accepts --use_gpu /
     --intra_op_threads as no-ops; latency is `timeit.default_timer` around one call, host-synchronised, and the line is
     printed exactly as tools.py:116 does: "{name}  Avg latency: {ms} ms, Std: {ms} ms.";
   * `test_keras_latency` (tools.py:170-213): --test_times + 1 calls, the first dropped,
@@ -108,16 +109,26 @@ def uint8_shape(name: str, shape: List[int]) -> List[int]:
 
 def latency_samples(model, shape: List[int], num_runs: int, warmup_runs: int,
                     io_binding: bool, seed: int = 0, graph: bool = False,
-                    uint8: bool = False) -> List[float]:
+                    uint8: bool = False, raw_shape: Optional[List[int]] = None) -> List[float]:
     """Seconds per call, `timeit.default_timer` around one host-synchronised forward
     (graph: replay of a captured HIP graph of the device-resident forward). uint8: `shape` is
-    [B, S, S, C] and the input a `Uint8Images` of seeded random bytes (ImageNet mean / std)."""
+    [B, S, S, C] and the input a `Uint8Images` of seeded random bytes (ImageNet mean / std).
+    raw_shape [H, W] (uint8 only): each timed call first transforms a device-resident batch of
+    B random H x W x C images with `EvalTransform(S)` (resize + centre crop) into the forward's
+    input bytes, then runs the forward."""
     import torch
     rng = np.random.default_rng(seed)
+    pre = raw = None
     if uint8:
-        from .images import Uint8Images
+        from .images import EvalTransform, Uint8Images
         host = Uint8Images(rng.integers(0, 256, size=shape, dtype=np.uint8))
         dev = host.to(model.device)
+        if raw_shape is not None:
+            pre = EvalTransform(shape[1])
+            raw = list(torch.from_numpy(rng.integers(
+                0, 256, size=[shape[0], raw_shape[0], raw_shape[1], shape[3]],
+                dtype=np.uint8)).to(model.device))
+            pre.into(raw, dev.data)  # plans are made here, outside the timed calls
     else:
         host = rng.standard_normal(shape, dtype=np.float32)   # tools.py:204 / utils.py:482 style
         dev = torch.from_numpy(host).to(model.device)
@@ -127,11 +138,16 @@ def latency_samples(model, shape: List[int], num_runs: int, warmup_runs: int,
         model.capture_graph(dev, logits)
 
     def run():
+        if pre is not None:  # the same buffer the forward (or its captured graph) reads
+            pre.into(raw, dev.data)
         if graph:
             model.replay_graph()
             torch.cuda.synchronize(model.device)
         elif io_binding:
             model.forward_into(dev, logits)
+            torch.cuda.synchronize(model.device)
+        elif pre is not None:
+            model(dev)
             torch.cuda.synchronize(model.device)
         else:
             model(host)  # numpy in -> numpy out (includes both copies)
@@ -181,6 +197,10 @@ def _server_flags(parser: argparse.ArgumentParser) -> None:
                         help="replay a captured HIP graph of the device-resident forward")
     parser.add_argument("--precision", default=2, choices=[2, 3, 4, 5, 6], type=int)
     parser.add_argument("--input_shape", default=None, type=str, help="input_shape")
+    parser.add_argument("--raw_shape", default=None, type=str,
+                        help="H,W of the decoded images (with --dtype uint8): every timed step "
+                             "resizes and centre-crops a resident batch of them on the device "
+                             "(EvalTransform) and then runs the forward")
 
 
 def parse_server_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
@@ -190,6 +210,13 @@ def parse_server_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     args = parser.parse_args(argv)
     if args.dtype not in INPUT_DTYPES:
         raise ValueError(f"input dtype must be one of {INPUT_DTYPES}")
+    if args.raw_shape is not None:
+        if args.dtype != "uint8":
+            raise ValueError("--raw_shape needs --dtype uint8")
+        hw = [int(v) for v in args.raw_shape.split(",")]
+        if len(hw) != 2 or min(hw) < 1:
+            raise ValueError(f"--raw_shape must be H,W, got {args.raw_shape}")
+        args.raw_shape = hw
     return args
 
 
@@ -200,7 +227,8 @@ def gpu_benchmark(argv: Optional[List[str]] = None) -> str:
                         image_size=_image_size(args.model, shape))
     u8 = args.dtype == "uint8"
     lat = latency_samples(model, uint8_shape(args.model, shape) if u8 else shape, args.num_runs,
-                          args.warmup_runs, args.io_binding, graph=args.graph, uint8=u8)
+                          args.warmup_runs, args.io_binding, graph=args.graph, uint8=u8,
+                          raw_shape=args.raw_shape)
     avg, std = summarize(lat, args.top)
     name = args.model + (f"_{args.prune_encoding}" if args.prune_encoding else "")
     line = format_line(name, avg, std, args.precision)
