@@ -201,6 +201,23 @@ PREPROCESS_SIGNATURES = {
     "evt_resize_crop_u8": (_I, [ctypes.POINTER(evt_resize_item), _I, _I, _I, _P, _P]),
 }
 
+
+class evt_attn_args(ctypes.Structure):
+    _fields_ = [("n_maps", ctypes.c_int32), ("blocks", ctypes.POINTER(ctypes.c_int32)),
+                ("maps", ctypes.POINTER(ctypes.c_void_p)), ("queries", ctypes.c_int32)]
+
+
+# include/evt_attention_maps.h constants
+ATTN_CLS, ATTN_ALL = 0, 1
+# the entry points of include/evt_attention_maps.h (evt.h includes it; bound like SIGNATURES)
+ATTENTION_SIGNATURES = {
+    "evt_attn_map_shape": (_I, [_P, _I, _PI, _PI]),
+    "evt_forward_attention": (_I, [_P, ctypes.POINTER(evt_image_args), _I,
+                                   ctypes.POINTER(evt_features_args),
+                                   ctypes.POINTER(evt_attn_args), _P]),
+    "evt_attention_probs": (_I, [_I, _P, _I64, _I64, _I64, _I, _I, _I, _I, _I, _F, _I, _P, _P]),
+}
+
 _lib = None
 _lock = threading.Lock()
 _initialized_devices = set()
@@ -221,7 +238,8 @@ def load_library() -> ctypes.CDLL:
             # every one (tests/test_capi.py)
             lenient = "EVT_LIB" in os.environ
             for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **FEATURE_SIGNATURES,
-                                      **IMAGE_SIGNATURES, **PREPROCESS_SIGNATURES}.items():
+                                      **IMAGE_SIGNATURES, **PREPROCESS_SIGNATURES,
+                                      **ATTENTION_SIGNATURES}.items():
                 if lenient and not hasattr(lib, name):
                     continue
                 fn = getattr(lib, name)

@@ -18,12 +18,13 @@ LAB = os.environ.get("EVT_LAB", "") not in ("", "0")
 LIB = os.path.join(HERE, "libevt_hip_lab.so" if LAB else "libevt_hip.so")
 OBJ = os.path.join(HERE, "build_obj_lab" if LAB else "build_obj")
 SOURCES = ["gemm.hip", "attention.hip", "norm.hip", "t2t.hip", "swin.hip", "mx8.hip",
-           "features.hip", "preprocess.hip", "capi.cpp"]
+           "features.hip", "preprocess.hip", "attn_maps.hip", "capi.cpp"]
 HEADERS = ["common.h", "evt_internal.h", os.path.join("..", "..", "include", "evt.h"),
            os.path.join("..", "..", "include", "evt_patchify.h"),
            os.path.join("..", "..", "include", "evt_features.h"),
            os.path.join("..", "..", "include", "evt_image.h"),
-           os.path.join("..", "..", "include", "evt_preprocess.h")]
+           os.path.join("..", "..", "include", "evt_preprocess.h"),
+           os.path.join("..", "..", "include", "evt_attention_maps.h")]
 ARCH = os.environ.get("EVT_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result",
          "-ffp-contract=on"]  # contraction only within one source expression: same result on
@@ -38,7 +39,7 @@ if LAB:
 # attention / window-attention / performer accumulators in AGPRs and copies every element back
 # (v_accvgpr_read) before the softmax / GELU VALU work (96 copies per window-attention wave).
 PER_FILE_FLAGS = {s: ["-mllvm", "-amdgpu-mfma-vgpr-form=true"]
-                  for s in ("attention.hip", "swin.hip", "t2t.hip")}
+                  for s in ("attention.hip", "swin.hip", "t2t.hip", "attn_maps.hip")}
 # attention.hip: no NaN operands either (scores of finite bf16 / fp32 q, k; masked keys are -inf):
 # the softmax max runs on the raw MFMA results without a canonicalising v_max per element
 PER_FILE_FLAGS["attention.hip"] = PER_FILE_FLAGS["attention.hip"] + ["-fno-honor-nans"]

@@ -225,6 +225,8 @@ struct ForwardCall {
   float* logits = nullptr;        // may be null in a features forward (no head then)
   const evt_features_args* feat = nullptr;  // evt_forward_features outputs (null: plain forward)
   int feat_next = 0;              // the next entry of feat's tap list
+  const evt_attn_args* attn = nullptr;  // evt_forward_attention maps (null: none)
+  int attn_next = 0;              // the next entry of attn's block list
   hipStream_t s = nullptr;
   // images [b0, b1) of a logits-only call, on stream `lane`: the input advances by whole images
   // (4 bytes per element of an fp32 batch, 1 of a uint8 one), the logits by rows
@@ -546,6 +548,21 @@ int feat_tap(evt_model* m, ForwardCall& call, int block, int64_t ldx, int rows, 
                      call.s);
 }
 
+// Right after block `block`'s attention kernel of an evt_forward_attention call, while ws.qkv still
+// holds the block's q and k in the layout `ap` describes: the block's map, if one was asked for
+// (attn_maps.hip; counted under EVT_PROF_HEAD like the feature exports)
+int attn_map(evt_model* m, ForwardCall& call, int block, const AttnParams& ap) {
+  const evt_attn_args* a = call.attn;
+  if (!a || call.attn_next >= a->n_maps || a->blocks[call.attn_next] != block) return EVT_OK;
+  const int nq = a->queries == EVT_ATTN_ALL ? ap.N : 1;
+  ProfScope ps(m, EVT_PROF_HEAD, call.s);
+  const double bh = (double)ap.B * ap.H;
+  prof_work(m, 4.0 * bh * nq * (double)ap.N * ap.hd,  // the scores, twice
+            bh * ((double)(nq + ap.N) * ap.hd * elem_size(m->dtype) + (double)nq * ap.N * 4.0));
+  EVT_HIP(attn_probs_launch(m->dtype, ap, nq, a->maps[call.attn_next++], call.s), "attention map");
+  return EVT_OK;
+}
+
 // Encoder weights (11 tensors per layer, 12 with the STANDARD qkv bias; evt_vit_num_weights
 // order) for m->heads / m->ffn.
 int build_encoder(evt_model* m, const float* const* w, hipStream_t s) {
@@ -668,21 +685,22 @@ int run_encoder(evt_model* m, ForwardCall& call) {
       }
       EVT_RC(dense(m, L.qkv, c, s));
     }
+    AttnParams ap{m->ws.qkv, 3 * L.inner, m->ws.o, L.inner, T, L.heads, B, scale_log2};
+    ap.hd = L.hd;
+    if (hm) {
+      ap.ldq = 64;
+      ap.sb = (int64_t)L.heads * 3 * T * 64;
+      ap.sh = (int64_t)3 * T * 64;
+      ap.ko = T * 64;
+      ap.vo = 2 * T * 64;
+    }
     {
       ProfScope ps(m, EVT_PROF_ATTENTION, s);
       prof_work(m, 4.0 * B * L.heads * (double)T * T * L.hd,
                 (double)rows * 4 * L.inner * elem_size(m->dtype));  // qkv read + O written
-      AttnParams ap{m->ws.qkv, 3 * L.inner, m->ws.o, L.inner, T, L.heads, B, scale_log2};
-      ap.hd = L.hd;
-      if (hm) {
-        ap.ldq = 64;
-        ap.sb = (int64_t)L.heads * 3 * T * 64;
-        ap.sh = (int64_t)3 * T * 64;
-        ap.ko = T * 64;
-        ap.vo = 2 * T * 64;
-      }
       EVT_HIP(attention_launch(m->dtype, ap, s), "attention");
     }
+    EVT_RC(attn_map(m, call, block, ap));
     // out-proj + bias + LN1(x) residual -> xm (+ stats); STANDARD: + x
     DenseCall co;
     co.flags = m->standard ? (EPI_BIAS | EPI_RESID | EPI_STATS)
@@ -2429,6 +2447,89 @@ int evt_graph_capture_image(evt_model* m, const evt_image_args* in, int B, float
   EVT_RC(check_batch(m, B));  // ahead of the capture's own checks, and of the previous graph's end
   ForwardCall call = image_call(in, aff, B, logits, stream);
   return graph_capture(m, stream, [&]() { return forward(m, call, true); });
+}
+
+// ---- attention-map outputs (include/evt_attention_maps.h) -----------------------------------
+
+static int attn_family(const evt_model* m) {
+  if (m->family == 2)
+    return fail(EVT_EINVAL, "attention maps: Swin's windowed, biased attention is not exported");
+  if (m->mx8) return fail(EVT_EINVAL, "attention maps are not available on an EVT_DTYPE_MX8 model");
+  return EVT_OK;
+}
+
+int evt_attn_map_shape(const evt_model* m, int block, int* heads, int* tokens) {
+  if (!m || !heads || !tokens) return fail(EVT_EINVAL, "null argument");
+  EVT_RC(attn_family(m));
+  if (block < 0 || block >= (int)m->layers.size())
+    return fail(EVT_EINVAL, "block must be in [0, " + std::to_string(m->layers.size()) + ")");
+  *heads = m->layers[block].heads;
+  *tokens = m->sh.T;
+  return EVT_OK;
+}
+
+int evt_forward_attention(evt_model* m, const evt_image_args* in, int B,
+                          const evt_features_args* feat, const evt_attn_args* a, void* stream) {
+  ImgAffine aff{};
+  if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and attn must be non-null");
+  EVT_RC(validate_image(m, in, &aff));
+  EVT_RC(attn_family(m));
+  if (a->n_maps < 0 || a->n_maps > 64) return fail(EVT_EINVAL, "n_maps must be in [0, 64]");
+  if (a->n_maps == 0 && !feat)
+    return fail(EVT_EINVAL, "no output requested: n_maps is 0 and feat is NULL");
+  if (feat) EVT_RC(validate_features(m, feat, B));
+  else EVT_RC(check_batch(m, B));
+  if (a->queries != EVT_ATTN_CLS && a->queries != EVT_ATTN_ALL)
+    return fail(EVT_EINVAL, "queries must be EVT_ATTN_CLS or EVT_ATTN_ALL");
+  if (a->n_maps > 0) {
+    if (!a->blocks || !a->maps) return fail(EVT_EINVAL, "n_maps > 0 needs the blocks and maps arrays");
+    const int nb = (int)m->layers.size();
+    for (int i = 0; i < a->n_maps; ++i) {
+      if (a->blocks[i] < 0 || a->blocks[i] >= nb)
+        return fail(EVT_EINVAL, "map block " + std::to_string(a->blocks[i]) + " is outside [0, " +
+                                    std::to_string(nb) + ")");
+      if (i > 0 && a->blocks[i] <= a->blocks[i - 1])
+        return fail(EVT_EINVAL, "map blocks must be strictly increasing");
+      if (!a->maps[i]) return fail(EVT_EINVAL, "map pointer " + std::to_string(i) + " is NULL");
+      if ((uintptr_t)a->maps[i] & 15) return fail(EVT_EINVAL, "attention maps must be 16-byte aligned");
+    }
+  }
+  ForwardCall call = image_call(in, aff, B, feat ? feat->logits : nullptr, stream);
+  call.feat = feat;
+  call.attn = a;
+  // one lane, on this handle's own workspace, whatever its lane count (as a features forward)
+  return forward(m, call, false);
+}
+
+int evt_attention_probs(int dtype, const void* qkv, int64_t ldq, int64_t sb, int64_t sh, int ko,
+                        int B, int N, int H, int head_dim, float scale, int nq, float* out,
+                        void* stream) {
+  if (dtype != EVT_DTYPE_F32 && dtype != EVT_DTYPE_BF16)
+    return fail(EVT_EINVAL, "attention_probs: dtype must be EVT_DTYPE_F32 or EVT_DTYPE_BF16");
+  if (!qkv || !out || B < 0 || N <= 0 || N > EVT_ATTN_MAX_TOKENS || H <= 0 || head_dim <= 0 ||
+      head_dim > 128)
+    return fail(EVT_EINVAL, "attention_probs: bad shape (N <= 4096, head size in [1, 128])");
+  if (nq != 1 && nq != N) return fail(EVT_EINVAL, "attention_probs: nq must be 1 or N");
+  if (!(scale > 0.f && scale < INFINITY))
+    return fail(EVT_EINVAL, "attention_probs: the scale must be positive and finite");
+  if ((uintptr_t)out & 15) return fail(EVT_EINVAL, "attention_probs: out must be 16-byte aligned");
+  const int64_t vec = dtype == DT_BF16 ? 8 : 4;
+  if (sb || sh || ko) {
+    if (dtype != DT_BF16 || head_dim != 64 || sb < 0 || sh < 0 || ko < 0 || sb % 8 || sh % 8 ||
+        ko % 8 || ldq % 8 || ldq < 64 || ((uintptr_t)qkv & 15))
+      return fail(EVT_EINVAL, "attention_probs: a slice layout needs bf16, head size 64 and "
+                              "non-negative strides that are multiples of 8");
+  } else {
+    if (ldq < 3 * (int64_t)H * head_dim)
+      return fail(EVT_EINVAL, "attention_probs: ldq must be at least 3*H*head_dim");
+    if (head_dim % vec == 0 && (ldq % vec || ((uintptr_t)qkv & 15)))
+      return fail(EVT_EINVAL, "attention_probs: qkv rows must be 16-B aligned for this head size");
+  }
+  AttnParams p{qkv, ldq, nullptr, 0, N, H, B, scale * 1.4426950408889634f};
+  p.hd = head_dim;
+  p.sb = sb; p.sh = sh; p.ko = ko;
+  EVT_HIP(attn_probs_launch(dtype, p, nq, out, (hipStream_t)stream), "attention_probs");
+  return EVT_OK;
 }
 
 int evt_patchify_u8(int dtype, const uint8_t* img, int B, int C, int HW, int ps, void* out,

@@ -151,6 +151,8 @@ __device__ __forceinline__ void store4_nt(bf16* p, f32x4 v) {
   const bf16x4 o = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
   __builtin_nontemporal_store(o, (bf16x4*)p);
 }
+// one float, non-temporal (the unaligned edges of the attention-map rows, attn_maps.hip)
+__device__ __forceinline__ void store1_nt(float* p, float v) { __builtin_nontemporal_store(v, p); }
 
 // tanh-approximate GELU in fp32 (reference modeling/layers/activation.py:13-15), evaluated as
 // x * 0.5 * (1 + tanh(u)) == x * sigmoid(2u) = x / (1 + 2^(-2u*log2 e)): one v_exp_f32 and one

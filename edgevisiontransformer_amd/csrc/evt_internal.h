@@ -126,7 +126,11 @@ struct AttnParams {
   int ko = 0, vo = 0;
 };
 hipError_t attention_launch(int dtype, const AttnParams& p, hipStream_t s);
-
+// Attention-map export (attn_maps.hip): out[b][h][i][j] = softmax_j(q_i . k_j scale) as fp32,
+// contiguous [B][H][nq][N], nq = 1 (the row of query 0) or N; p as attention_launch (out, ldo, vo
+// and the MX8 fields unused; sb / sh / ko: bf16 h_k = 64 only). scale_log2 positive and finite,
+// out 16-byte aligned (hipErrorInvalidValue otherwise).
+hipError_t attn_probs_launch(int dtype, const AttnParams& p, int nq, float* out, hipStream_t s);
 
 
 // LayerNorm over rows of D (fp32 in) -> activation dtype out (eps 1e-5).

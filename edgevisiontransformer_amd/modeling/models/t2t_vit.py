@@ -24,10 +24,10 @@ import torch
 
 from ... import _lib
 from ...weights import T2TConfig, make_t2t_params, t2t_config, t2t_param_shapes
-from .features import FeatureOutputs
+from .attention_maps import AttentionMaps
 
 
-class T2T_ViT(FeatureOutputs):
+class T2T_ViT(AttentionMaps):
     """Tokens-to-Token ViT forward on MI355X (reference `T2T_ViT`, t2t_vit.py:91-135).
     `image_size`: a multiple of 16 with (image_size / 16)^2 + 1 <= 4096 tokens."""
 
@@ -76,6 +76,11 @@ class T2T_ViT(FeatureOutputs):
     def _image_dims(self):
         c = self.cfg
         return c.image_size, c.image_size, c.in_chans
+
+    # -- attention maps (attention_maps.py): the encoder blocks, not the token performers -------
+    def _attn_geometry(self):
+        c = self.cfg
+        return [(c.heads, c.tokens)] * c.depth
 
 
 def get_t2t_vit_7(**kw) -> T2T_ViT:

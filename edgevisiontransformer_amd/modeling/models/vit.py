@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from ... import _lib
-from .features import FeatureOutputs
+from .attention_maps import AttentionMaps
 from ...weights import (ViTConfig, make_std_vit_params, make_vit_params, std_vit_param_shapes,
                         vit_config, vit_param_shapes)
 
@@ -54,7 +54,7 @@ def decode_prune_encoding(prune_encoding: str):
     return prune_setting, num_heads_list, ffn_threshold_list
 
 
-class ViT(FeatureOutputs):
+class ViT(AttentionMaps):
     """Vision Transformer forward on MI355X (reference `ViT`, vit.py:9-55).
 
     `image_size` / `patch_size`: any pair with (image_size / patch_size)^2 + 1 <= 4096 tokens per
@@ -124,6 +124,11 @@ class ViT(FeatureOutputs):
     def _image_dims(self):
         c = self.cfg
         return c.in_chans, c.image_size, c.image_size
+
+    # -- attention maps (attention_maps.py): a pruned model's heads differ per block ------------
+    def _attn_geometry(self):
+        c = self.cfg
+        return [(int(h), c.tokens) for h in list(c.heads)[:c.depth]]
 
 
 class ViT_Pruned(ViT):
