@@ -218,6 +218,11 @@ ATTENTION_SIGNATURES = {
     "evt_attention_probs": (_I, [_I, _P, _I64, _I64, _I64, _I, _I, _I, _I, _I, _F, _I, _P, _P]),
 }
 
+# the entry point of include/evt_tail.h (evt.h includes it; bound like SIGNATURES)
+TAIL_SIGNATURES = {
+    "evt_model_tail_mode": (_I, [_P, _PI]),
+}
+
 _lib = None
 _lock = threading.Lock()
 _initialized_devices = set()
@@ -239,7 +244,7 @@ def load_library() -> ctypes.CDLL:
             lenient = "EVT_LIB" in os.environ
             for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **FEATURE_SIGNATURES,
                                       **IMAGE_SIGNATURES, **PREPROCESS_SIGNATURES,
-                                      **ATTENTION_SIGNATURES}.items():
+                                      **ATTENTION_SIGNATURES, **TAIL_SIGNATURES}.items():
                 if lenient and not hasattr(lib, name):
                     continue
                 fn = getattr(lib, name)

@@ -229,7 +229,7 @@ __device__ __forceinline__ void attn_tile_bf16(const AttnParams& p, const EVT_LD
 
 // Stage one (image, head)'s K and V rows (NP rows, clamped past N) into LDS with glds, WAVES
 // waves sharing the rows, and load the Q fragments of query tiles wave, wave + WAVES, ...
-template <int NKT, int WAVES, int NQW, bool NT = false, bool NTQ = NT>
+template <int NKT, int WAVES, int NQW, bool NT = false, bool NTQ = NT, bool Q0 = false>
 __device__ __forceinline__ void attn_stage_bf16(const AttnParams& p, EVT_LDS char* Ks,
                                                 EVT_LDS char* Vs, u32x4 (&qf)[NQW][2], int b,
                                                 int h, int wave, int lane) {
@@ -238,6 +238,7 @@ __device__ __forceinline__ void attn_stage_bf16(const AttnParams& p, EVT_LDS cha
   const int g = lane >> 4, c16 = lane & 15;
 #pragma unroll
   for (int i = 0; i < NQW; ++i) {
+    if (Q0 && wave != 0) break;  // query tile 0 only (wave 0's): the others stage K / V alone
     const int qi = min((wave + WAVES * i) * 16 + c16, p.N - 1);
     const bf16* qrow = qkv + (int64_t)qi * p.ldq;
     if (NTQ) {
@@ -264,11 +265,14 @@ __device__ __forceinline__ void attn_stage_bf16(const AttnParams& p, EVT_LDS cha
 }
 
 // One workgroup (4 waves) per (image, head); 3 per CU (53 KiB of LDS each).
-template <int NKT, int NTM = 0>  // 16-key tiles (keys padded to NKT*16; odd NKT: a half last PV step)
+// CLS (AttnParams::cls_only, the last block of a logits-only forward): K and V staged by all four
+// waves as ever, then query tile 0 alone, by wave 0 and the same attn_tile_bf16 (its rows are
+// bitwise the full launch's); the launch is then bound by the K / V read
+template <int NKT, int NTM = 0, bool CLS = false>  // 16-key tiles (keys padded to NKT*16; odd NKT: a half last PV step)
 __global__ __launch_bounds__(256, (NKT == 13 || NKT == 12) ? 3 : 1) void attn_bf16_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NP = NKT * 16, ROWB = 128;
-  constexpr int NQW = (NP / 16 + 3) / 4;
+  constexpr int NQW = CLS ? 1 : (NP / 16 + 3) / 4;
   EVT_LDS char* Ks = (EVT_LDS char*)smem;
   EVT_LDS char* Vs = Ks + NP * ROWB;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -277,10 +281,11 @@ __global__ __launch_bounds__(256, (NKT == 13 || NKT == 12) ? 3 : 1) void attn_bf
   u32x4 qf[NQW][2];
   // NTM: cache policy of the qkv loads / O stores, non-temporal for 1 all, 2 K/V loads only, 3 O
   // stores only, 4 K/V + Q loads only, 5 K/V loads + O stores (the launched form)
-  attn_stage_bf16<NKT, 4, NQW, (NTM == 1 || NTM == 2 || NTM == 4 || NTM == 5), (NTM == 1 || NTM == 4)>(
+  attn_stage_bf16<NKT, 4, NQW, (NTM == 1 || NTM == 2 || NTM == 4 || NTM == 5), (NTM == 1 || NTM == 4), CLS>(
       p, Ks, Vs, qf, b, h, wave, lane);
   wait_vmcnt0();
   __syncthreads();
+  if (CLS && wave != 0) return;
 #pragma unroll
   for (int it = 0; it < NQW; ++it) {
     const int qt = wave + 4 * it;
@@ -667,7 +672,9 @@ hipError_t launch_nkt(int dtype, const AttnParams& p, hipStream_t s) {
   // K / V loads and O stores non-temporal (NTM 5): measured in the model, out-proj (whose A is O
   // and whose residual x was read by the QKV GEMM just before) 161 -> 157 us and attention equal
   // or 2 us faster; all-NT (Q too) made attention 4 us slower (scripts/gpu_attnnt.sh)
-  if (dtype == DT_BF16)
+  if (dtype == DT_BF16 && p.cls_only)
+    hipLaunchKernelGGL((attn_bf16_kernel<NKT, 5, true>), dim3(p.B * p.H), dim3(256), lds, s, p);
+  else if (dtype == DT_BF16)
     hipLaunchKernelGGL((attn_bf16_kernel<NKT, 5>), dim3(p.B * p.H), dim3(256), lds, s, p);
   else if constexpr (NKT % 2 == 0)
     hipLaunchKernelGGL(attn_f32_kernel<NKT>, dim3(p.B * p.H), dim3(64 * ATTN_F32_WAVES), lds, s, p);
@@ -1120,8 +1127,13 @@ void set_lds_attrs() {
 
 }  // namespace
 
+bool attention_cls_ok(int dtype, const AttnParams& p) {
+  return dtype == DT_BF16 && p.hd == 64 && p.N <= 256 && !p.q8;
+}
+
 hipError_t attention_launch(int dtype, const AttnParams& p_in, hipStream_t s) {
   if (p_in.B <= 0) return hipSuccess;
+  if (p_in.cls_only && !attention_cls_ok(dtype, p_in)) return hipErrorInvalidValue;
   if (p_in.N <= 0 || p_in.N > EVT_ATTN_MAX_TOKENS || p_in.H <= 0 || p_in.hd <= 0 || p_in.hd > 128)
     return hipErrorInvalidValue;
   if (p_in.N > 256 && p_in.q8) return hipErrorInvalidValue;  // MX8 output: the one-pass kernels only

@@ -174,6 +174,7 @@ struct Workspace {
   void* o = nullptr;         // [B*T, inner]
   void* hbuf = nullptr;      // [B*T, ffn_st]
   size_t hbuf_bytes = 0;
+  void* hc = nullptr;        // [B, max ffn_st] FFN hidden rows of the CLS tail (run_encoder)
   void* hh = nullptr;        // [B, head_st]
   void* sk = nullptr;        // stream-K scratch of the model's GEMMs (gemm_sk_bytes)
   void* pooled = nullptr;    // Swin: [B, Cst_last] LayerNorm + token mean (head A operand)
@@ -191,6 +192,7 @@ struct evt_model : ModelCore {  // a handle: the core, its own workspace, its ow
   int max_batch = 0;
   std::vector<void*> allocs;         // every device allocation this handle owns (weights, ws)
   int hm_layers = 0;         // encoder layers whose QKV stored head-major in the last forward
+  int tail_mode = 0;         // last forward's last encoder block: bit 0 CLS tail, bit 1 full rows
   hipGraph_t graph = nullptr;        // evt_graph_capture
   hipGraphExec_t graph_exec = nullptr;
   // evt_model_profile: HIP events around every launch of the last forward, by role
@@ -216,7 +218,8 @@ struct evt_model : ModelCore {  // a handle: the core, its own workspace, its ow
 namespace {
 
 // The arguments of one forward. The entry points build one and the run functions read it; nothing
-// of a call is kept on the handle (hm_layers, which evt_model_qkv_layout reads later, aside).
+// of a call is kept on the handle (hm_layers and tail_mode, which evt_model_qkv_layout and
+// evt_model_tail_mode read later, aside).
 struct ForwardCall {
   const float* img = nullptr;     // the fp32 batch, or null with
   const uint8_t* img8 = nullptr;  // a uint8 NHWC batch (evt_forward_image) and
@@ -440,7 +443,8 @@ size_t workspace_bytes(const evt_vit_desc* d, const Shape& sh, int B) {
   }
   return 2 * rows * sh.D * es + 2 * rows * stats_slots(sh.D) * 2 * sizeof(float) +
          rows * 3 * sh.max_inner * es +
-         rows * sh.max_inner * es + hb + (size_t)B * sh.head_st * es + 9 * 256 + extra;
+         rows * sh.max_inner * es + hb + (size_t)B * sh.max_ffn_st * es +  // hc (the CLS tail)
+         (size_t)B * sh.head_st * es + 10 * 256 + extra;
 }
 
 struct DenseCall {
@@ -463,15 +467,20 @@ struct DenseCall {
   int ln_width = 0;    // LayerNorm width of stats_in / rstats / stats_out (0: the model width D)
   int stats_step = 1;  // EPI_LNIN: A row m reads stats_in row m * stats_step
   int slot_width = 0;  // width whose stats_slots() numbers the slots (0: ln_width)
+  // the encoder's CLS tail (run_encoder): its M = B launches
+  int rs_step = 1;     // EPI_RESLN / EPI_STATS: row m's rstats / stats_out rows are m * rs_step
+  bool force_nt = false;  // the 128x128 kernel whatever M is (the same bits at every batch)
+  int work_M = 0;      // rows evt_model_profile_work counts (0: M, < 0: none), dense_work
 };
 
 // Algorithmic work of one Dense launch: 2 M K N with the layer's real K and N; bytes = A and W
 // read once, C written once, plus the residual, the row statistics read / written and the small
-// bias / position vectors (what the kernel cannot avoid moving).
+// bias / position vectors (what the kernel cannot avoid moving). A CLS-tail launch (work_M) counts
+// the layer's model work, all B T rows, once per role: the reference's count, whatever rows ran.
 void dense_work(const evt_model* m, const DenseW& w, const DenseCall& c) {
-  if (!m->prof) return;
+  if (!m->prof || c.work_M < 0) return;
   const double es = (double)elem_size(m->dtype);
-  const double M = c.M, K = w.K, N = std::min(c.N, w.N);
+  const double M = c.work_M ? c.work_M : c.M, K = w.K, N = std::min(c.N, w.N);
   const int width = c.ln_width ? c.ln_width : m->D;
   const double slot_row = (double)stats_slots(c.slot_width ? c.slot_width : width) * 8.0;
   double bytes = M * K * es + K * N * es + M * N * ((c.flags & EPI_OUT_F32) ? 4.0 : es) + 8.0 * N;
@@ -517,6 +526,8 @@ GemmParams dense_params(const evt_model* m, const DenseW& w, const DenseCall& c)
   p.eps = m->eps;  // Keras LayerNormalization(epsilon=1e-5), reference norm.py:6
   p.nslots = stats_slots(c.slot_width ? c.slot_width : width);
   p.stats_step = c.stats_step;
+  p.rs_step = c.rs_step;
+  p.force_nt = c.force_nt;
   gemm_sk_bind(m->ws.sk, p);
   return p;
 }
@@ -629,6 +640,8 @@ int alloc_encoder_ws(evt_model* m, int B, size_t hbuf_bytes, hipStream_t s) {
   EVT_HIP(hipMemsetAsync(m->ws.o, 0, ob, s), "memset o");
   EVT_RC(dev_alloc(m, &m->ws.hbuf, hbuf_bytes));
   m->ws.hbuf_bytes = hbuf_bytes;
+  // the CLS tail's FFN hidden rows (FC1 writes all ffn_st columns of a row before FC2 reads them)
+  if (!m->mx8) EVT_RC(dev_alloc(m, &m->ws.hc, (size_t)B * m->sh.max_ffn_st * es));
   return EVT_OK;
 }
 
@@ -659,6 +672,7 @@ int run_encoder(evt_model* m, ForwardCall& call) {
   hipStream_t s = call.s;
   const float log2e = 1.4426950408889634f;
   m->hm_layers = 0;
+  m->tail_mode = 0;
   int block = 0;
   for (const Layer& L : m->layers) {
     const float scale_log2 = log2e / std::sqrt((float)L.hd);  // h_k^-0.5 (attention.py:13)
@@ -694,11 +708,25 @@ int run_encoder(evt_model* m, ForwardCall& call) {
       ap.ko = T * 64;
       ap.vo = 2 * T * 64;
     }
+    // The classifier and `pooled` read token 0 of the last block and nothing else, so its
+    // out-proj, FC1 and FC2 run on the B CLS rows (the CLS tail, below) and its attention on query
+    // tile 0. A call that exports the last block's token map (tokens, or a tap on it) runs the
+    // full-row block as well; the CLS rows it exports, and the head reads, are still the tail's.
+    const bool last = block + 1 == (int)m->layers.size();
+    bool full = !last;
+    if (last && call.feat) {
+      const evt_features_args* a = call.feat;
+      full = a->tokens || (a->n_taps > 0 && a->tap_blocks[a->n_taps - 1] == block);
+    }
+    if (last) m->tail_mode = full ? 3 : 1;
     {
       ProfScope ps(m, EVT_PROF_ATTENTION, s);
       prof_work(m, 4.0 * B * L.heads * (double)T * T * L.hd,
                 (double)rows * 4 * L.inner * elem_size(m->dtype));  // qkv read + O written
-      EVT_HIP(attention_launch(m->dtype, ap, s), "attention");
+      // (the model's work also where only query tile 0 runs: evt_model_profile_work)
+      AttnParams aq = ap;
+      aq.cls_only = !full && attention_cls_ok(m->dtype, ap);
+      EVT_HIP(attention_launch(m->dtype, aq, s), "attention");
     }
     EVT_RC(attn_map(m, call, block, ap));
     // out-proj + bias + LN1(x) residual -> xm (+ stats); STANDARD: + x
@@ -713,23 +741,45 @@ int run_encoder(evt_model* m, ForwardCall& call) {
     c1.flags = EPI_LNIN | EPI_BIAS | (m->standard ? EPI_GELU_ERF : EPI_GELU);
     c1.A = m->ws.xm; c1.lda = D; c1.C = m->ws.hbuf; c1.ldc = L.ffn_st; c1.M = rows; c1.N = L.ffn_st;
     c1.stats_in = m->ws.sm;
+    // FC2 + bias + LN2(xm) residual -> x (+ stats); STANDARD: + xm
+    DenseCall c2;
+    c2.flags = co.flags;
+    c2.A = m->ws.hbuf; c2.lda = L.ffn_st; c2.C = m->ws.x; c2.ldc = D; c2.M = rows; c2.N = D;
+    c2.resid = m->ws.xm; c2.ldr = D; c2.rstats = m->ws.sm; c2.rgamma = L.ln2_g; c2.rbeta = L.ln2_b;
+    c2.stats_out = m->ws.sx;
+    // The CLS tail's form of a launch: row b is row b T of the stream and statistics buffers, in
+    // place (the head, and `pooled`, read them where they always did), the FFN hidden rows compact
+    // in ws.hc, and the 128x128 kernel whatever B is (one image alone = the image in a batch). It
+    // counts the layer's model work, or nothing where the full-row launch of the role did.
+    auto tail = [&](DenseCall c) {
+      c.M = B;
+      if (c.A == m->ws.hbuf) c.A = m->ws.hc;
+      else c.lda *= T;
+      if (c.C == m->ws.hbuf) c.C = m->ws.hc;
+      else c.ldc *= T;
+      c.ldr *= T;
+      c.stats_step = c.rs_step = T;
+      c.force_nt = true;
+      c.work_M = full ? -1 : rows;
+      return c;
+    };
+    // Each full-row launch comes before its role's tail launch: the tail's out-proj still finds
+    // the block's input rows in x / sx, and what it, FC1 and FC2 leave in rows b T of xm / sm,
+    // hc and x / sx is what the next tail launch, the exports and the head read.
     {
       ProfScope ps(m, EVT_PROF_OUT_PROJ, s);
-      EVT_RC(dense(m, L.out, co, s));
+      if (full) EVT_RC(dense(m, L.out, co, s));
+      if (last) EVT_RC(dense(m, L.out, tail(co), s));
     }
     {
       ProfScope ps(m, EVT_PROF_FC1, s);
-      EVT_RC(dense(m, L.fc1, c1, s));
+      if (full) EVT_RC(dense(m, L.fc1, c1, s));
+      if (last) EVT_RC(dense(m, L.fc1, tail(c1), s));
     }
-    {  // FC2 + bias + LN2(xm) residual -> x (+ stats); STANDARD: + xm
+    {
       ProfScope ps(m, EVT_PROF_FC2, s);
-      DenseCall c;
-      c.flags = m->standard ? (EPI_BIAS | EPI_RESID | EPI_STATS)
-                            : (EPI_BIAS | EPI_RESID | EPI_RESLN | EPI_STATS);
-      c.A = m->ws.hbuf; c.lda = L.ffn_st; c.C = m->ws.x; c.ldc = D; c.M = rows; c.N = D;
-      c.resid = m->ws.xm; c.ldr = D; c.rstats = m->ws.sm; c.rgamma = L.ln2_g; c.rbeta = L.ln2_b;
-      c.stats_out = m->ws.sx;
-      EVT_RC(dense(m, L.fc2, c, s));
+      if (full) EVT_RC(dense(m, L.fc2, c2, s));
+      if (last) EVT_RC(dense(m, L.fc2, tail(c2), s));
     }
     EVT_RC(feat_tap(m, call, block++, D, rows, D));
   }
@@ -853,7 +903,8 @@ size_t t2t_workspace_bytes(const evt_t2t_desc* d, const T2TShape& ts, int B) {
   return t2t_unfold_elems(ts, B) * es + t2t_unfold_stat_floats(ts, B) * 4 + t1 * 4 * 64 * es +
          performer_part_floats(B, ts.grid[0] * ts.grid[0]) * 4 + 2 * rows * d->dim * es +
          2 * rows * stats_slots(d->dim) * 2 * 4 + rows * 4 * ts.enc.max_inner * es +
-         rows * ts.enc.max_ffn_st * es + t1 * 2 * 4 + 256;
+         rows * ts.enc.max_ffn_st * es + (size_t)B * ts.enc.max_ffn_st * es +  // hbuf, hc
+         t1 * 2 * 4 + 2 * 256;
 }
 
 // ---- Swin geometry ------------------------------------------------------------------------
@@ -1063,6 +1114,7 @@ static int lanes_forward(evt_model* m, const ForwardCall& call) {
   for (int i = 0; i < k; ++i)
     EVT_HIP(hipStreamWaitEvent(s, m->lane_ev[1 + i], 0), "lanes join");
   m->hm_layers = m->lanes[0]->hm_layers;
+  m->tail_mode = m->lanes[0]->tail_mode;
   return EVT_OK;
 }
 
@@ -1546,6 +1598,12 @@ int evt_model_profile_read(evt_model* m, float* us, int* launches) {
 int evt_model_qkv_layout(const evt_model* m, int* headmajor_layers) {
   if (!m || !headmajor_layers) return fail(EVT_EINVAL, "null argument");
   *headmajor_layers = m->hm_layers;
+  return EVT_OK;
+}
+
+int evt_model_tail_mode(const evt_model* m, int* mode) {
+  if (!m || !mode) return fail(EVT_EINVAL, "null argument");
+  *mode = m->tail_mode;
   return EVT_OK;
 }
 

@@ -57,6 +57,11 @@ struct GemmParams {
   float eps;                          // LayerNorm epsilon (1e-5)
   int nslots;                         // stats rows are [nslots][2]: per-128-column-slab partials
   int stats_step;                     // EPI_LNIN: A row m reads stats_in row m * stats_step (0 = 1)
+  int rs_step;                        // EPI_RESLN / EPI_STATS: row m reads rstats row m * rs_step
+                                      // and writes stats_out row m * rs_step (0 = 1); takes the
+                                      // 128x128 kernel (use_big / use_pers refuse it)
+  int force_nt;                       // 1: the 128x128 kernel whatever M is (launches whose bits
+                                      // must not depend on the batch: the encoder's CLS tail)
   int gR, gC;                         // EPI_GATHER: A row (b, y, x) of an OW x OW grid gathered
   float g_inv_rr, g_inv_r;            //   from the R x R token grid A (ld lda, C channels);
   int gmode, gOW;                     //   1/OW^2, 1/OW; gmode 1 Swin PatchMerging (OW = R/2),
@@ -124,8 +129,13 @@ struct AttnParams {
   // ldq = 64, ko = N 64, vo = 2 N 64 (q, k and v of a slice each one contiguous run)
   int64_t sb = 0, sh = 0;
   int ko = 0, vo = 0;
+  // 1: K and V staged as ever, but only query tile 0 (tokens 0..15, the CLS row among them) is
+  // computed and stored, by the same tile code: its rows are bitwise the full launch's. The bf16
+  // h_k = 64 one-pass kernels only (no MX8 output); attention_cls_ok says whether a launch takes it
+  int cls_only = 0;
 };
 hipError_t attention_launch(int dtype, const AttnParams& p, hipStream_t s);
+bool attention_cls_ok(int dtype, const AttnParams& p);  // p.cls_only is honoured (else EINVAL)
 // Attention-map export (attn_maps.hip): out[b][h][i][j] = softmax_j(q_i . k_j scale) as fp32,
 // contiguous [B][H][nq][N], nq = 1 (the row of query 0) or N; p as attention_launch (out, ldo, vo
 // and the MX8 fields unused; sb / sh / ko: bf16 h_k = 64 only). scale_log2 positive and finite,

@@ -136,6 +136,7 @@ __device__ __forceinline__ void epi_rows_t(const GemmParams& p, EVT_LDS char* st
     }
   }
   // per-row LayerNorm coefficients: lane c (both halves) owns row row_lo + c
+  const int64_t rs_step = p.rs_step > 1 ? p.rs_step : 1;  // rstats / stats_out rows per row m
   float in_mu = 0.f, in_r = 0.f, rs_mu = 0.f, rs_r = 0.f;
   if (FL & (EPI_LNIN | EPI_RESLN)) {
     const int mr = m0 + row_lo + c;
@@ -143,7 +144,7 @@ __device__ __forceinline__ void epi_rows_t(const GemmParams& p, EVT_LDS char* st
       if (FL & EPI_LNIN)
         ln_coef(p.stats_in, p.nslots, (int64_t)mr * (p.stats_step > 1 ? p.stats_step : 1), p.inv_d,
                 p.eps, in_mu, in_r);
-      if (FL & EPI_RESLN) ln_coef(p.rstats, p.nslots, mr, p.inv_d, p.eps, rs_mu, rs_r);
+      if (FL & EPI_RESLN) ln_coef(p.rstats, p.nslots, (int64_t)mr * rs_step, p.inv_d, p.eps, rs_mu, rs_r);
     }
   }
 #pragma unroll
@@ -226,7 +227,7 @@ __device__ __forceinline__ void epi_rows_t(const GemmParams& p, EVT_LDS char* st
         const int img = m / p.P, t = m - img * p.P;
         orow = (int64_t)img * (p.P + 1) + 1 + t;
       }
-      *(f32x2*)(p.stats_out + 2 * (p.nslots * orow + slot)) = f32x2{s1, s2};
+      *(f32x2*)(p.stats_out + 2 * (p.nslots * orow * rs_step + slot)) = f32x2{s1, s2};
     }
   }
 }
@@ -258,6 +259,7 @@ __device__ __forceinline__ void epi_rows8_t(const GemmParams& p, EVT_LDS char* s
       }
     }
   }
+  const int64_t rs_step = p.rs_step > 1 ? p.rs_step : 1;  // rstats / stats_out rows per row m
   float in_mu = 0.f, in_r = 0.f, rs_mu = 0.f, rs_r = 0.f;  // lane c: row row_lo + (c & 31)
   if (FL & (EPI_LNIN | EPI_RESLN)) {
     const int mr = m0 + row_lo + (lane & 31);
@@ -265,7 +267,7 @@ __device__ __forceinline__ void epi_rows8_t(const GemmParams& p, EVT_LDS char* s
       if (FL & EPI_LNIN)
         ln_coef(p.stats_in, p.nslots, (int64_t)mr * (p.stats_step > 1 ? p.stats_step : 1), p.inv_d,
                 p.eps, in_mu, in_r);
-      if (FL & EPI_RESLN) ln_coef(p.rstats, p.nslots, mr, p.inv_d, p.eps, rs_mu, rs_r);
+      if (FL & EPI_RESLN) ln_coef(p.rstats, p.nslots, (int64_t)mr * rs_step, p.inv_d, p.eps, rs_mu, rs_r);
     }
   }
 #pragma unroll
@@ -370,7 +372,7 @@ __device__ __forceinline__ void epi_rows8_t(const GemmParams& p, EVT_LDS char* s
         const int img = m / p.P, t = m - img * p.P;
         orow = (int64_t)img * (p.P + 1) + 1 + t;
       }
-      *(f32x2*)(p.stats_out + 2 * (p.nslots * orow + slot)) = f32x2{s1, s2};
+      *(f32x2*)(p.stats_out + 2 * (p.nslots * orow * rs_step + slot)) = f32x2{s1, s2};
     }
   }
 }
@@ -534,6 +536,9 @@ int num_cus();
 constexpr int64_t BIG_MAX_LD = ((int64_t)1 << 31) / (2 * 384) - 64;
 
 bool use_big(const GemmParams& p, int flags) {
+  // the CLS tail's launches: rstats / stats_out at a row step (the 128x128 epilogue only), and
+  // one kernel whatever the batch is
+  if (p.force_nt || p.rs_step > 1) return false;
   if ((p.ntiles * GEMM_BN) % BIG_BN) return false;
   if (std::max(std::max(p.lda, p.ldw), std::max(p.ldc, p.resid ? p.ldr : (int64_t)0)) > BIG_MAX_LD)
     return false;
@@ -2656,7 +2661,7 @@ bool use_pers(const GemmParams& p, int flags) {
     return false;
   // timeline variants stamp s_memtime through p.pos: never on the patch GEMM (p.pos = the table)
   if ((v == 13 || v == 15) && (flags & EPI_POS)) return false;
-  if (p.N % 8 || p.vec_ok < 2) return false;
+  if (p.N % 8 || p.vec_ok < 2 || p.force_nt || p.rs_step > 1) return false;
   if ((flags & (EPI_LNIN | EPI_RESLN)) && (p.nslots > 12 || p.nslots % 2 || p.stats_step > 1))
     return false;
   // 10 / 12 slots: two statistics rounds inside the main loop, which needs its K-tiles
@@ -2754,6 +2759,7 @@ hipError_t launch_pers(const GemmParams& p, hipStream_t s) {
 bool use_p384(const GemmParams& p, int flags) {
   const int v = g_gemm_variant;
   if ((v != 0 && v != 30) || p.N % 384 || p.vec_ok < 2 || p.K < 64) return false;
+  if (p.force_nt || p.rs_step > 1) return false;
   if (std::max(std::max(p.lda, p.ldw), std::max(p.ldc, p.resid ? p.ldr : (int64_t)0)) > BIG_MAX_LD)
     return false;
   if ((flags & (EPI_LNIN | EPI_RESLN)) && (p.nslots > 8 || p.nslots % 2 || p.stats_step > 1))

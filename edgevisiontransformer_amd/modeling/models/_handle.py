@@ -99,6 +99,13 @@ class ModelHandle:
         _lib.check(_lib.load_library().evt_model_lanes(self._ptr(), ctypes.byref(out)))
         return out.value
 
+    def tail_mode(self) -> int:
+        """How the last forward ran its last encoder block (include/evt_tail.h
+        evt_model_tail_mode): bit 0 the CLS tail, bit 1 the full-row block; 0 for Swin and MX8."""
+        out = ctypes.c_int()
+        _lib.check(_lib.load_library().evt_model_tail_mode(self._ptr(), ctypes.byref(out)))
+        return out.value
+
     def workspace_bytes(self, batch: int) -> int:
         out = ctypes.c_size_t()
         _lib.check(getattr(_lib.load_library(), self._C_QUERY_WORKSPACE)(

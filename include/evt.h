@@ -192,7 +192,12 @@ int evt_model_profile_read(evt_model* m, float* us, int* launches);
  * attention: 4 B H N^2 d), gbytes = the bytes its kernels must move at least (every operand read
  * once, every output written once: activations, weights, residuals, row statistics). Replaces
  * the reference's FLOP counter (flops_calculation.py:216-251) per kernel; bench.py divides by the
- * role's time for the MFMA and HBM roofline fractions. */
+ * role's time for the MFMA and HBM roofline fractions.
+ * The last encoder block's attention, out-proj, FC1 and FC2 run on the CLS rows only (evt_tail.h)
+ * but report the layer's model work, all B T rows, as the reference's counter does: the per-role
+ * sums still add up to the model's FLOPs per image, and those four roles' averages (and bench.py's
+ * roofline fractions) read up to 1 / depth higher than the full-size kernels achieve. Kernel
+ * efficiency is to be quoted from a per-kernel trace of the full-size launches. */
 int evt_model_profile_work(evt_model* m, double* gflop, double* gbytes);
 
 /* Pack a Keras [K, N] fp32 kernel into the GEMM operand layout Wp[Npad][Kpad] (dtype), zero
@@ -514,5 +519,6 @@ int evt_model_qkv_layout(const evt_model* m, int* headmajor_layers);
 #include "evt_image.h"     /* evt_forward_image, evt_graph_capture_image, evt_patchify_u8, evt_unfold_u8 */
 #include "evt_preprocess.h"  /* evt_resize_geometry, evt_resize_plan_*, evt_resize_crop_u8 */
 #include "evt_attention_maps.h"  /* evt_forward_attention, evt_attn_map_shape, evt_attention_probs */
+#include "evt_tail.h"      /* evt_model_tail_mode (the encoder's CLS tail) */
 
 #endif /* EVT_H_ */
