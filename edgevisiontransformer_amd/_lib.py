@@ -223,6 +223,24 @@ TAIL_SIGNATURES = {
     "evt_model_tail_mode": (_I, [_P, _PI]),
 }
 
+
+class evt_classify_args(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_int32), ("values", ctypes.c_int32),
+                ("indices", ctypes.c_void_p), ("vals", ctypes.c_void_p), ("lse", ctypes.c_void_p),
+                ("labels", ctypes.c_void_p), ("rank", ctypes.c_void_p),
+                ("counters", ctypes.c_void_p)]
+
+
+# include/evt_classify.h constants
+CLASSIFY_PROB, CLASSIFY_LOGIT, CLASSIFY_MAX_K = 0, 1, 32
+# the entry points of include/evt_classify.h (evt.h includes it; bound like SIGNATURES)
+CLASSIFY_SIGNATURES = {
+    "evt_classify": (_I, [_P, _I64, _I, _I, ctypes.POINTER(evt_classify_args), _P]),
+    "evt_forward_classify": (_I, [_P, ctypes.POINTER(evt_image_args), _I,
+                                  ctypes.POINTER(evt_features_args),
+                                  ctypes.POINTER(evt_classify_args), _P]),
+}
+
 _lib = None
 _lock = threading.Lock()
 _initialized_devices = set()
@@ -244,7 +262,8 @@ def load_library() -> ctypes.CDLL:
             lenient = "EVT_LIB" in os.environ
             for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **FEATURE_SIGNATURES,
                                       **IMAGE_SIGNATURES, **PREPROCESS_SIGNATURES,
-                                      **ATTENTION_SIGNATURES, **TAIL_SIGNATURES}.items():
+                                      **ATTENTION_SIGNATURES, **TAIL_SIGNATURES,
+                                      **CLASSIFY_SIGNATURES}.items():
                 if lenient and not hasattr(lib, name):
                     continue
                 fn = getattr(lib, name)

@@ -25,7 +25,8 @@ HEADERS = ["common.h", "evt_internal.h", os.path.join("..", "..", "include", "ev
            os.path.join("..", "..", "include", "evt_image.h"),
            os.path.join("..", "..", "include", "evt_preprocess.h"),
            os.path.join("..", "..", "include", "evt_attention_maps.h"),
-           os.path.join("..", "..", "include", "evt_tail.h")]
+           os.path.join("..", "..", "include", "evt_tail.h"),
+           os.path.join("..", "..", "include", "evt_classify.h")]
 ARCH = os.environ.get("EVT_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result",
          "-ffp-contract=on"]  # contraction only within one source expression: same result on

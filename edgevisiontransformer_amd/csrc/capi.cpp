@@ -2590,6 +2590,76 @@ int evt_attention_probs(int dtype, const void* qkv, int64_t ldq, int64_t sb, int
   return EVT_OK;
 }
 
+// ---- classification outputs (include/evt_classify.h) ----------------------------------------
+
+// What evt_classify checks of its arguments (the logits pointer aside); evt_forward_classify
+// shares it. Fills the launch parameters.
+static int validate_classify(const evt_classify_args* a, int B, int C, int64_t ldl,
+                             ClassifyParams* p) {
+  if (!a) return fail(EVT_EINVAL, "classify: the classify arguments are NULL");
+  if (B < 1) return fail(EVT_EINVAL, "classify: batch must be at least 1");
+  if (C < 1 || C > (1 << 20)) return fail(EVT_EINVAL, "classify: num_classes must be in [1, 2^20]");
+  if (ldl < C) return fail(EVT_EINVAL, "classify: ldl must be at least num_classes");
+  const int kmax = std::min(C, EVT_CLASSIFY_MAX_K);
+  if (a->k < 1 || a->k > kmax)
+    return fail(EVT_EINVAL, "classify: k must be in [1, min(num_classes, EVT_CLASSIFY_MAX_K) = " +
+                                std::to_string(kmax) + "]");
+  if (a->values != EVT_CLASSIFY_PROB && a->values != EVT_CLASSIFY_LOGIT)
+    return fail(EVT_EINVAL, "classify: values must be EVT_CLASSIFY_PROB or EVT_CLASSIFY_LOGIT");
+  if (!a->indices && !a->vals && !a->lse && !a->rank && !a->counters)
+    return fail(EVT_EINVAL, "classify: no output requested: indices, vals, lse, rank and counters "
+                            "are NULL");
+  if ((a->rank || a->counters) && !a->labels)
+    return fail(EVT_EINVAL, "classify: rank and counters need labels");
+  if (((uintptr_t)a->indices | (uintptr_t)a->vals | (uintptr_t)a->lse | (uintptr_t)a->labels |
+       (uintptr_t)a->rank) & 3)
+    return fail(EVT_EINVAL, "classify: indices, vals, lse, labels and rank must be 4-byte aligned");
+  if ((uintptr_t)a->counters & 7)
+    return fail(EVT_EINVAL, "classify: counters must be 8-byte aligned");
+  p->k = a->k;
+  p->values = a->values == EVT_CLASSIFY_LOGIT ? CLS_LOGIT : CLS_PROB;
+  p->indices = a->indices; p->vals = a->vals; p->lse = a->lse;
+  p->labels = a->labels; p->rank = a->rank; p->counters = (long long*)a->counters;
+  return EVT_OK;
+}
+
+int evt_classify(const float* logits, int64_t ldl, int B, int C, const evt_classify_args* a,
+                 void* stream) {
+  if (!logits) return fail(EVT_EINVAL, "classify: logits are NULL");
+  if ((uintptr_t)logits & 3) return fail(EVT_EINVAL, "classify: logits must be 4-byte aligned");
+  ClassifyParams p;
+  EVT_RC(validate_classify(a, B, C, ldl, &p));
+  EVT_HIP(classify_launch(logits, ldl, B, C, p, (hipStream_t)stream), "classify");
+  return EVT_OK;
+}
+
+int evt_forward_classify(evt_model* m, const evt_image_args* in, int B,
+                         const evt_features_args* feat, const evt_classify_args* cls,
+                         void* stream) {
+  ImgAffine aff{};
+  if (!feat || !cls)
+    return fail(EVT_EINVAL, "forward_classify: feat and cls must be non-null");
+  EVT_RC(validate_image(m, in, &aff));
+  if (!feat->logits)
+    return fail(EVT_EINVAL, "forward_classify: feat->logits is required (the caller owns the "
+                            "logits the classification reads)");
+  if ((uintptr_t)feat->logits & 3)
+    return fail(EVT_EINVAL, "forward_classify: logits must be 4-byte aligned");
+  EVT_RC(validate_features(m, feat, B));
+  ClassifyParams p;
+  EVT_RC(validate_classify(cls, B, m->num_classes, m->num_classes, &p));
+  // the forward of evt_forward_image: logits alone over the lanes, anything more as one lane
+  const bool logits_only = !feat->pooled && !feat->tokens && feat->n_taps == 0;
+  ForwardCall call = image_call(in, aff, B, feat->logits, stream);
+  if (!logits_only) call.feat = feat;
+  EVT_RC(forward(m, call, logits_only));
+  // the lanes have joined `stream` (lanes_forward): the logits of every image are ordered before
+  ProfScope ps(m, EVT_PROF_HEAD, call.s);
+  prof_work(m, 0.0, (double)B * m->num_classes * 4.0 * (p.k + 1 + (p.labels ? 1 : 0)));
+  EVT_HIP(classify_launch(feat->logits, m->num_classes, B, m->num_classes, p, call.s), "classify");
+  return EVT_OK;
+}
+
 int evt_patchify_u8(int dtype, const uint8_t* img, int B, int C, int HW, int ps, void* out,
                     int64_t ldo, void* x, const float* cls, const float* pos, int D, float* stats,
                     const float* scale, const float* shift, void* stream) {

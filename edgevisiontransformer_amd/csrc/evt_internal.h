@@ -154,6 +154,24 @@ hipError_t layernorm_launch(int dtype, const float* x, int64_t ldx, void* y, int
 hipError_t export_rows_launch(int dtype, const void* x, int64_t ldx, int64_t row_step, float* out,
                               const float* gamma, const float* beta, int rows, int D, float eps,
                               hipStream_t s);
+// Classification outputs (features.hip; the contract is include/evt_classify.h's, whose
+// evt_classify_args this mirrors field by field): of logits [B, C] (fp32, rows ldl >= C apart) the
+// ordered top-k classes, their probabilities (CLS_PROB) or logits (CLS_LOGIT), the log-sum-exp,
+// the rank of labels[b] and counters += (valid labels, rank < 1, rank < k). 1 <= k <= min(C,
+// CLS_MAX_K), C <= 2^20, pointers 4-byte (counters 8-byte) aligned, rank / counters only with
+// labels (hipErrorInvalidValue otherwise).
+enum : int { CLS_PROB = 0, CLS_LOGIT = 1, CLS_MAX_K = 32 };
+struct ClassifyParams {
+  int k = 0, values = CLS_PROB;
+  int* indices = nullptr;      // [B, k]
+  float* vals = nullptr;       // [B, k]
+  float* lse = nullptr;        // [B]
+  const int* labels = nullptr; // [B]
+  int* rank = nullptr;         // [B]
+  long long* counters = nullptr;  // [3]
+};
+hipError_t classify_launch(const float* logits, int64_t ldl, int B, int C, const ClassifyParams& a,
+                           hipStream_t s);
 
 // Number of statistics slots of a LayerNorm of width D: one per 128-column slab of a 256-padded
 // row (both GEMM tile shapes number their slabs n0 / 128).

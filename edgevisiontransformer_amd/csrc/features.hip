@@ -100,7 +100,163 @@ __global__ __launch_bounds__(256) void export_rows_kernel(const T* __restrict__ 
   }
 }
 
+// ---- classification outputs (include/evt_classify.h) --------------------------------------------
+//
+// logits [B, C] (fp32, rows ldl apart, 4-byte aligned) -> the ordered top-k classes, their
+// probabilities or logits, the log-sum-exp, the label's rank and the hit counters.
+//
+// The order of the header (l_i > l_j, ties and -0.0 / +0.0 by index, NaN last) is the descending
+// order of one 64-bit integer per class: the usual monotone map of the float's bits (zeros folded
+// to +0, NaN to 0, below -inf) in the high word and ~index in the low word. Every class of a row
+// has a different key, so the j-th class is the largest key below the (j-1)-th: selection keeps no
+// state but the previous winner, integer maxima are exact in any order, and the rank of a label is
+// the number of keys above its own. All of it is integer work: it does not depend on the float
+// mode the file is compiled with.
+//
+// One wave64 per row, four rows per 256-thread block, grid-stride over rows, as above. A lane owns
+// the 4-class chunks lane, lane + 64, ... of its row whatever the row's alignment (one 16-byte load
+// when the row start is 16-byte aligned and the chunk is whole, dword loads otherwise): the order
+// in which a lane adds its exponentials is a function of C alone, so a row gives the same bits at
+// any batch position. Round 0 of the selection finds the row maximum m; the sum of exp(l - m) is
+// then one more pass over the (L1 / L2 resident) row with m exact, which needs no running-max
+// rescaling and no guard beyond m itself: exp(-inf - m) is exactly 0 for a finite m. k + 1 reads
+// of the row (+ 1 with labels), the same as an online first pass followed by k rounds.
+constexpr unsigned long long CLS_NO_KEY = ~0ull;  // above every key (no class has index 2^32-1)
+
+__device__ __forceinline__ unsigned long long cls_key(unsigned bits, int idx) {
+  unsigned k;
+  if ((bits & 0x7fffffffu) > 0x7f800000u) k = 0u;            // NaN: after -inf
+  else if ((bits << 1) == 0u) k = 0x80000000u;               // -0.0 == +0.0
+  else k = (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
+  return ((unsigned long long)k << 32) | (unsigned)(~(unsigned)idx);
+}
+__device__ __forceinline__ int cls_key_index(unsigned long long key) {
+  return (int)(~(unsigned)(key & 0xffffffffu));
+}
+
+// f(class, bits) for every class of the lane's chunks, in rising class order
+template <typename F>
+__device__ __forceinline__ void cls_scan(const unsigned* __restrict__ row, int C, bool al16,
+                                         int lane, F&& f) {
+  const int nch = (C + 3) >> 2;
+  for (int ch = lane; ch < nch; ch += 64) {
+    const int c0 = ch * 4;
+    if (al16 && c0 + 3 < C) {
+      const u32x4 q = *(const u32x4*)(row + c0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) f(c0 + j, q[j]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (c0 + j < C) f(c0 + j, row[c0 + j]);
+    }
+  }
+}
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long w = __shfl_xor(v, o, 64);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+__device__ __forceinline__ int wave_sum_i32(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void classify_kernel(
+    const float* __restrict__ logits, int64_t ldl, int B, int C, int k, int values,
+    int* __restrict__ indices, float* __restrict__ vals, float* __restrict__ lse,
+    const int* __restrict__ labels, int* __restrict__ rank,
+    unsigned long long* __restrict__ counters) {
+  __shared__ int hits[4][3];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool want_sum = lse != nullptr || (vals != nullptr && values == CLS_PROB);
+  int n_valid = 0, n_top1 = 0, n_topk = 0;  // of this wave's rows (wave-uniform)
+  for (int b = blockIdx.x * 4 + wave; b < B; b += gridDim.x * 4) {
+    const float* rowf = logits + (int64_t)b * ldl;
+    const unsigned* row = (const unsigned*)rowf;
+    const bool al16 = ((uintptr_t)row & 15) == 0;
+    // selection: lane j keeps the j-th key
+    unsigned long long prev = CLS_NO_KEY, mine = 0ull;
+    float m = 0.f, s = 1.f;
+    for (int j = 0; j < k; ++j) {
+      unsigned long long best = 0ull;
+      cls_scan(row, C, al16, lane, [&](int c, unsigned bits) {
+        const unsigned long long key = cls_key(bits, c);
+        if (key < prev && key > best) best = key;
+      });
+      prev = wave_max_u64(best);
+      if (lane == j) mine = prev;
+      if (j == 0 && want_sum) {
+        m = rowf[cls_key_index(prev)];
+        float acc = 0.f;
+        cls_scan(row, C, al16, lane,
+                 [&](int, unsigned bits) { acc += expf(__uint_as_float(bits) - m); });
+        s = wave_sum(acc);
+      }
+    }
+    if (lane < k && (indices || vals)) {
+      const int c = cls_key_index(mine);
+      const int64_t o = (int64_t)b * k + lane;
+      if (indices) indices[o] = c;
+      if (vals) {
+        const float l = rowf[c];
+        vals[o] = values == CLS_LOGIT ? l : expf(l - m) / s;
+      }
+    }
+    if (lse && lane == 0) lse[b] = m + logf(s);
+    if (labels) {
+      const int y = labels[b];
+      int r = -1;
+      if (y >= 0 && y < C) {
+        const unsigned long long ky = cls_key(row[y], y);
+        int above = 0;
+        cls_scan(row, C, al16, lane,
+                 [&](int c, unsigned bits) { above += cls_key(bits, c) > ky ? 1 : 0; });
+        r = wave_sum_i32(above);
+        n_valid += 1;
+        n_top1 += r < 1 ? 1 : 0;
+        n_topk += r < k ? 1 : 0;
+      }
+      if (rank && lane == 0) rank[b] = r;
+    }
+  }
+  if (counters) {  // one 64-bit integer add per block and counter (exact, order-independent)
+    if (lane == 0) {
+      hits[wave][0] = n_valid;
+      hits[wave][1] = n_top1;
+      hits[wave][2] = n_topk;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+      const int n = hits[0][threadIdx.x] + hits[1][threadIdx.x] + hits[2][threadIdx.x] +
+                    hits[3][threadIdx.x];
+      if (n) atomicAdd(counters + threadIdx.x, (unsigned long long)n);
+    }
+  }
+}
+
 }  // namespace
+
+hipError_t classify_launch(const float* logits, int64_t ldl, int B, int C,
+                           const ClassifyParams& a, hipStream_t s) {
+  if (!logits || B < 1 || C < 1 || C > (1 << 20) || ldl < C || a.k < 1 || a.k > C ||
+      a.k > CLS_MAX_K ||
+      (a.values != CLS_PROB && a.values != CLS_LOGIT) ||
+      ((a.rank || a.counters) && !a.labels) ||
+      (((uintptr_t)logits | (uintptr_t)a.indices | (uintptr_t)a.vals | (uintptr_t)a.lse |
+        (uintptr_t)a.labels | (uintptr_t)a.rank) & 3) || ((uintptr_t)a.counters & 7))
+    return hipErrorInvalidValue;
+  const int grid = std::min((B + 3) / 4, device_cus() * 8);
+  hipLaunchKernelGGL(classify_kernel, dim3(grid), dim3(256), 0, s, logits, ldl, B, C, a.k,
+                     a.values, a.indices, a.vals, a.lse, a.labels, a.rank,
+                     (unsigned long long*)a.counters);
+  return hipGetLastError();
+}
 
 hipError_t export_rows_launch(int dtype, const void* x, int64_t ldx, int64_t row_step, float* out,
                               const float* gamma, const float* beta, int rows, int D, float eps,

@@ -1,0 +1,82 @@
+"""Accuracy of a model over a dataset: the mirror of the reference's `evaluate_torch(model,
+data_loader, device)` (utils.py:785-813: argmax of the logits against the target, correct / total).
+
+    from edgevisiontransformer_amd import evaluate, EvalTransform
+    res = evaluate(model, loader, topk=5)                       # fp32 batches or Uint8Images
+    res = evaluate(model, loader, transform=EvalTransform(224), log=print)   # decoded uint8 images
+    res["acc1"], res["acck"], res["seen"], res["top1"], res["topk"]
+
+`loader` is any iterable of (images, target). The hits are counted on the device (the classify
+kernel's int64[3] counters, include/evt_classify.h): the loop enqueues one forward + classify per
+batch and reads three integers once at its end; only with `log` does it read them after every
+batch, for the reference's progress lines. A target outside [0, num_classes) (-1: unlabelled) is not
+counted. The counters are sums, so the results of several ranks or shards add up.
+"""
+from __future__ import annotations
+
+import contextlib
+from datetime import datetime
+from typing import Callable, Dict, Iterable, Optional
+
+import numpy as np
+
+from .images import Uint8Images
+
+
+def _device_batch(model, images, transform):
+    """The device-resident batch `classify_into` takes, of one loader item."""
+    import torch
+    if transform is not None and not isinstance(images, (Uint8Images, torch.Tensor, np.ndarray)):
+        images = transform(images, model.device)  # a list of decoded uint8 HWC images
+    x, _ = model._checked_image(images)
+    return x
+
+
+def _device_labels(target, batch: int, device):
+    import torch
+    y = target if isinstance(target, torch.Tensor) else torch.as_tensor(np.asarray(target))
+    y = y.reshape(-1)
+    if y.shape[0] != batch or y.dtype.is_floating_point or y.dtype == torch.bool:
+        raise ValueError(f"target must be {batch} integers, one per image")
+    return y.to(device=device, dtype=torch.int32).contiguous()
+
+
+def evaluate(model, loader: Iterable, topk: int = 5, transform=None,
+             log: Optional[Callable[[str], None]] = None) -> Dict[str, float]:
+    """Top-1 and top-`topk` accuracy of `model` over `loader`, an iterable of (images, target):
+    images an fp32 batch in the model's layout, a `Uint8Images` or, with `transform=
+    EvalTransform(...)`, a list of decoded uint8 HWC arrays; target [B] integers. Returns {"seen",
+    "top1", "topk"} (integers) and {"acc1" = top1 / seen, "acck"}; "acc1" is what the reference's
+    evaluate_torch returns. `log` (e.g. print) gets the reference's progress line per batch and
+    its summary line."""
+    import torch
+    device = model.device
+    on_device = torch.cuda.device(device) if device.type == "cuda" else contextlib.nullcontext()
+    counters = torch.zeros(3, dtype=torch.int64, device=device)
+    logits = None
+    before = (0, 0, 0)
+    for images, target in loader:
+        x = _device_batch(model, images, transform)
+        b = x.shape[0]
+        y = _device_labels(target, b, device)
+        if logits is None or logits.shape[0] < b:  # one buffer for the loop; a short last batch
+            logits = torch.empty((b, model.cfg.num_classes), dtype=torch.float32, device=device)
+        with on_device:
+            model.classify_into(x, logits=logits[:b], labels=y, counters=counters, topk=topk)
+        if log is not None:
+            now = tuple(int(v) for v in counters.cpu())
+            n, hit = now[0] - before[0], now[1] - before[1]
+            cur = hit / n * 100 if n else 0.0
+            log(f'[{datetime.now().strftime("D%m%d %H:%M:%S")} {now[0]: 5d}]  '
+                f'Cur Accuracy: {cur: .2f}% Total Accuracy: {_ratio(now[1], now[0]) * 100: .2f}%')
+            before = now
+    seen, top1, topn = (int(v) for v in counters.cpu())
+    res = {"seen": seen, "top1": top1, "topk": topn, "acc1": _ratio(top1, seen),
+           "acck": _ratio(topn, seen)}
+    if log is not None:
+        log(f'Summary model accuracy is {res["acc1"] * 100: .2f}%')
+    return res
+
+
+def _ratio(a: int, b: int) -> float:
+    return a / b if b else 0.0

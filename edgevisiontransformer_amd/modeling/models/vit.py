@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from ... import _lib
-from .attention_maps import AttentionMaps
+from .classify import Classification
 from ...weights import (ViTConfig, make_std_vit_params, make_vit_params, std_vit_param_shapes,
                         vit_config, vit_param_shapes)
 
@@ -54,7 +54,7 @@ def decode_prune_encoding(prune_encoding: str):
     return prune_setting, num_heads_list, ffn_threshold_list
 
 
-class ViT(AttentionMaps):
+class ViT(Classification):
     """Vision Transformer forward on MI355X (reference `ViT`, vit.py:9-55).
 
     `image_size` / `patch_size`: any pair with (image_size / patch_size)^2 + 1 <= 4096 tokens per
