@@ -218,6 +218,8 @@ def _attn_ref(qkv64, B, N, H):
 @pytest.mark.parametrize("B,N,H", [(2, 197, 3), (1, 197, 12), (3, 50, 2), (2, 256, 1),
                                    (1, 1, 2), (2, 129, 4), (1, 224, 6)])
 def test_attention(gpu, dtype, B, N, H):
+    """Random inputs at a few N. Both sides of every kernel / tile boundary, with inputs on which
+    one miscounted key shows: tests/test_gpu_attn_probes.py."""
     qkv64 = _rand((B * N, 3 * H * 64), 11, scale=1.5)
     qkv = qkv64.to(_ops.TDT[dtype]).to(gpu)
     out = _ops.attention(dtype, qkv, B, N, H)
