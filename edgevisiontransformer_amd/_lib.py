@@ -223,6 +223,11 @@ TAIL_SIGNATURES = {
     "evt_model_tail_mode": (_I, [_P, _PI]),
 }
 
+# the entry point of include/evt_workspace.h (evt.h includes it; bound like SIGNATURES)
+WORKSPACE_SIGNATURES = {
+    "evt_model_workspace_bytes": (_I, [_P, ctypes.POINTER(ctypes.c_size_t)]),
+}
+
 
 class evt_classify_args(ctypes.Structure):
     _fields_ = [("k", ctypes.c_int32), ("values", ctypes.c_int32),
@@ -263,7 +268,7 @@ def load_library() -> ctypes.CDLL:
             for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **FEATURE_SIGNATURES,
                                       **IMAGE_SIGNATURES, **PREPROCESS_SIGNATURES,
                                       **ATTENTION_SIGNATURES, **TAIL_SIGNATURES,
-                                      **CLASSIFY_SIGNATURES}.items():
+                                      **CLASSIFY_SIGNATURES, **WORKSPACE_SIGNATURES}.items():
                 if lenient and not hasattr(lib, name):
                     continue
                 fn = getattr(lib, name)

@@ -18,15 +18,17 @@ LAB = os.environ.get("EVT_LAB", "") not in ("", "0")
 LIB = os.path.join(HERE, "libevt_hip_lab.so" if LAB else "libevt_hip.so")
 OBJ = os.path.join(HERE, "build_obj_lab" if LAB else "build_obj")
 SOURCES = ["gemm.hip", "attention.hip", "norm.hip", "t2t.hip", "swin.hip", "mx8.hip",
-           "features.hip", "preprocess.hip", "attn_maps.hip", "capi.cpp"]
-HEADERS = ["common.h", "evt_internal.h", os.path.join("..", "..", "include", "evt.h"),
+           "features.hip", "preprocess.hip", "attn_maps.hip", "model.cpp", "encoder.cpp",
+           "model_vit.cpp", "model_t2t.cpp", "model_swin.cpp", "ops.cpp", "resize_plan.cpp"]
+HEADERS = ["common.h", "evt_internal.h", "model.h", os.path.join("..", "..", "include", "evt.h"),
            os.path.join("..", "..", "include", "evt_patchify.h"),
            os.path.join("..", "..", "include", "evt_features.h"),
            os.path.join("..", "..", "include", "evt_image.h"),
            os.path.join("..", "..", "include", "evt_preprocess.h"),
            os.path.join("..", "..", "include", "evt_attention_maps.h"),
            os.path.join("..", "..", "include", "evt_tail.h"),
-           os.path.join("..", "..", "include", "evt_classify.h")]
+           os.path.join("..", "..", "include", "evt_classify.h"),
+           os.path.join("..", "..", "include", "evt_workspace.h")]
 ARCH = os.environ.get("EVT_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result",
          "-ffp-contract=on"]  # contraction only within one source expression: same result on

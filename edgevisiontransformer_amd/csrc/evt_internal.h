@@ -1,4 +1,4 @@
-// Host-side kernel launch interface shared by the .hip translation units and capi.cpp.
+// Host-side kernel launch interface shared by the .hip translation units and the host layer (model.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

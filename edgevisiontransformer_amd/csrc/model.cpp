@@ -1,0 +1,731 @@
+// The model handle of libevt_hip.so (include/evt.h): what the three families share, lanes, graph
+// capture, profiling and the features / image / attention-map / classification forwards.
+#include "model.h"
+
+using namespace evt;
+
+namespace evt {
+
+static thread_local std::string g_err;
+
+int fail(int code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
+
+int hip_fail(hipError_t e, const char* what) {
+  return fail(EVT_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// EVT_QKV_LAYOUT=token (read when a model is created): keep the token-major qkv layout
+bool qkv_headmajor_default() {
+  const char* e = std::getenv("EVT_QKV_LAYOUT");
+  return !(e && std::strcmp(e, "token") == 0);
+}
+
+void prof_reset(evt_model* m) {
+  if (!m->prof) return;
+  m->prof_role.clear();
+  m->prof_gflop.clear();
+  m->prof_gbytes.clear();
+}
+// add algorithmic work (flops, bytes) to the innermost open ProfScope of a profiled forward
+void prof_work(const evt_model* m, double flops, double bytes) {
+  if (!m->prof || m->prof_gflop.empty()) return;
+  m->prof_gflop.back() += flops * 1e-9;
+  m->prof_gbytes.back() += bytes * 1e-9;
+}
+
+int dev_alloc(evt_model* m, void** p, size_t bytes) {
+  if (bytes == 0) bytes = 16;
+  hipError_t e = hipMalloc(p, bytes);
+  if (e != hipSuccess)
+    return fail(EVT_ENOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
+  m->allocs.push_back(*p);
+  return EVT_OK;
+}
+
+const FamilyOps& family_ops(const ModelCore& m) {
+  static const FamilyOps* const table[] = {&vit_ops(), &t2t_ops(), &swin_ops()};  // by Family
+  return *table[m.family];
+}
+
+int encoder_blocks(const ModelCore& m) { return (int)m.layers.size(); }
+
+void encoder_shape(const ModelCore& m, int, int* tokens, int* width) {
+  *tokens = m.sh.T;
+  *width = m.D;
+}
+
+int alloc_ws(evt_model* m, int B, hipStream_t s) {
+  const WsLayout l = family_ops(*m).workspace(*m, B);
+  for (const WsBuf& b : l.bufs) {
+    void** p = (void**)((char*)&m->ws + b.member);
+    EVT_RC(dev_alloc(m, p, b.bytes));
+    m->ws_bytes += b.bytes;
+    if (b.zeroed) EVT_HIP(hipMemsetAsync(*p, 0, b.zeroed, s), b.what);
+  }
+  m->ws.hbuf_bytes = l.hbuf_bytes;
+  m->ws.qa_ld = l.qa_ld;
+  m->ws.qh_ld = l.qh_ld;
+  if (l.patch_in_hbuf) m->ws.apatch = m->ws.hbuf;
+  return EVT_OK;
+}
+
+// Pack a Keras [K, N] Dense kernel. With ln_g/ln_b (the LayerNorm in front of it), gamma is folded
+// into the weight rows and b becomes c = beta . W + bias, with the column sums of the packed
+// weights alongside (gemm.hip, "LayerNorm folding").
+int make_dense(evt_model* m, DenseW* dw, const float* W, const float* bias, int K, int N,
+               hipStream_t s, const float* ln_g, const float* ln_b) {
+  const int dt = m->dtype;
+  dw->K = K;
+  dw->N = N;
+  dw->kpad = (int)round_up(K, PAD_K);
+  dw->npad = (int)round_up(N, PACK_N);
+  EVT_RC(dev_alloc(m, &dw->w, (size_t)dw->kpad * dw->npad * elem_size(dt)));
+  EVT_HIP(pack_weight(dt, W, ln_g, K, N, dw->w, dw->kpad, dw->npad, s), "pack_weight");
+  if (ln_g) {
+    EVT_RC(dev_alloc(m, (void**)&dw->b, (size_t)dw->npad * sizeof(float)));
+    EVT_RC(dev_alloc(m, (void**)&dw->colsum, (size_t)dw->npad * sizeof(float)));
+    EVT_HIP(ln_fold(dt, dw->w, dw->kpad, W, ln_b, bias, K, N, dw->colsum, dw->b, dw->npad, s),
+            "ln_fold");
+  } else if (bias) {
+    EVT_RC(dev_alloc(m, (void**)&dw->b, (size_t)dw->npad * sizeof(float)));
+    EVT_HIP(hipMemsetAsync(dw->b, 0, (size_t)dw->npad * sizeof(float), s), "memset bias");
+    EVT_HIP(hipMemcpyAsync(dw->b, bias, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s),
+            "copy bias");
+  }
+  return EVT_OK;
+}
+
+int copy_vec(evt_model* m, float** dst, const float* src, size_t n, hipStream_t s) {
+  EVT_RC(dev_alloc(m, (void**)dst, n * sizeof(float)));
+  EVT_HIP(hipMemcpyAsync(*dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s), "copy vec");
+  return EVT_OK;
+}
+
+// Pack a Keras [K, N] Dense kernel to MXFP8 (no LayerNorm folding: the MX8 model normalises in
+// the quantizer). N is padded to 32 columns of zeros so an MX8 output covers whole blocks.
+int make_mx8(evt_model* m, Mx8W* dw, const float* W, const float* bias, int K, int N,
+             hipStream_t s) {
+  dw->K = K;
+  dw->N = (int)round_up(N, 32);
+  dw->kpad = (int)round_up(K, 128);
+  dw->npad = (int)round_up(N, 128);
+  EVT_RC(dev_alloc(m, &dw->w, (size_t)dw->kpad * dw->npad));
+  EVT_RC(dev_alloc(m, (void**)&dw->s, (size_t)dw->kpad / 128 * dw->npad * 4));
+  EVT_HIP(mx8_pack_launch(W, nullptr, K, N, dw->w, dw->kpad, dw->npad, dw->s, s), "mx8_pack");
+  EVT_RC(dev_alloc(m, (void**)&dw->b, (size_t)dw->npad * sizeof(float)));
+  EVT_HIP(hipMemsetAsync(dw->b, 0, (size_t)dw->npad * sizeof(float), s), "memset bias");
+  if (bias)
+    EVT_HIP(hipMemcpyAsync(dw->b, bias, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s),
+            "copy bias");
+  return EVT_OK;
+}
+
+int dense_mx8(const Mx8W& w, int flags, const void* A, int64_t lda, const uint32_t* as, void* C,
+              int64_t ldc, uint32_t* cs, int M, const void* resid, int64_t ldr, hipStream_t s,
+              const float* rstats, const float* rgamma, const float* rbeta) {
+  Mx8GemmParams p{};
+  p.A = (const uint8_t*)A; p.lda = lda; p.As = as; p.ldas = M;
+  p.W = (const uint8_t*)w.w; p.ldw = w.kpad; p.Ws = w.s; p.ldws = w.npad;
+  p.C = C; p.ldc = ldc; p.Cs = cs; p.ldcs = M;
+  p.M = M; p.N = w.N; p.K = w.kpad;
+  p.bias = w.b; p.resid = resid; p.ldr = ldr;
+  p.rstats = rstats; p.rgamma = rgamma; p.rbeta = rbeta;
+  EVT_HIP(gemm_mx8_launch(flags, p, s), "dense_mx8");
+  return EVT_OK;
+}
+
+// Algorithmic work of one Dense launch: 2 M K N with the layer's real K and N; bytes = A and W
+// read once, C written once, plus the residual, the row statistics read / written and the small
+// bias / position vectors (what the kernel cannot avoid moving). A CLS-tail launch (work_M) counts
+// the layer's model work, all B T rows, once per role: the reference's count, whatever rows ran.
+void dense_work(const evt_model* m, const DenseW& w, const DenseCall& c) {
+  if (!m->prof || c.work_M < 0) return;
+  const double es = (double)elem_size(m->dtype);
+  const double M = c.work_M ? c.work_M : c.M, K = w.K, N = std::min(c.N, w.N);
+  const int width = c.ln_width ? c.ln_width : m->D;
+  const double slot_row = (double)stats_slots(c.slot_width ? c.slot_width : width) * 8.0;
+  double bytes = M * K * es + K * N * es + M * N * ((c.flags & EPI_OUT_F32) ? 4.0 : es) + 8.0 * N;
+  if (c.flags & EPI_RESID) bytes += M * N * es;
+  if (c.flags & EPI_LNIN) bytes += M * slot_row;
+  if (c.flags & EPI_RESLN) bytes += M * slot_row + 8.0 * N;
+  if (c.flags & EPI_STATS) bytes += M * slot_row;
+  if (c.flags & EPI_POS) bytes += (double)(c.P + 1) * N * 4.0;
+  prof_work(m, 2.0 * M * K * N, bytes);
+}
+
+GemmParams gemm_operands(const void* A, int64_t lda, const void* W, int Kpad, int Npad, void* C,
+                         int64_t ldc, int M, int N, const float* bias, const void* resid,
+                         int64_t ldr, const float* pos, int64_t ldp, int P) {
+  GemmParams p{};
+  p.A = A; p.lda = lda; p.W = W; p.ldw = Kpad; p.C = C; p.ldc = ldc;
+  p.M = M; p.N = N; p.K = Kpad; p.ntiles = Npad / GEMM_BN;
+  p.bias = bias; p.resid = resid; p.ldr = ldr; p.pos = pos; p.ldp = ldp; p.P = P;
+  p.vec_ok = (ldc % 4 == 0) && (ldr % 4 == 0) && (ldp % 4 == 0);
+  if (p.vec_ok && ldc % 8 == 0 && ldr % 8 == 0 && ldp % 8 == 0 &&
+      (((uintptr_t)C | (uintptr_t)resid) & 15) == 0)
+    p.vec_ok = 2;
+  return p;
+}
+
+GemmParams dense_params(const evt_model* m, const DenseW& w, const DenseCall& c) {
+  GemmParams p = gemm_operands(c.A, c.lda, w.w, w.kpad, w.npad, c.C, c.ldc, c.M, c.N, w.b,
+                               c.resid, c.ldr, c.pos, c.ldp, c.P);
+  p.colsum = w.colsum;
+  p.no_balance = m->no_balance;
+  p.stats_in = c.stats_in;
+  p.rstats = c.rstats;
+  p.rgamma = c.rgamma;
+  p.rbeta = c.rbeta;
+  p.stats_out = c.stats_out;
+  const int width = c.ln_width ? c.ln_width : m->D;
+  p.inv_d = 1.0f / (float)width;
+  p.eps = m->eps;  // Keras LayerNormalization(epsilon=1e-5), reference norm.py:6
+  p.nslots = stats_slots(c.slot_width ? c.slot_width : width);
+  p.stats_step = c.stats_step;
+  p.rs_step = c.rs_step;
+  p.force_nt = c.force_nt;
+  gemm_sk_bind(m->ws.sk, p);
+  return p;
+}
+
+int dense(const evt_model* m, const DenseW& w, const DenseCall& c, hipStream_t s) {
+  dense_work(m, w, c);
+  const GemmParams p = dense_params(m, w, c);
+  EVT_HIP(gemm_launch(m->dtype, c.flags, p, s), "dense");
+  return EVT_OK;
+}
+
+// evt_forward_features: one stream-export launch (features.hip) of `rows` rows of width D, through
+// the final LayerNorm when `norm`; counted under EVT_PROF_HEAD
+int feat_export(evt_model* m, const void* x, int64_t ldx, int64_t row_step, float* out, bool norm,
+                int rows, int D, hipStream_t s) {
+  ProfScope ps(m, EVT_PROF_HEAD, s);
+  prof_work(m, 0.0, (double)rows * D * (elem_size(m->dtype) + 4.0));
+  EVT_HIP(export_rows_launch(m->dtype, x, ldx, row_step, out, norm ? m->norm_g : nullptr,
+                             norm ? m->norm_b : nullptr, rows, D, m->eps, s),
+          "feature export");
+  return EVT_OK;
+}
+
+// After block `block` of a features forward, its output in ws.x: the tap, if one was asked for
+int feat_tap(evt_model* m, ForwardCall& call, int block, int64_t ldx, int rows, int D) {
+  const evt_features_args* a = call.feat;
+  if (!a || call.feat_next >= a->n_taps || a->tap_blocks[call.feat_next] != block) return EVT_OK;
+  return feat_export(m, m->ws.x, ldx, 1, a->taps[call.feat_next++], a->tap_norm != 0, rows, D,
+                     call.s);
+}
+
+// Right after block `block`'s attention kernel of an evt_forward_attention call, while ws.qkv still
+// holds the block's q and k in the layout `ap` describes: the block's map, if one was asked for
+// (attn_maps.hip; counted under EVT_PROF_HEAD like the feature exports)
+int attn_map(evt_model* m, ForwardCall& call, int block, const AttnParams& ap) {
+  const evt_attn_args* a = call.attn;
+  if (!a || call.attn_next >= a->n_maps || a->blocks[call.attn_next] != block) return EVT_OK;
+  const int nq = a->queries == EVT_ATTN_ALL ? ap.N : 1;
+  ProfScope ps(m, EVT_PROF_HEAD, call.s);
+  const double bh = (double)ap.B * ap.H;
+  prof_work(m, 4.0 * bh * nq * (double)ap.N * ap.hd,  // the scores, twice
+            bh * ((double)(nq + ap.N) * ap.hd * elem_size(m->dtype) + (double)nq * ap.N * 4.0));
+  EVT_HIP(attn_probs_launch(m->dtype, ap, nq, a->maps[call.attn_next++], call.s), "attention map");
+  return EVT_OK;
+}
+
+int finish_create(evt_model* m, int rc, evt_model** out) {
+  if (rc) {
+    std::string keep = g_err;
+    evt_model_destroy(m);
+    g_err = keep;
+    return rc;
+  }
+  *out = m;
+  return EVT_OK;
+}
+
+static int lanes_forward(evt_model* m, const ForwardCall& call) {
+  // the joins go onto s after every lane's work: a lane stream that shares s's hardware queue
+  // would otherwise queue its kernels behind s's wait for the previous lane (measured: lanes
+  // serialised in part)
+  const int k = (int)m->lanes.size(), B = call.B;
+  hipStream_t s = call.s;
+  EVT_HIP(hipEventRecord(m->lane_ev[0], s), "lanes fork");
+  for (int i = 0; i < k; ++i)
+    EVT_HIP(hipStreamWaitEvent(m->lane_s[i], m->lane_ev[0], 0), "lane fork wait");
+  for (int i = 0; i < k; ++i) {
+    const int b0 = (int)((int64_t)B * i / k), b1 = (int)((int64_t)B * (i + 1) / k);
+    if (b1 > b0) {
+      ForwardCall lane = call.slice(b0, b1, m->img_elems, m->num_classes, m->lane_s[i]);
+      EVT_RC(family_ops(*m).run(m->lanes[i], lane));
+    }
+    EVT_HIP(hipEventRecord(m->lane_ev[1 + i], m->lane_s[i]), "lane done");
+  }
+  for (int i = 0; i < k; ++i)
+    EVT_HIP(hipStreamWaitEvent(s, m->lane_ev[1 + i], 0), "lanes join");
+  m->hm_layers = m->lanes[0]->hm_layers;
+  m->tail_mode = m->lanes[0]->tail_mode;
+  return EVT_OK;
+}
+
+int check_batch(const evt_model* m, int B) {
+  if (B <= 0 || B > m->max_batch)
+    return fail(EVT_EINVAL, "batch must be in [1, max_batch=" + std::to_string(m->max_batch) + "]");
+  return EVT_OK;
+}
+
+// Every forward, eager or captured: over the lanes when the caller asked for them (logits-only
+// forwards do), the handle has lanes, is not profiling (profiling: one lane) and every lane gets
+// an image; on this handle's own workspace otherwise.
+int forward(evt_model* m, ForwardCall& call, bool use_lanes) {
+  EVT_RC(check_batch(m, call.B));
+  if (use_lanes && !m->lanes.empty() && !m->prof && call.B >= (int)m->lanes.size())
+    return lanes_forward(m, call);
+  return family_ops(*m).run(m, call);
+}
+
+// What evt_{vit,t2t,swin}_forward are: the argument checks, then the forward of an fp32 batch
+int family_forward(evt_model* m, int family, const char* wrong_family, const float* img, int B,
+                   float* logits, void* stream) {
+  if (!m || !img || !logits) return fail(EVT_EINVAL, "model, img and logits must be non-null");
+  if (m->family != family) return fail(EVT_EINVAL, wrong_family);
+  ForwardCall call;
+  call.img = img; call.B = B; call.logits = logits; call.s = (hipStream_t)stream;
+  return forward(m, call, true);
+}
+
+int affine_from(const float* scale, const float* shift, int C, ImgAffine* aff,
+                const char* what) {
+  if (C < 1 || C > 4) return fail(EVT_EINVAL, std::string(what) + ": uint8 images have 1 to 4 channels");
+  if (!scale || !shift) return fail(EVT_EINVAL, std::string(what) + ": scale and shift must be non-null");
+  *aff = ImgAffine{};
+  for (int c = 0; c < C; ++c) {
+    if (!std::isfinite(scale[c]) || !std::isfinite(shift[c]))
+      return fail(EVT_EINVAL, std::string(what) + ": scale and shift must be finite");
+    aff->scale[c] = scale[c];
+    aff->shift[c] = shift[c];
+  }
+  return EVT_OK;
+}
+
+}  // namespace evt
+
+extern "C" {
+
+int evt_init(int device) {
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess || n <= 0) return fail(EVT_ENODEV, "no HIP device visible");
+  if (device < 0 || device >= n) return fail(EVT_ENODEV, "device index out of range");
+  hipDeviceProp_t prop;
+  EVT_HIP(hipGetDeviceProperties(&prop, device), "hipGetDeviceProperties");
+  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(EVT_ENODEV, std::string("device is ") + prop.gcnArchName + ", this build is gfx950");
+  EVT_HIP(hipSetDevice(device), "hipSetDevice");
+  return EVT_OK;
+}
+
+const char* evt_last_error(void) { return g_err.c_str(); }
+
+// evt_model_set_lanes: the children (their workspaces), streams and events of a model
+static void release_lanes(evt_model* m) {
+  for (evt_model* c : m->lanes) evt_model_destroy(c);
+  for (size_t i = 0; i < m->lane_s.size(); ++i)
+    if (m->lane_own[i]) (void)hipStreamDestroy(m->lane_s[i]);
+  for (hipEvent_t e : m->lane_ev) (void)hipEventDestroy(e);
+  m->lanes.clear();
+  m->lane_s.clear();
+  m->lane_own.clear();
+  m->lane_ev.clear();
+}
+
+int evt_model_destroy(evt_model* m) {
+  if (!m) return EVT_OK;
+  // forwards enqueued on any stream may still read the workspace / weights: wait for the device
+  // before freeing (hipFree would also synchronise, but only implicitly)
+  (void)hipDeviceSynchronize();
+  release_lanes(m);
+  if (m->graph_exec) (void)hipGraphExecDestroy(m->graph_exec);
+  if (m->graph) (void)hipGraphDestroy(m->graph);
+  for (hipEvent_t e : m->prof_ev) (void)hipEventDestroy(e);
+  for (void* p : m->allocs) (void)hipFree(p);
+  delete m;
+  return EVT_OK;
+}
+
+int evt_model_profile(evt_model* m, int enable) {
+  if (!m) return fail(EVT_EINVAL, "model is NULL");
+  if (m->graph && enable) return fail(EVT_EINVAL, "profiling a model with a captured graph");
+  m->prof = enable != 0;
+  m->prof_role.clear();
+  m->prof_gflop.clear();
+  m->prof_gbytes.clear();
+  return EVT_OK;
+}
+
+int evt_model_profile_read(evt_model* m, float* us, int* launches) {
+  if (!m || !us || !launches) return fail(EVT_EINVAL, "null argument");
+  for (int r = 0; r < EVT_PROF_ROLES; ++r) {
+    us[r] = 0.f;
+    launches[r] = 0;
+  }
+  for (size_t i = 0; i < m->prof_role.size(); ++i) {
+    EVT_HIP(hipEventSynchronize(m->prof_ev[2 * i + 1]), "profile sync");
+    float ms = 0.f;
+    EVT_HIP(hipEventElapsedTime(&ms, m->prof_ev[2 * i], m->prof_ev[2 * i + 1]), "profile read");
+    us[m->prof_role[i]] += 1000.f * ms;
+    launches[m->prof_role[i]] += 1;
+  }
+  return EVT_OK;
+}
+
+int evt_model_qkv_layout(const evt_model* m, int* headmajor_layers) {
+  if (!m || !headmajor_layers) return fail(EVT_EINVAL, "null argument");
+  *headmajor_layers = m->hm_layers;
+  return EVT_OK;
+}
+
+int evt_model_tail_mode(const evt_model* m, int* mode) {
+  if (!m || !mode) return fail(EVT_EINVAL, "null argument");
+  *mode = m->tail_mode;
+  return EVT_OK;
+}
+
+int evt_model_set_lanes(evt_model* m, int lanes, void* stream) {
+  if (!m) return fail(EVT_EINVAL, "model is NULL");
+  if (m->is_lane) return fail(EVT_EINVAL, "the model is a lane of another model");
+  if (lanes < 1 || lanes > 4) return fail(EVT_EINVAL, "lanes must be in [1, 4]");
+  if (m->graph) return fail(EVT_EINVAL, "set the lanes before evt_graph_capture");
+  (void)hipDeviceSynchronize();  // forwards of the current lanes may still be running
+  release_lanes(m);
+  if (lanes == 1) return EVT_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int per = (m->max_batch + lanes - 1) / lanes;
+  auto run = [&]() -> int {
+    for (int i = 0; i < lanes; ++i) {
+      // a fresh handle with a copy of the parent's core: it shares the weights (whose allocations
+      // stay the parent's) and nothing else, and allocates its own workspace for `per` images
+      evt_model* c = new evt_model();
+      static_cast<ModelCore&>(*c) = *m;
+      c->bind_desc();
+      c->is_lane = true;
+      c->max_batch = per;
+      c->no_balance = m->family == FAM_T2T ? 1 : 0;
+      m->lanes.push_back(c);
+      EVT_RC(alloc_ws(c, per, s));
+      hipStream_t st = nullptr;
+      EVT_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "lane stream");
+      m->lane_s.push_back(st);
+      m->lane_own.push_back(1);
+    }
+    for (int i = 0; i <= lanes; ++i) {
+      hipEvent_t e = nullptr;
+      EVT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming), "lane event");
+      m->lane_ev.push_back(e);
+    }
+    EVT_HIP(hipStreamSynchronize(s), "lanes sync");
+    return EVT_OK;
+  };
+  const int rc = run();
+  if (rc) {
+    const std::string keep = g_err;
+    (void)hipDeviceSynchronize();
+    release_lanes(m);
+    g_err = keep;
+  }
+  return rc;
+}
+
+int evt_model_set_lane_streams(evt_model* m, int n, void* const* streams) {
+  if (!m || !streams) return fail(EVT_EINVAL, "null argument");
+  if (m->lanes.empty() || n != (int)m->lanes.size())
+    return fail(EVT_EINVAL, "n must equal the lane count (evt_model_set_lanes first)");
+  for (int i = 0; i < n; ++i)
+    if (!streams[i]) return fail(EVT_EINVAL, "lane streams must be non-NULL");
+  if (m->graph) return fail(EVT_EINVAL, "set the lane streams before evt_graph_capture");
+  (void)hipDeviceSynchronize();
+  for (int i = 0; i < n; ++i) {
+    if (m->lane_own[i]) (void)hipStreamDestroy(m->lane_s[i]);
+    m->lane_s[i] = (hipStream_t)streams[i];
+    m->lane_own[i] = 0;
+  }
+  return EVT_OK;
+}
+
+int evt_model_lanes(const evt_model* m, int* lanes) {
+  if (!m || !lanes) return fail(EVT_EINVAL, "null argument");
+  *lanes = m->lanes.empty() ? 1 : (int)m->lanes.size();
+  return EVT_OK;
+}
+
+int evt_model_workspace_bytes(const evt_model* m, size_t* bytes) {
+  if (!m || !bytes) return fail(EVT_EINVAL, "null argument");
+  *bytes = m->ws_bytes;
+  for (const evt_model* c : m->lanes) *bytes += c->ws_bytes;
+  return EVT_OK;
+}
+
+int evt_model_profile_work(evt_model* m, double* gflop, double* gbytes) {
+  if (!m || !gflop || !gbytes) return fail(EVT_EINVAL, "null argument");
+  for (int r = 0; r < EVT_PROF_ROLES; ++r) gflop[r] = gbytes[r] = 0.0;
+  for (size_t i = 0; i < m->prof_role.size(); ++i) {
+    gflop[m->prof_role[i]] += m->prof_gflop[i];
+    gbytes[m->prof_role[i]] += m->prof_gbytes[i];
+  }
+  return EVT_OK;
+}
+
+// Capture what `enqueue` puts on `stream` as the model's graph (evt_graph_capture[_image])
+static int graph_capture(evt_model* m, void* stream, const std::function<int()>& enqueue) {
+  if (!m || !stream) return fail(EVT_EINVAL, "graph capture needs a model and a non-NULL stream");
+  if (m->prof)  // the events would be captured into the graph, never recorded on the stream
+    return fail(EVT_EINVAL, "graph capture while profiling is enabled (evt_model_profile(m, 0) first)");
+  hipStream_t s = (hipStream_t)stream;
+  if (m->graph_exec) {
+    (void)hipGraphExecDestroy(m->graph_exec);
+    m->graph_exec = nullptr;
+  }
+  if (m->graph) {
+    (void)hipGraphDestroy(m->graph);
+    m->graph = nullptr;
+  }
+  EVT_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal), "begin capture");
+  const int rc = enqueue();
+  hipGraph_t g = nullptr;
+  const hipError_t e = hipStreamEndCapture(s, &g);
+  if (rc) {
+    if (g) (void)hipGraphDestroy(g);
+    return rc;
+  }
+  if (e != hipSuccess) return hip_fail(e, "end capture");
+  hipGraphExec_t ge = nullptr;
+  const hipError_t ei = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+  if (ei != hipSuccess) {
+    (void)hipGraphDestroy(g);
+    return hip_fail(ei, "graph instantiate");
+  }
+  m->graph = g;
+  m->graph_exec = ge;
+  return EVT_OK;
+}
+
+int evt_graph_capture(evt_model* m, const float* img, int batch, float* logits, void* stream) {
+  return graph_capture(m, stream, [&]() {  // any family: the handle's own
+    return family_forward(m, m->family, "", img, batch, logits, stream);
+  });
+}
+
+int evt_graph_launch(evt_model* m, void* stream) {
+  if (!m || !m->graph_exec) return fail(EVT_EINVAL, "no captured graph (call evt_graph_capture)");
+  EVT_HIP(hipGraphLaunch(m->graph_exec, (hipStream_t)stream), "graph launch");
+  return EVT_OK;
+}
+
+// ---- feature outputs (include/evt_features.h) ---------------------------------------------
+
+static int model_blocks(const evt_model* m) { return family_ops(*m).blocks(*m); }
+
+int evt_features_shape(const evt_model* m, int* F, int* T, int* n_blocks) {
+  if (!m) return fail(EVT_EINVAL, "model is NULL");
+  int tokens = 0, width = 0;
+  family_ops(*m).shape(*m, -1, &tokens, &width);
+  if (F) *F = width;
+  if (T) *T = tokens;
+  if (n_blocks) *n_blocks = model_blocks(m);
+  return EVT_OK;
+}
+
+int evt_tap_shape(const evt_model* m, int block, int* tokens, int* width) {
+  if (!m || !tokens || !width) return fail(EVT_EINVAL, "null argument");
+  if (block < 0 || block >= model_blocks(m))
+    return fail(EVT_EINVAL, "block must be in [0, " + std::to_string(model_blocks(m)) + ")");
+  family_ops(*m).shape(*m, block, tokens, width);
+  return EVT_OK;
+}
+
+// What evt_forward_features checks of (model, outputs, batch); evt_forward_image shares it
+static int validate_features(const evt_model* m, const evt_features_args* a, int B) {
+  if (a->n_taps < 0 || a->n_taps > 64) return fail(EVT_EINVAL, "n_taps must be in [0, 64]");
+  if (!a->logits && !a->pooled && !a->tokens && a->n_taps == 0)
+    return fail(EVT_EINVAL, "no output requested: logits, pooled and tokens are NULL, n_taps is 0");
+  EVT_RC(check_batch(m, B));  // (here, ahead of forward's own: the order the checks fire in)
+  if (a->tap_norm != 0 && a->tap_norm != 1) return fail(EVT_EINVAL, "tap_norm must be 0 or 1");
+  if (a->tap_norm && (m->family == FAM_SWIN || !m->norm_g))
+    return fail(EVT_EINVAL, m->family == FAM_SWIN
+                                ? "tap_norm: Swin stage widths differ from the final LayerNorm's"
+                                : "tap_norm: a REFERENCE ViT has no final LayerNorm");
+  uintptr_t align = (uintptr_t)a->pooled | (uintptr_t)a->tokens;  // 16-B stores (features.hip)
+  if (a->n_taps > 0) {
+    if (!a->tap_blocks || !a->taps)
+      return fail(EVT_EINVAL, "n_taps > 0 needs the tap_blocks and taps arrays");
+    if (m->mx8) return fail(EVT_EINVAL, "taps are not available on an EVT_DTYPE_MX8 model");
+    const int nb = model_blocks(m);
+    for (int i = 0; i < a->n_taps; ++i) {
+      if (a->tap_blocks[i] < 0 || a->tap_blocks[i] >= nb)
+        return fail(EVT_EINVAL, "tap block " + std::to_string(a->tap_blocks[i]) +
+                                    " is outside [0, " + std::to_string(nb) + ")");
+      if (i > 0 && a->tap_blocks[i] <= a->tap_blocks[i - 1])
+        return fail(EVT_EINVAL, "tap_blocks must be strictly increasing");
+      if (!a->taps[i]) return fail(EVT_EINVAL, "tap pointer " + std::to_string(i) + " is NULL");
+      align |= (uintptr_t)a->taps[i];
+    }
+  }
+  if (align & 15) return fail(EVT_EINVAL, "feature outputs must be 16-byte aligned");
+  return EVT_OK;
+}
+
+int evt_forward_features(evt_model* m, const float* img, int B, const evt_features_args* a,
+                         void* stream) {
+  if (!m || !img || !a) return fail(EVT_EINVAL, "model, img and args must be non-null");
+  EVT_RC(validate_features(m, a, B));
+  ForwardCall call;
+  call.img = img; call.B = B; call.logits = a->logits; call.feat = a; call.s = (hipStream_t)stream;
+  // one lane, on this handle's own workspace, whatever its lane count (as a profiled forward)
+  return forward(m, call, false);
+}
+
+// ---- uint8 image input (include/evt_image.h) ------------------------------------------------
+
+// The descriptor alone (no model needed), then what the model adds for EVT_IMG_U8_NHWC
+static int validate_image(const evt_model* m, const evt_image_args* in, ImgAffine* aff) {
+  if (!in) return fail(EVT_EINVAL, "image descriptor is NULL");
+  if (!in->data) return fail(EVT_EINVAL, "image data is NULL");
+  if (in->format != EVT_IMG_F32 && in->format != EVT_IMG_U8_NHWC)
+    return fail(EVT_EINVAL, "unknown image format " + std::to_string(in->format));
+  if (!m) return fail(EVT_EINVAL, "model is NULL");
+  if (in->format == EVT_IMG_F32) return EVT_OK;
+  const int C = m->in_chans, S = m->image_size;
+  if (C > 4) return fail(EVT_EINVAL, "uint8 input: in_chans must be <= 4");
+  EVT_RC(affine_from(in->scale, in->shift, C, aff, "uint8 input"));
+  const uintptr_t a = (uintptr_t)in->data;
+  if (m->family == FAM_T2T) return (C == 4 && (a & 3)) ? fail(EVT_EINVAL, "uint8 input: data must be 4-byte aligned") : EVT_OK;
+  const int ps = m->patch_size;
+  if (((int64_t)ps * S * C) % 4)
+    return fail(EVT_EINVAL, "uint8 input: patch_size*image_size*in_chans must be a multiple of 4");
+  if (m->family == FAM_VIT && !m->patch_cm && !m->patch_ld)
+    return fail(EVT_EINVAL, "uint8 input: this ViT's patch vectors are not channel-major "
+                            "(patch_size % 8 != 0 with patch_size^2*in_chans % 64 == 0)");
+  // lanes start at multiples of S*S*C bytes: a multiple of 4 (and of 16 for the fused stem)
+  const bool stem96 = m->family == FAM_SWIN && m->dtype == DT_BF16 && C == 3 && ps == 4 &&
+                      m->stages[0].C == 96 && S % 16 == 0 && S <= 256 && m->stages[0].w == 7;
+  if (a & (stem96 ? 15 : 3))
+    return fail(EVT_EINVAL, stem96 ? "uint8 input: data must be 16-byte aligned (fused Swin stem)"
+                                   : "uint8 input: data must be 4-byte aligned");
+  return EVT_OK;
+}
+
+// A call of B images from a validated image descriptor (aff: validate_image's; uint8 only reads it)
+static ForwardCall image_call(const evt_image_args* in, const ImgAffine& aff, int B, float* logits,
+                              void* stream) {
+  ForwardCall call;
+  if (in->format == EVT_IMG_F32) call.img = (const float*)in->data;
+  else call.img8 = (const uint8_t*)in->data;
+  call.aff = aff; call.B = B; call.logits = logits; call.s = (hipStream_t)stream;
+  return call;
+}
+
+int evt_forward_image(evt_model* m, const evt_image_args* in, int B, const evt_features_args* a,
+                      void* stream) {
+  ImgAffine aff{};
+  if (!a) return fail(EVT_EINVAL, "image descriptor, outputs and model must be non-null");
+  EVT_RC(validate_image(m, in, &aff));
+  EVT_RC(validate_features(m, a, B));
+  // logits alone: over the handle's lanes, like evt_*_forward; anything more: a features forward
+  const bool logits_only = a->logits && !a->pooled && !a->tokens && a->n_taps == 0;
+  ForwardCall call = image_call(in, aff, B, a->logits, stream);
+  if (!logits_only) call.feat = a;
+  return forward(m, call, logits_only);
+}
+
+int evt_graph_capture_image(evt_model* m, const evt_image_args* in, int B, float* logits,
+                            void* stream) {
+  ImgAffine aff{};
+  EVT_RC(validate_image(m, in, &aff));
+  if (in->format == EVT_IMG_F32)
+    return evt_graph_capture(m, (const float*)in->data, B, logits, stream);
+  if (!logits || !stream)
+    return fail(EVT_EINVAL, "graph capture needs logits and a non-NULL stream");
+  EVT_RC(check_batch(m, B));  // ahead of the capture's own checks, and of the previous graph's end
+  ForwardCall call = image_call(in, aff, B, logits, stream);
+  return graph_capture(m, stream, [&]() { return forward(m, call, true); });
+}
+
+// ---- attention-map outputs (include/evt_attention_maps.h) -----------------------------------
+
+static int attn_family(const evt_model* m) {
+  if (const char* why = family_ops(*m).no_attn_maps) return fail(EVT_EINVAL, why);
+  if (m->mx8) return fail(EVT_EINVAL, "attention maps are not available on an EVT_DTYPE_MX8 model");
+  return EVT_OK;
+}
+
+int evt_attn_map_shape(const evt_model* m, int block, int* heads, int* tokens) {
+  if (!m || !heads || !tokens) return fail(EVT_EINVAL, "null argument");
+  EVT_RC(attn_family(m));
+  if (block < 0 || block >= (int)m->layers.size())
+    return fail(EVT_EINVAL, "block must be in [0, " + std::to_string(m->layers.size()) + ")");
+  *heads = m->layers[block].heads;
+  *tokens = m->sh.T;
+  return EVT_OK;
+}
+
+int evt_forward_attention(evt_model* m, const evt_image_args* in, int B,
+                          const evt_features_args* feat, const evt_attn_args* a, void* stream) {
+  ImgAffine aff{};
+  if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and attn must be non-null");
+  EVT_RC(validate_image(m, in, &aff));
+  EVT_RC(attn_family(m));
+  if (a->n_maps < 0 || a->n_maps > 64) return fail(EVT_EINVAL, "n_maps must be in [0, 64]");
+  if (a->n_maps == 0 && !feat)
+    return fail(EVT_EINVAL, "no output requested: n_maps is 0 and feat is NULL");
+  if (feat) EVT_RC(validate_features(m, feat, B));
+  else EVT_RC(check_batch(m, B));
+  if (a->queries != EVT_ATTN_CLS && a->queries != EVT_ATTN_ALL)
+    return fail(EVT_EINVAL, "queries must be EVT_ATTN_CLS or EVT_ATTN_ALL");
+  if (a->n_maps > 0) {
+    if (!a->blocks || !a->maps) return fail(EVT_EINVAL, "n_maps > 0 needs the blocks and maps arrays");
+    const int nb = (int)m->layers.size();
+    for (int i = 0; i < a->n_maps; ++i) {
+      if (a->blocks[i] < 0 || a->blocks[i] >= nb)
+        return fail(EVT_EINVAL, "map block " + std::to_string(a->blocks[i]) + " is outside [0, " +
+                                    std::to_string(nb) + ")");
+      if (i > 0 && a->blocks[i] <= a->blocks[i - 1])
+        return fail(EVT_EINVAL, "map blocks must be strictly increasing");
+      if (!a->maps[i]) return fail(EVT_EINVAL, "map pointer " + std::to_string(i) + " is NULL");
+      if ((uintptr_t)a->maps[i] & 15) return fail(EVT_EINVAL, "attention maps must be 16-byte aligned");
+    }
+  }
+  ForwardCall call = image_call(in, aff, B, feat ? feat->logits : nullptr, stream);
+  call.feat = feat;
+  call.attn = a;
+  // one lane, on this handle's own workspace, whatever its lane count (as a features forward)
+  return forward(m, call, false);
+}
+
+int evt_forward_classify(evt_model* m, const evt_image_args* in, int B,
+                         const evt_features_args* feat, const evt_classify_args* cls,
+                         void* stream) {
+  ImgAffine aff{};
+  if (!feat || !cls)
+    return fail(EVT_EINVAL, "forward_classify: feat and cls must be non-null");
+  EVT_RC(validate_image(m, in, &aff));
+  if (!feat->logits)
+    return fail(EVT_EINVAL, "forward_classify: feat->logits is required (the caller owns the "
+                            "logits the classification reads)");
+  if ((uintptr_t)feat->logits & 3)
+    return fail(EVT_EINVAL, "forward_classify: logits must be 4-byte aligned");
+  EVT_RC(validate_features(m, feat, B));
+  ClassifyParams p;
+  EVT_RC(validate_classify(cls, B, m->num_classes, m->num_classes, &p));
+  // the forward of evt_forward_image: logits alone over the lanes, anything more as one lane
+  const bool logits_only = !feat->pooled && !feat->tokens && feat->n_taps == 0;
+  ForwardCall call = image_call(in, aff, B, feat->logits, stream);
+  if (!logits_only) call.feat = feat;
+  EVT_RC(forward(m, call, logits_only));
+  // the lanes have joined `stream` (lanes_forward): the logits of every image are ordered before
+  ProfScope ps(m, EVT_PROF_HEAD, call.s);
+  prof_work(m, 0.0, (double)B * m->num_classes * 4.0 * (p.k + 1 + (p.labels ? 1 : 0)));
+  EVT_HIP(classify_launch(feat->logits, m->num_classes, B, m->num_classes, p, call.s), "classify");
+  return EVT_OK;
+}
+
+}  // extern "C"

@@ -112,6 +112,12 @@ class ModelHandle:
             ctypes.byref(self._desc(batch)), batch, ctypes.byref(out)))
         return out.value
 
+    def allocated_workspace_bytes(self) -> int:
+        """Bytes this handle's workspace, lanes included, asked for (include/evt_workspace.h)."""
+        out = ctypes.c_size_t()
+        _lib.check(_lib.load_library().evt_model_workspace_bytes(self._ptr(), ctypes.byref(out)))
+        return out.value
+
     def close(self) -> None:
         if getattr(self, "_handle", None):
             _lib.load_library().evt_model_destroy(self._ptr())

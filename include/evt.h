@@ -521,5 +521,6 @@ int evt_model_qkv_layout(const evt_model* m, int* headmajor_layers);
 #include "evt_attention_maps.h"  /* evt_forward_attention, evt_attn_map_shape, evt_attention_probs */
 #include "evt_classify.h"  /* evt_classify, evt_forward_classify */
 #include "evt_tail.h"      /* evt_model_tail_mode (the encoder's CLS tail) */
+#include "evt_workspace.h" /* evt_model_workspace_bytes */
 
 #endif /* EVT_H_ */

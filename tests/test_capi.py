@@ -133,7 +133,8 @@ def test_swin_host_validation(lib):
 
 def test_mx8_dtype_host_validation(lib):
     """EVT_DTYPE_MX8 (2): accepted for the reference semantics, workspace includes the MX8
-    operand buffers (qa, qh, their scales, the LayerNorm row statistics); rejected for STANDARD."""
+    operand buffers (qa, qh, their scales, the LayerNorm row statistics) and, the MX8 encoder
+    having no CLS tail, leaves out its hidden rows ([B, ffn_st], bf16); rejected for STANDARD."""
     from edgevisiontransformer_amd import _lib
     arr = (ctypes.c_int32 * 12)(*([12] * 12))
     hd = (ctypes.c_int32 * 12)(*([64] * 12))
@@ -145,7 +146,7 @@ def test_mx8_dtype_host_validation(lib):
     assert lib.evt_query_workspace(ctypes.byref(d8), 512, ctypes.byref(out_8)) == 0
     rows = 512 * 197
     extra = rows * (768 + 768 // 32 + 3072 + 3072 // 32 + 8)
-    assert out_8.value - out_bf.value >= extra
+    assert out_8.value - out_bf.value == extra - 512 * 3072 * 2
     d8.semantics = _lib.VIT_STANDARD
     assert lib.evt_query_workspace(ctypes.byref(d8), 512, ctypes.byref(out_8)) == _lib.EVT_EINVAL
     assert b"MX8" in lib.evt_last_error()

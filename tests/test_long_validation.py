@@ -1,4 +1,4 @@
-"""Host-side validation of the limits past 256 tokens per image (csrc/capi.cpp validate /
+"""Host-side validation of the limits past 256 tokens per image (csrc/model_vit.cpp validate /
 validate_t2t through the workspace queries, and the op entry points' argument checks): no GPU is
 touched, every call returns before any launch."""
 import ctypes

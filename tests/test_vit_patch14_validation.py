@@ -1,4 +1,4 @@
-"""Host-side validation of the patch-14 and wide ViT configurations (csrc/capi.cpp validate through
+"""Host-side validation of the patch-14 and wide ViT configurations (csrc/model_vit.cpp validate through
 evt_query_workspace, and evt_patchify_ld's argument checks): no GPU is touched, every call returns
 before any launch."""
 import ctypes
