@@ -218,6 +218,15 @@ ATTENTION_SIGNATURES = {
     "evt_attention_probs": (_I, [_I, _P, _I64, _I64, _I64, _I, _I, _I, _I, _I, _F, _I, _P, _P]),
 }
 
+# the entry points of include/evt_window_attention.h (evt.h includes it; bound like SIGNATURES)
+WINDOW_ATTENTION_SIGNATURES = {
+    "evt_window_attn_map_shape": (_I, [_P, _I, _PI, _PI, _PI]),
+    "evt_forward_window_attention": (_I, [_P, ctypes.POINTER(evt_image_args), _I,
+                                          ctypes.POINTER(evt_features_args),
+                                          ctypes.POINTER(evt_attn_args), _P]),
+    "evt_window_attention_probs": (_I, [_I, _P, _I64, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+}
+
 # the entry point of include/evt_tail.h (evt.h includes it; bound like SIGNATURES)
 TAIL_SIGNATURES = {
     "evt_model_tail_mode": (_I, [_P, _PI]),
@@ -267,7 +276,8 @@ def load_library() -> ctypes.CDLL:
             lenient = "EVT_LIB" in os.environ
             for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **FEATURE_SIGNATURES,
                                       **IMAGE_SIGNATURES, **PREPROCESS_SIGNATURES,
-                                      **ATTENTION_SIGNATURES, **TAIL_SIGNATURES,
+                                      **ATTENTION_SIGNATURES, **WINDOW_ATTENTION_SIGNATURES,
+                                      **TAIL_SIGNATURES,
                                       **CLASSIFY_SIGNATURES, **WORKSPACE_SIGNATURES}.items():
                 if lenient and not hasattr(lib, name):
                     continue

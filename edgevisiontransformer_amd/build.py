@@ -26,6 +26,7 @@ HEADERS = ["common.h", "evt_internal.h", "model.h", os.path.join("..", "..", "in
            os.path.join("..", "..", "include", "evt_image.h"),
            os.path.join("..", "..", "include", "evt_preprocess.h"),
            os.path.join("..", "..", "include", "evt_attention_maps.h"),
+           os.path.join("..", "..", "include", "evt_window_attention.h"),
            os.path.join("..", "..", "include", "evt_tail.h"),
            os.path.join("..", "..", "include", "evt_classify.h"),
            os.path.join("..", "..", "include", "evt_workspace.h")]

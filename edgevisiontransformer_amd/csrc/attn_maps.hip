@@ -323,4 +323,320 @@ hipError_t attn_probs_launch(int dtype, const AttnParams& p_in, int nq, float* o
   return launch_probs<float, 128>(p, nq, nqb, wide, out, s);
 }
 
+// ---- Swin window attention maps (include/evt_window_attention.h) -------------------------------
+//
+//   out[b][win][h][q][k] = softmax_k(q_q . k_k 32^-0.5 + rpb[rel(q, k)][h] + mask(win, q, k))
+//
+// of the q and k rows the block's QKV GEMM stored in raster order: what the window kernels of
+// swin.hip form in registers, multiply by V and discard. q, k: window-local tokens of the SHIFTED
+// frame, row-major inside the window (swin.hip WinGeom::row); win: row-major over that frame's
+// windows; N = w * w tokens per window, head size 32. A pair in different SW-MSA regions gets a
+// -inf score, so exactly 0.0f (the reference's additive -100 leaves at most e^-100 of relative
+// weight, below fp32 resolution); a query shares a region with itself, so no row is empty and the
+// row maximum's own term keeps the sum >= 1: every value is finite and in [0, 1]. Scores,
+// statistics and normalisation in fp32: the probability before the bf16 rounding the forward
+// applies for P . V.
+//
+// The bias comes from the head's compact table (rpb_compact_table: entry r = table[r][h] log2 e),
+// bias(q, k) = T[(2w - 1)(qi - ki + w - 1) + (qj - kj + w - 1)], copied to LDS; the regions are
+// worked out on the VALU as in swin.hip (region bit 0: rows >= w - shift of a window of the last
+// window row, bit 1: the same for columns). There is no V, no LDS V tile and no P . V.
+//
+// bf16 (window_probs_bf16_kernel<w>): the geometry of window_attn_bf16_kernel (w = 7: four waves
+// per block, a wave per (image, window, head), four 16-token tiles of which keys 49 .. 63 never
+// contribute and are never stored) and of window12_attn_bf16_kernel (w = 12: three waves per
+// (image, window, head), three query tiles each, nine K tiles). Q / K fragments are 16-B loads
+// straight from the raster qkv rows through the image's buffer descriptor, S^T = K Q^T is one
+// v_mfma_f32_16x16x32_bf16 per tile pair. Every wave keeps its own copy of the bias table, so the
+// kernel has no block barrier. fp32 (window_probs_f32_kernel<w>): thread = query on the VALU, K
+// and the table in LDS, the scores computed twice (maximum, then exp2) as in
+// window12_attn_f32_kernel.
+//
+// Stores. The [N, N] matrix of one (image, window, head) is one contiguous run of the output
+// (9604 B for w = 7, 82944 B for w = 12), and the 16 query rows of a tile are a contiguous piece of
+// it. The MFMA result has a query per lane column, so each wave passes its tile through a private
+// LDS tile and stores the piece as consecutive non-temporal dwords, a lane per float: 256
+// contiguous bytes per wave instruction, the form that won for the ViT export (above). A w = 7
+// matrix starts 16-byte aligned one time in four and keeps that form; a w = 12 matrix always does
+// (and its rows are 576 B), so the bf16 w = 12 kernel also has a 16-B form, a lane per 4 keys, and
+// launches it: measured at Swin-B 384 px stage 1 with 64 images (1.36 GB) 400.8 us against 444.2 us
+// for the dword form (scripts/window_attention_maps_measure.py). Unlike the ViT rows it
+// has no unaligned edges to peel. EVT_WINDOW_MAPS_STORE=dword selects the other form for a
+// measurement; both write the same bits. Output offsets are 64-bit.
+namespace {
+
+constexpr int wp_prow(int w) { return w == 7 ? 49 : 148; }  // LDS tile row (148: b128 conflict-free)
+constexpr int wp_tl(int w) { return w == 7 ? 192 : 576; }   // LDS floats of a table copy
+
+template <int W, bool WIDE>
+__global__ __launch_bounds__(W == 7 ? 256 : 192) void window_probs_bf16_kernel(
+    SwinAttnParams p, const float* __restrict__ table, int trow, float* __restrict__ out) {
+  constexpr int N = W * W, NKT = (N + 15) / 16, TW = 2 * W - 1;
+  constexpr int PW = W == 7 ? 1 : 3;  // waves per (image, window, head)
+  constexpr int PB = W == 7 ? 4 : 1;  // (image, window, head) per block
+  constexpr int QTW = NKT / PW;       // query tiles per wave
+  constexpr int PROW = wp_prow(W), PT = 16 * PROW, TL = wp_tl(W);
+  static_assert(NKT % PW == 0 && TW * TW <= TL && PT % 4 == 0 && (!WIDE || N % 4 == 0), "geometry");
+  __shared__ __attribute__((aligned(16))) float smem[PB * PW * (PT + TL)];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // uniform: scalar index math
+  const int pair = blockIdx.x * PB + wave / PW, pw = wave % PW;  // (pairs < 2^31: the launcher)
+  const int nw = p.nwx * p.nwx;
+  if (pair >= p.B * nw * p.H) return;  // wave-uniform; the kernel has no block barrier
+  const int h = pair % p.H;
+  const int bw = pair / p.H;
+  const int win = bw % nw, b = bw / nw;
+  const int R = p.R, s0 = p.shift;
+  const int wy = win / p.nwx, wx = win - wy * p.nwx;
+  const int y0 = wy * W + s0, x0 = wx * W + s0;
+  const bool lr_ = s0 && wy == p.nwx - 1, lc_ = s0 && wx == p.nwx - 1;  // last window row / column
+  const int cut = W - s0;
+  // image-local raster row of window token t (with the cyclic shift)
+  auto lrow = [&](int t) {
+    const int i = t / W, j = t - W * i;
+    int y = y0 + i, x = x0 + j;
+    if (y >= R) y -= R;
+    if (x >= R) x -= R;
+    return y * R + x;
+  };
+  const int ldq2 = (int)p.ldq * 2, C2 = p.C * 2;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+      (char*)const_cast<void*>(p.qkv) + (int64_t)b * R * R * ldq2, 0, R * R * ldq2, 0x00020000);
+  EVT_LDS float* Ps = (EVT_LDS float*)smem + wave * (PT + TL);  // this wave's [16 queries][PROW]
+  EVT_LDS float* Ts = Ps + PT;                                  // and its copy of the head's table
+  for (int e = lane; e < TW * TW; e += 64) Ts[e] = table[(int64_t)h * trow + e];
+  // K fragments of every tile, Q fragments of this wave's: tile i, lane (token 16 i + c16,
+  // d 8 g .. 8 g + 7); tokens past N - 1 (w = 7) repeat token N - 1 and are masked below
+  const int g = lane >> 4, c16 = lane & 15;
+  u32x4 kf[NKT], qf[QTW];
+#pragma unroll
+  for (int i = 0; i < NKT; ++i) {
+    const int vo = lrow(min(16 * i + c16, N - 1)) * ldq2 + (h * 32 + 8 * g) * 2;
+    kf[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, C2, 0));
+  }
+#pragma unroll
+  for (int n = 0; n < QTW; ++n) {
+    const int vo = lrow(min(16 * (pw * QTW + n) + c16, N - 1)) * ldq2 + (h * 32 + 8 * g) * 2;
+    qf[n] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, 0, 0));
+  }
+  // per-lane table offsets of its keys k = 16 kt + 4 g + j and their region codes, a byte per j
+  int kofs[NKT][4];
+  unsigned kc[NKT];
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt) {
+    kc[kt] = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int k = min(16 * kt + 4 * g + j, N - 1), ki = k / W, kj = k - W * ki;
+      kofs[kt][j] = TW * ki + kj;
+      kc[kt] |= (unsigned)((lr_ && ki >= cut ? 1 : 0) | (lc_ && kj >= cut ? 2 : 0)) << (8 * j);
+    }
+  }
+  // the table copy is this wave's alone: LDS operations of a wave complete in order
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+  const int64_t obase = (int64_t)pair * N * N;  // element offset of the (image, window, head)
+  const float NEG = -INFINITY;
+#pragma unroll
+  for (int n = 0; n < QTW; ++n) {
+    const int qt = pw * QTW + n;
+    const int q = min(16 * qt + c16, N - 1), qi = q / W, qj = q - W * qi;
+    const EVT_LDS float* Tq = Ts + (TW * (qi + W - 1) + qj + W - 1);
+    const unsigned cq = ((lr_ && qi >= cut ? 1u : 0u) | (lc_ && qj >= cut ? 2u : 0u)) * 0x01010101u;
+    // s[kt][j] = S^T[key 16 kt + 4 g + j][query q], in the log2 domain, + bias, then the masks
+    f32x4 s[NKT];
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) {
+      const f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf[kt]),
+                                                      __builtin_bit_cast(bf16x8, qf[n]), acc, 0, 0,
+                                                      0);
+      const unsigned x = kc[kt] ^ cq;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        s[kt][j] = s[kt][j] * p.scale_log2 + Tq[-kofs[kt][j]];
+        if ((x >> (8 * j)) & 3u) s[kt][j] = NEG;            // a key of another region
+        if (N % 16 != 0 && 16 * kt + 4 * g + j >= N) s[kt][j] = NEG;  // w = 7: keys 49 .. 63
+      }
+    }
+    float mx = NEG;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+      mx = fmaxf(mx, fmaxf(fmaxf(s[kt][0], s[kt][1]), fmaxf(s[kt][2], s[kt][3])));
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    float sum = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[kt][j] = __builtin_amdgcn_exp2f(s[kt][j] - mx);
+      sum += (s[kt][0] + s[kt][1]) + (s[kt][2] + s[kt][3]);
+    }
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+    const float inv = 1.0f / sum;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) {
+      const f32x4 pv = s[kt] * inv;
+      if constexpr (PROW % 4 == 0) {
+        *(EVT_LDS f32x4*)(Ps + c16 * PROW + 16 * kt + 4 * g) = pv;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (16 * kt + 4 * g + j < N) Ps[c16 * PROW + 16 * kt + 4 * g + j] = pv[j];
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // rows 16 qt .. of the matrix: one contiguous piece of nr * N floats
+    const int nr = min(16, N - 16 * qt);
+    float* dst = out + obase + (int64_t)16 * qt * N;
+    if constexpr (!WIDE) {
+      for (int e = lane; e < nr * N; e += 64) {
+        const int r = e / N, k = e - r * N;
+        store1_nt(dst + e, Ps[r * PROW + k]);
+      }
+    } else {
+      for (int e = lane; e < nr * (N / 4); e += 64) {
+        const int r = e / (N / 4), k = 4 * (e - r * (N / 4));
+        store4_nt(dst + r * N + k, *(const EVT_LDS f32x4*)(Ps + r * PROW + k));
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// fp32 (parity path): block = one (image, window, head), thread = query (49 of 64, 144 of 192)
+template <int W>
+__global__ __launch_bounds__(W == 7 ? 64 : 192) void window_probs_f32_kernel(
+    SwinAttnParams p, const float* __restrict__ table, int trow, float* __restrict__ out) {
+  constexpr int N = W * W, NT = W == 7 ? 64 : 192, TW = 2 * W - 1;
+  constexpr int PR = N % 2 ? N : N + 1;  // row stride of the P tile: odd, so conflict-free
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* Ks = (float*)smem;  // [N][33]
+  float* Ts = Ks + N * 33;   // [TW * TW]
+  float* Ps = Ts + TW * TW;  // [N][PR]
+  const int tid = threadIdx.x;
+  const int64_t pair = blockIdx.x;
+  const int nw = p.nwx * p.nwx;
+  const int h = (int)(pair % p.H);
+  const int64_t bw = pair / p.H;
+  const int win = (int)(bw % nw), b = (int)(bw / nw);
+  const int R = p.R, s0 = p.shift;
+  const int wy = win / p.nwx, wx = win - wy * p.nwx;
+  const bool lr_ = s0 && wy == p.nwx - 1, lc_ = s0 && wx == p.nwx - 1;
+  const int cut = W - s0;
+  const int64_t base = (int64_t)b * R * R;
+  auto row = [&](int t) {
+    const int i = t / W, j = t - W * i;
+    int y = wy * W + s0 + i, x = wx * W + s0 + j;
+    if (y >= R) y -= R;
+    if (x >= R) x -= R;
+    return base + (y * R + x);
+  };
+  const float* qkv = (const float*)p.qkv;
+  for (int e = tid; e < N * 32; e += NT) {
+    const int t = e >> 5, d = e & 31;
+    Ks[t * 33 + d] = qkv[row(t) * p.ldq + p.C + h * 32 + d];
+  }
+  for (int e = tid; e < TW * TW; e += NT) Ts[e] = table[(int64_t)h * trow + e];
+  __syncthreads();
+  if (tid < N) {
+    const int t = tid, qi = t / W, qj = t - W * qi;
+    const int64_t qrow = row(t);
+    float q[32];
+#pragma unroll
+    for (int d = 0; d < 32; ++d) q[d] = qkv[qrow * p.ldq + h * 32 + d];
+    const int cq = (lr_ && qi >= cut ? 1 : 0) | (lc_ && qj >= cut ? 2 : 0);
+    const float* Tq = Ts + (TW * (qi + W - 1) + qj + W - 1);
+    auto score = [&](int k, int ki, int kj) {
+      float a = 0.f;
+#pragma unroll
+      for (int d = 0; d < 32; ++d) a += q[d] * Ks[k * 33 + d];
+      const int ck = (lr_ && ki >= cut ? 1 : 0) | (lc_ && kj >= cut ? 2 : 0);
+      return ck != cq ? -INFINITY : a * p.scale_log2 + Tq[-(TW * ki + kj)];
+    };
+    float mx = -INFINITY;
+#pragma unroll 1
+    for (int ki = 0, k = 0; ki < W; ++ki)
+      for (int kj = 0; kj < W; ++kj, ++k) mx = fmaxf(mx, score(k, ki, kj));
+    float sum = 0.f;
+#pragma unroll 1
+    for (int ki = 0, k = 0; ki < W; ++ki)
+      for (int kj = 0; kj < W; ++kj, ++k) {
+        const float e = exp2f(score(k, ki, kj) - mx);
+        Ps[t * PR + k] = e;
+        sum += e;
+      }
+    const float inv = 1.0f / sum;
+    for (int k = 0; k < N; ++k) Ps[t * PR + k] *= inv;  // the thread's own row
+  }
+  __syncthreads();
+  float* dst = out + pair * N * N;
+  for (int e = tid; e < N * N; e += NT) {
+    const int r = e / N, k = e - r * N;
+    store1_nt(dst + e, Ps[r * PR + k]);
+  }
+}
+
+template <int W>
+constexpr size_t wp_f32_lds() {
+  constexpr int N = W * W, TW = 2 * W - 1;
+  return (size_t)(N * 33 + TW * TW + N * (N % 2 ? N : N + 1)) * sizeof(float);
+}
+
+// the store form of the bf16 w = 12 kernel: 16-B unless EVT_WINDOW_MAPS_STORE=dword asks for the
+// other one (for the measurement)
+bool window_wide_stores() {
+  const char* e = std::getenv("EVT_WINDOW_MAPS_STORE");
+  return !(e && std::strcmp(e, "dword") == 0);
+}
+
+}  // namespace
+
+hipError_t window_probs_launch(int dtype, int w, const SwinAttnParams& p, float* out,
+                               hipStream_t s) {
+  if (p.B <= 0) return hipSuccess;
+  if ((w != 7 && w != 12) || !p.qkv || !p.bias || !out || ((uintptr_t)out & 15) || p.R <= 0 ||
+      p.R % w || p.nwx * w != p.R || p.H <= 0 || p.C != p.H * 32 || p.ldq < 3 * (int64_t)p.C ||
+      p.shift < 0 || p.shift >= w || (p.shift && p.R == w))
+    return hipErrorInvalidValue;
+  // the -inf masks and 2^(s - m) <= 1 need a positive finite scale
+  if (!(p.scale_log2 > 0.f && p.scale_log2 < INFINITY)) return hipErrorInvalidValue;
+  const int64_t pairs = (int64_t)p.B * p.nwx * p.nwx * p.H;
+  if (pairs + 4 >= (int64_t)1 << 31) return hipErrorInvalidValue;
+  int trow = 0;
+  const float* table = rpb_compact_table(p.bias, p.H, w, p.shift, &trow);
+  if (dtype == DT_BF16) {
+    // 16-B fragment loads and per-image 32-bit buffer offsets
+    if (p.ldq % 8 || ((uintptr_t)p.qkv & 15) || (int64_t)p.R * p.R * p.ldq * 2 >= (int64_t)1 << 31)
+      return hipErrorInvalidValue;
+    if (w == 7)
+      hipLaunchKernelGGL((window_probs_bf16_kernel<7, false>), dim3((unsigned)((pairs + 3) / 4)),
+                         dim3(256), 0, s, p, table, trow, out);
+    else if (window_wide_stores())
+      hipLaunchKernelGGL((window_probs_bf16_kernel<12, true>), dim3((unsigned)pairs), dim3(192), 0,
+                         s, p, table, trow, out);
+    else
+      hipLaunchKernelGGL((window_probs_bf16_kernel<12, false>), dim3((unsigned)pairs), dim3(192), 0,
+                         s, p, table, trow, out);
+    return hipGetLastError();
+  }
+  if (dtype != DT_F32) return hipErrorInvalidValue;
+  if (w == 7) {
+    hipLaunchKernelGGL(window_probs_f32_kernel<7>, dim3((unsigned)pairs), dim3(64), wp_f32_lds<7>(),
+                       s, p, table, trow, out);
+  } else {
+    (void)hipFuncSetAttribute((const void*)window_probs_f32_kernel<12>,  // 104644 B of LDS
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)wp_f32_lds<12>());
+    hipLaunchKernelGGL(window_probs_f32_kernel<12>, dim3((unsigned)pairs), dim3(192),
+                       wp_f32_lds<12>(), s, p, table, trow, out);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace evt

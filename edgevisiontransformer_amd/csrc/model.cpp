@@ -233,6 +233,24 @@ int attn_map(evt_model* m, ForwardCall& call, int block, const AttnParams& ap) {
   return EVT_OK;
 }
 
+// The Swin counterpart (evt_forward_window_attention): while ws.qkv holds block `block`'s LN1-folded
+// QKV rows that `ap` describes, the block's window map, if it is the next one asked for
+bool window_attn_wanted(const ForwardCall& call, int block) {
+  const evt_attn_args* a = call.attn;
+  return a && call.attn_next < a->n_maps && a->blocks[call.attn_next] == block;
+}
+
+int window_attn_map(evt_model* m, ForwardCall& call, int block, int w, const SwinAttnParams& ap) {
+  if (!window_attn_wanted(call, block)) return EVT_OK;
+  ProfScope ps(m, EVT_PROF_HEAD, call.s);
+  const double n = (double)w * w, wh = (double)ap.B * ap.nwx * ap.nwx * ap.H;
+  prof_work(m, 2.0 * wh * n * n * 32,  // the scores
+            wh * (2.0 * n * 32 * elem_size(m->dtype) + n * n * 4.0));
+  EVT_HIP(window_probs_launch(m->dtype, w, ap, call.attn->maps[call.attn_next++], call.s),
+          "window attention map");
+  return EVT_OK;
+}
+
 int finish_create(evt_model* m, int rc, evt_model** out) {
   if (rc) {
     std::string keep = g_err;
@@ -668,22 +686,21 @@ int evt_attn_map_shape(const evt_model* m, int block, int* heads, int* tokens) {
   return EVT_OK;
 }
 
-int evt_forward_attention(evt_model* m, const evt_image_args* in, int B,
-                          const evt_features_args* feat, const evt_attn_args* a, void* stream) {
-  ImgAffine aff{};
-  if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and attn must be non-null");
-  EVT_RC(validate_image(m, in, &aff));
-  EVT_RC(attn_family(m));
+// The map list of an attention call on a model of nb blocks (after the image and family checks);
+// cls_ok: EVT_ATTN_CLS is a mode of the call (evt_forward_attention) or not (the window maps)
+static int validate_attn(const evt_model* m, int B, const evt_features_args* feat,
+                         const evt_attn_args* a, int nb, bool cls_ok) {
   if (a->n_maps < 0 || a->n_maps > 64) return fail(EVT_EINVAL, "n_maps must be in [0, 64]");
   if (a->n_maps == 0 && !feat)
     return fail(EVT_EINVAL, "no output requested: n_maps is 0 and feat is NULL");
   if (feat) EVT_RC(validate_features(m, feat, B));
   else EVT_RC(check_batch(m, B));
+  if (!cls_ok && a->queries != EVT_ATTN_ALL)
+    return fail(EVT_EINVAL, "window attention maps: queries must be EVT_ATTN_ALL");
   if (a->queries != EVT_ATTN_CLS && a->queries != EVT_ATTN_ALL)
     return fail(EVT_EINVAL, "queries must be EVT_ATTN_CLS or EVT_ATTN_ALL");
   if (a->n_maps > 0) {
     if (!a->blocks || !a->maps) return fail(EVT_EINVAL, "n_maps > 0 needs the blocks and maps arrays");
-    const int nb = (int)m->layers.size();
     for (int i = 0; i < a->n_maps; ++i) {
       if (a->blocks[i] < 0 || a->blocks[i] >= nb)
         return fail(EVT_EINVAL, "map block " + std::to_string(a->blocks[i]) + " is outside [0, " +
@@ -694,10 +711,61 @@ int evt_forward_attention(evt_model* m, const evt_image_args* in, int B,
       if ((uintptr_t)a->maps[i] & 15) return fail(EVT_EINVAL, "attention maps must be 16-byte aligned");
     }
   }
+  return EVT_OK;
+}
+
+int evt_forward_attention(evt_model* m, const evt_image_args* in, int B,
+                          const evt_features_args* feat, const evt_attn_args* a, void* stream) {
+  ImgAffine aff{};
+  if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and attn must be non-null");
+  EVT_RC(validate_image(m, in, &aff));
+  EVT_RC(attn_family(m));
+  EVT_RC(validate_attn(m, B, feat, a, (int)m->layers.size(), true));
   ForwardCall call = image_call(in, aff, B, feat ? feat->logits : nullptr, stream);
   call.feat = feat;
   call.attn = a;
   // one lane, on this handle's own workspace, whatever its lane count (as a features forward)
+  return forward(m, call, false);
+}
+
+// ---- Swin window attention maps (include/evt_window_attention.h) ----------------------------
+
+static int window_attn_family(const evt_model* m) {
+  if (m->family != FAM_SWIN)
+    return fail(EVT_EINVAL, "window attention maps are Swin's: this model's maps are "
+                            "evt_forward_attention's");
+  return EVT_OK;
+}
+
+int evt_window_attn_map_shape(const evt_model* m, int block, int* windows, int* heads,
+                              int* tokens) {
+  if (!m || !windows || !heads || !tokens) return fail(EVT_EINVAL, "null argument");
+  EVT_RC(window_attn_family(m));
+  int i = block;
+  for (const SwinStage& st : m->stages) {
+    if (i >= 0 && i < (int)st.blocks.size()) {
+      *windows = (st.R / st.w) * (st.R / st.w);
+      *heads = st.H;
+      *tokens = st.w * st.w;
+      return EVT_OK;
+    }
+    i -= (int)st.blocks.size();
+  }
+  return fail(EVT_EINVAL, "block must be in [0, " + std::to_string(model_blocks(m)) + ")");
+}
+
+int evt_forward_window_attention(evt_model* m, const evt_image_args* in, int B,
+                                 const evt_features_args* feat, const evt_attn_args* a,
+                                 void* stream) {
+  ImgAffine aff{};
+  if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and attn must be non-null");
+  EVT_RC(validate_image(m, in, &aff));
+  EVT_RC(window_attn_family(m));
+  EVT_RC(validate_attn(m, B, feat, a, model_blocks(m), false));
+  ForwardCall call = image_call(in, aff, B, feat ? feat->logits : nullptr, stream);
+  call.feat = feat;
+  call.attn = a;
+  // one lane, on this handle's own workspace, whatever its lane count (as evt_forward_attention)
   return forward(m, call, false);
 }
 

@@ -360,6 +360,9 @@ int feat_export(evt_model* m, const void* x, int64_t ldx, int64_t row_step, floa
                 int rows, int D, hipStream_t s);
 int feat_tap(evt_model* m, ForwardCall& call, int block, int64_t ldx, int rows, int D);
 int attn_map(evt_model* m, ForwardCall& call, int block, const AttnParams& ap);
+// evt_forward_window_attention (Swin): whether the call asks for block's map next, and the export
+bool window_attn_wanted(const ForwardCall& call, int block);
+int window_attn_map(evt_model* m, ForwardCall& call, int block, int w, const SwinAttnParams& ap);
 int finish_create(evt_model* m, int rc, evt_model** out);
 int check_batch(const evt_model* m, int B);
 int forward(evt_model* m, ForwardCall& call, bool use_lanes);

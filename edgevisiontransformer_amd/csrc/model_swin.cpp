@@ -238,6 +238,22 @@ int swin_run(evt_model* m, ForwardCall& call) {
       // the fused C = 96 sublayers are window-7 kernels; a window-12 stage takes the GEMM path
       const bool fuse96 = dt == DT_BF16 && C == 96 && st.H == 3 && st.w == 7 && gemm_auto();
       const double slot_rows = (double)rows * stats_slots(C) * 8;
+      DenseCall qc;  // LN1-folded QKV (+ bias): ws.x -> ws.qkv
+      qc.flags = EPI_LNIN | EPI_BIAS;
+      qc.A = m->ws.x; qc.lda = Cst; qc.C = m->ws.qkv; qc.ldc = 3 * C; qc.M = rows; qc.N = 3 * C;
+      qc.stats_in = m->ws.sx; qc.ln_width = C;
+      const SwinAttnParams ap{m->ws.qkv, 3 * C, m->ws.o, Cst, bl.bias, B, st.R, st.R / st.w, C, st.H,
+                              bl.shift, scale_log2};
+      if (fuse96 && window_attn_wanted(call, block)) {
+        // The fused sublayer keeps q and k on chip: for a requested block only, the general
+        // path's QKV GEMM into ws.qkv (ws.x / ws.sx stay as the sublayer reads them) and the map
+        // of its q / k; the sublayer below runs unchanged (evt_window_attention.h)
+        {
+          ProfScope ps(m, EVT_PROF_HEAD, s);
+          EVT_RC(dense(m, bl.qkv, qc, s));
+        }
+        EVT_RC(window_attn_map(m, call, block, st.w, ap));
+      }
       if (fuse96) {  // stage-1 attention sublayer fused (swin.hip, swin_attn96_kernel)
         ProfScope ps(m, EVT_PROF_ATTN_SUBLAYER, s);
         prof_work(m, 2.0 * rows * C * 4 * C + 4.0 * rows * 49 * C,
@@ -250,20 +266,15 @@ int swin_run(evt_model* m, ForwardCall& call) {
       if (!fuse96) {  // LN1-folded QKV (+ bias)
         {
           ProfScope ps(m, EVT_PROF_QKV, s);
-          DenseCall c;
-          c.flags = EPI_LNIN | EPI_BIAS;
-          c.A = m->ws.x; c.lda = Cst; c.C = m->ws.qkv; c.ldc = 3 * C; c.M = rows; c.N = 3 * C;
-          c.stats_in = m->ws.sx; c.ln_width = C;
-          EVT_RC(dense(m, bl.qkv, c, s));
+          EVT_RC(dense(m, bl.qkv, qc, s));
         }
         {
           ProfScope ps(m, EVT_PROF_ATTENTION, s);
           prof_work(m, 4.0 * rows * st.w * st.w * C, 4.0 * rows * C * es);  // w^2 keys per query
-          SwinAttnParams ap{m->ws.qkv, 3 * C, m->ws.o, Cst, bl.bias, B, st.R, st.R / st.w, C, st.H,
-                            bl.shift, scale_log2};
           EVT_HIP(st.w == 12 ? window12_attn_launch(dt, ap, s) : window_attn_launch(dt, ap, s),
                   "window attention");
         }
+        EVT_RC(window_attn_map(m, call, block, st.w, ap));  // ws.qkv still holds the block
         ProfScope ps(m, EVT_PROF_OUT_PROJ, s);
         DenseCall pc;  // proj + bias + residual x -> xm (+ stats)
         pc.flags = EPI_BIAS | EPI_RESID | EPI_STATS;

@@ -371,6 +371,37 @@ int evt_attention_probs(int dtype, const void* qkv, int64_t ldq, int64_t sb, int
   return EVT_OK;
 }
 
+int evt_window_attention_probs(int dtype, const void* qkv, int64_t ldq, const float* rpb, int B,
+                               int R, int window, int C, int H, int shift, float* out,
+                               void* stream) {
+  if (dtype != EVT_DTYPE_F32 && dtype != EVT_DTYPE_BF16)
+    return fail(EVT_EINVAL, "window_attention_probs: dtype must be EVT_DTYPE_F32 or EVT_DTYPE_BF16");
+  if (!qkv || !rpb || !out) return fail(EVT_EINVAL, "window_attention_probs: null pointer");
+  if (window != 7 && window != 12)
+    return fail(EVT_EINVAL, "window_attention_probs: window must be 7 or 12");
+  if (B < 0 || R <= 0 || R % window || H <= 0 || C != 32 * H || shift < 0 || shift >= window ||
+      (shift && R == window) || ldq < 3 * (int64_t)C)
+    return fail(EVT_EINVAL, "window_attention_probs: bad shape (R % window == 0, C == 32*H, "
+                            "0 <= shift < window, no shift with a single window, ldq >= 3*C)");
+  if ((uintptr_t)out & 15)
+    return fail(EVT_EINVAL, "window_attention_probs: out must be 16-byte aligned");
+  if (dtype == EVT_DTYPE_BF16 && (ldq % 8 || ((uintptr_t)qkv & 15)))
+    return fail(EVT_EINVAL, "window_attention_probs: bf16 qkv rows must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  float* tables = nullptr;
+  EVT_HIP(hipMallocAsync((void**)&tables, rpb_table_floats(H, window, shift) * sizeof(float), s),
+          "malloc bias");
+  hipError_t e = rpb_dense_launch(rpb, H, window, shift, tables, s);
+  if (e == hipSuccess) {
+    SwinAttnParams ap{qkv, ldq, nullptr, 0, tables, B, R, R / window, C, H, shift,
+                      0.17677669529663687f * 1.4426950408889634f};
+    e = window_probs_launch(dtype, window, ap, out, s);
+  }
+  (void)hipFreeAsync(tables, s);
+  EVT_HIP(e, "window_attention_probs");
+  return EVT_OK;
+}
+
 int evt_classify(const float* logits, int64_t ldl, int B, int C, const evt_classify_args* a,
                  void* stream) {
   if (!logits) return fail(EVT_EINVAL, "classify: logits are NULL");

@@ -1672,6 +1672,11 @@ size_t rpb_table_floats(int H, int w, int shift) {
   return (size_t)(shift ? 4 : 1) * H * w * w * 64 + (size_t)H * RPB_CROW;
 }
 
+const float* rpb_compact_table(const float* tables, int H, int w, int shift, int* row) {
+  *row = w == 12 ? RPB12_CROW : RPB_CROW;
+  return w == 12 ? tables : rpb_compact(tables, H, shift);
+}
+
 hipError_t window_attn_launch(int dtype, const SwinAttnParams& p, hipStream_t s) {
   if (p.B <= 0) return hipSuccess;
   if (p.R % 7 || p.nwx * 7 != p.R || p.C != p.H * 32 || p.ldo < p.C || p.shift < 0 ||

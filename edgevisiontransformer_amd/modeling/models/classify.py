@@ -24,7 +24,7 @@ import torch
 
 from ... import _lib
 from ...images import Uint8Images
-from .attention_maps import AttentionMaps
+from .window_attention_maps import WindowAttentionMaps
 
 VALUES = {"prob": _lib.CLASSIFY_PROB, "logit": _lib.CLASSIFY_LOGIT}
 MAX_CLASSES = 1 << 20
@@ -84,7 +84,7 @@ def classify_reference(logits, k: int, labels=None) -> Dict[str, np.ndarray]:
     return out
 
 
-class Classification(AttentionMaps):
+class Classification(WindowAttentionMaps):
     """What ViT, T2T_ViT and SwinTransformer derive from: the classification outputs on top of the
     attention maps and feature outputs. Needs nothing of the model class but `cfg.num_classes`."""
 

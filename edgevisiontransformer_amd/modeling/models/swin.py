@@ -101,6 +101,12 @@ class SwinTransformer(Classification):
                                                   for i in range(c.num_stages)
                                                   for _ in range(c.depths[i])]
 
+    # -- window attention maps (window_attention_maps.py) --------------------------------------
+    def _window_geometry(self):
+        c = self.cfg
+        return [(c.res(i), c.window(i), c.shift(i, j), c.num_heads[i])
+                for i in range(c.num_stages) for j in range(c.depths[i])]
+
     def _image_dims(self):
         c = self.cfg
         return c.in_chans, c.image_size, c.image_size

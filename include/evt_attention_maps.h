@@ -21,8 +21,8 @@
  * token-major QKV layout (evt_model_qkv_layout) give bitwise equal maps.
  *
  * Families: ViT (EVT_VIT_REFERENCE and EVT_VIT_STANDARD, pruned or not) and T2T-ViT (its encoder
- * blocks). Swin is EVT_EINVAL: its windowed, biased attention is a different object. An
- * EVT_DTYPE_MX8 handle is EVT_EINVAL, as for taps.
+ * blocks). Swin is EVT_EINVAL: its windowed, biased attention is a different object, with its own
+ * entry points (evt_window_attention.h). An EVT_DTYPE_MX8 handle is EVT_EINVAL, as for taps.
  *
  * The kernels that produce the logits (and pooled / tokens / taps through `feat`) are the ones
  * evt_*_forward / evt_forward_features launch, in the same order on the same operands: those
