@@ -237,6 +237,14 @@ WORKSPACE_SIGNATURES = {
     "evt_model_workspace_bytes": (_I, [_P, ctypes.POINTER(ctypes.c_size_t)]),
 }
 
+# the entry points of include/evt_performer.h (evt.h includes it; bound like SIGNATURES):
+# evt_performer's arguments + (kqv_perm, tstats) before the stream
+PERFORMER_SIGNATURES = {
+    "evt_performer_ex": (_I, [_I, _P, _I64, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                              _I64, _I, _P, _P]),
+    "evt_unfold_stats": (_I, [_P, _I, _I, _P, _I, _P]),
+}
+
 
 class evt_classify_args(ctypes.Structure):
     _fields_ = [("k", ctypes.c_int32), ("values", ctypes.c_int32),
@@ -278,7 +286,8 @@ def load_library() -> ctypes.CDLL:
                                       **IMAGE_SIGNATURES, **PREPROCESS_SIGNATURES,
                                       **ATTENTION_SIGNATURES, **WINDOW_ATTENTION_SIGNATURES,
                                       **TAIL_SIGNATURES,
-                                      **CLASSIFY_SIGNATURES, **WORKSPACE_SIGNATURES}.items():
+                                      **CLASSIFY_SIGNATURES, **WORKSPACE_SIGNATURES,
+                                      **PERFORMER_SIGNATURES}.items():
                 if lenient and not hasattr(lib, name):
                     continue
                 fn = getattr(lib, name)

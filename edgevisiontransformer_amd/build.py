@@ -29,7 +29,8 @@ HEADERS = ["common.h", "evt_internal.h", "model.h", os.path.join("..", "..", "in
            os.path.join("..", "..", "include", "evt_window_attention.h"),
            os.path.join("..", "..", "include", "evt_tail.h"),
            os.path.join("..", "..", "include", "evt_classify.h"),
-           os.path.join("..", "..", "include", "evt_workspace.h")]
+           os.path.join("..", "..", "include", "evt_workspace.h"),
+           os.path.join("..", "..", "include", "evt_performer.h")]
 ARCH = os.environ.get("EVT_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result",
          "-ffp-contract=on"]  # contraction only within one source expression: same result on

@@ -310,6 +310,33 @@ int evt_performer(int dtype, const void* kqv, int64_t ldq, int B, int T, const f
   return EVT_OK;
 }
 
+// include/evt_performer.h: evt_performer's checks, then the launcher with the model's two extras
+int evt_performer_ex(int dtype, const void* kqv, int64_t ldq, int B, int T, const float* w,
+                     const float* out_w, const float* out_b, const float* ln2_g,
+                     const float* ln2_b, const float* fc1_w, const float* fc1_b,
+                     const float* fc2_w, const float* fc2_b, float* part, void* out, int64_t ldo,
+                     int kqv_perm, float* tstats, void* stream) {
+  if (!kqv || !w || !out_w || !out_b || !ln2_g || !ln2_b || !fc1_w || !fc1_b || !fc2_w ||
+      !fc2_b || !part || !out || B < 0 || T <= 0 || ldq < 192 || ldo < 64 || ldq % 4 || ldo % 4)
+    return fail(EVT_EINVAL, "performer_ex: bad arguments (ldq >= 192, ldo >= 64, multiples of 4)");
+  if ((kqv_perm || tstats) && dtype != EVT_DTYPE_BF16)
+    return fail(EVT_EINVAL, "performer_ex: kqv_perm and tstats are bf16 only");
+  if (kqv_perm && (ldq % 8 || ((uintptr_t)kqv & 15)))
+    return fail(EVT_EINVAL, "performer_ex: kqv_perm needs ldq % 8 == 0 and a 16-B aligned kqv");
+  PerformerWeights pw{w, out_w, out_b, ln2_g, ln2_b, fc1_w, fc1_b, fc2_w, fc2_b};
+  EVT_HIP(performer_launch(dtype, kqv, ldq, B, T, pw, part, out, ldo, (hipStream_t)stream, tstats,
+                           kqv_perm != 0),
+          "performer_ex");
+  return EVT_OK;
+}
+
+int evt_unfold_stats(const float* tstats, int B, int R, float* dst, int nslots, void* stream) {
+  if (!tstats || !dst || B < 0 || R <= 0 || nslots <= 0)
+    return fail(EVT_EINVAL, "unfold_stats: bad arguments (tstats, dst non-null, R > 0, nslots > 0)");
+  EVT_HIP(unfold_stats_launch(tstats, B, R, dst, nslots, (hipStream_t)stream), "unfold_stats");
+  return EVT_OK;
+}
+
 int evt_window_attention(int dtype, const void* qkv, int64_t ldq, void* out, int64_t ldo,
                          const float* rpb, int B, int R, int C, int H, int shift, void* stream) {
   if (!qkv || !out || !rpb) return fail(EVT_EINVAL, "null pointer");

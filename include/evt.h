@@ -523,5 +523,6 @@ int evt_model_qkv_layout(const evt_model* m, int* headmajor_layers);
 #include "evt_classify.h"  /* evt_classify, evt_forward_classify */
 #include "evt_tail.h"      /* evt_model_tail_mode (the encoder's CLS tail) */
 #include "evt_workspace.h" /* evt_model_workspace_bytes */
+#include "evt_performer.h" /* evt_performer_ex, evt_unfold_stats (diagnostic) */
 
 #endif /* EVT_H_ */

@@ -109,6 +109,31 @@ def test_t2t_host_validation(lib):
     assert lib.evt_performer_scratch(3, 784) == 3 * (4 + 1) * (64 * 32 + 32)
 
 
+def test_performer_diagnostics_host_validation(lib):
+    """include/evt_performer.h: evt_performer's checks, and the two extras are bf16 only."""
+    from edgevisiontransformer_amd import _lib
+    nul = [None] * 10   # w .. fc2_b, part
+    assert lib.evt_performer_ex(1, None, 192, 1, 16, *nul, None, 64, 0, None, None) == _lib.EVT_EINVAL
+    buf = (ctypes.c_float * 64)()
+    arr = ctypes.cast(buf, ctypes.c_void_p)
+    ok = [arr] * 10
+    for ldq, ldo, T in ((188, 64, 16), (192, 60, 16), (194, 64, 16), (192, 66, 16), (192, 64, 0)):
+        assert lib.evt_performer_ex(1, arr, ldq, 1, T, *ok, arr, ldo, 0, None, None) == _lib.EVT_EINVAL
+        assert lib.evt_performer(1, arr, ldq, 1, T, *ok, arr, ldo, None) == _lib.EVT_EINVAL
+    # f32 with either extra; the permuted path with ldq % 8 != 0 or a kqv off 16 bytes
+    assert lib.evt_performer_ex(0, arr, 192, 1, 16, *ok, arr, 64, 1, None, None) == _lib.EVT_EINVAL
+    assert b"bf16 only" in lib.evt_last_error()
+    assert lib.evt_performer_ex(0, arr, 192, 1, 16, *ok, arr, 64, 0, arr, None) == _lib.EVT_EINVAL
+    assert lib.evt_performer_ex(1, arr, 196, 1, 16, *ok, arr, 64, 1, None, None) == _lib.EVT_EINVAL
+    assert b"ldq % 8" in lib.evt_last_error()
+    off = ctypes.c_void_p(arr.value + (8 if arr.value % 16 == 0 else 0))   # 8 mod 16
+    assert lib.evt_performer_ex(1, off, 192, 1, 16, *ok, arr, 64, 1, None, None) == _lib.EVT_EINVAL
+    assert lib.evt_unfold_stats(None, 1, 4, None, 2, None) == _lib.EVT_EINVAL
+    assert lib.evt_unfold_stats(arr, 1, 0, arr, 2, None) == _lib.EVT_EINVAL
+    assert lib.evt_unfold_stats(arr, 1, 4, arr, 0, None) == _lib.EVT_EINVAL
+    assert lib.evt_unfold_stats(arr, -1, 4, arr, 2, None) == _lib.EVT_EINVAL
+
+
 def test_swin_host_validation(lib):
     from edgevisiontransformer_amd import _lib
     from edgevisiontransformer_amd.modeling.models.swin import swin_config_from_name
