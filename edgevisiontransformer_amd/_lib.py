@@ -278,7 +278,7 @@ def load_library() -> ctypes.CDLL:
                     f"{LIB_PATH} not found: build it with `python -m edgevisiontransformer_amd.build`"
                     " (hipcc --offload-arch=gfx950). There is no CPU fallback.")
             lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-            # an EVT_LIB override (a lab build, or an older build for an A/B measurement) may lack
+            # an EVT_LIB override (an older build, for an A/B measurement) may lack
             # entry points added since: those stay unbound there; the in-tree library must export
             # every one (tests/test_capi.py)
             lenient = "EVT_LIB" in os.environ

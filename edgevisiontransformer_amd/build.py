@@ -12,15 +12,16 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-# EVT_LAB=1: the diagnostic build (GEMM ablation / timeline variants, qkv_attn ablations) into
-# libevt_hip_lab.so (load it with EVT_LIB=<path>); the product library never contains them
-LAB = os.environ.get("EVT_LAB", "") not in ("", "0")
-LIB = os.path.join(HERE, "libevt_hip_lab.so" if LAB else "libevt_hip.so")
-OBJ = os.path.join(HERE, "build_obj_lab" if LAB else "build_obj")
+LIB = os.path.join(HERE, "libevt_hip.so")
+OBJ = os.path.join(HERE, "build_obj")
 SOURCES = ["gemm.hip", "attention.hip", "norm.hip", "t2t.hip", "swin.hip", "mx8.hip",
            "features.hip", "preprocess.hip", "attn_maps.hip", "model.cpp", "encoder.cpp",
            "model_vit.cpp", "model_t2t.cpp", "model_swin.cpp", "ops.cpp", "resize_plan.cpp"]
-HEADERS = ["common.h", "evt_internal.h", "model.h", os.path.join("..", "..", "include", "evt.h"),
+# the GEMM kernels, one header per kernel, all included by gemm.hip (one translation unit)
+GEMM_HEADERS = ["gemm_epi.h", "gemm_nt.h", "gemm_big8.h", "gemm_big.h", "gemm_pers.h",
+                "gemm_p384.h", "gemm_sk.h"]
+HEADERS = GEMM_HEADERS + [
+           "common.h", "evt_internal.h", "model.h", os.path.join("..", "..", "include", "evt.h"),
            os.path.join("..", "..", "include", "evt_patchify.h"),
            os.path.join("..", "..", "include", "evt_features.h"),
            os.path.join("..", "..", "include", "evt_image.h"),
@@ -35,11 +36,6 @@ ARCH = os.environ.get("EVT_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result",
          "-ffp-contract=on"]  # contraction only within one source expression: same result on
 #                                every code path (interior / edge tiles) -> batch-independent bits
-if LAB:
-    FLAGS += ["-DEVT_GEMM_LAB"] + ([f"-DEVT_QA_DBG={os.environ['EVT_QA_DBG']}"]
-                                   if os.environ.get("EVT_QA_DBG") else [])
-    FLAGS += os.environ.get("EVT_LAB_DEFS", "").split()  # e.g. -DEVT_MFMA_PRIO=0 (lab A/B)
-
 
 # MFMA results straight into VGPRs: with the default AGPR form the compiler parks the small
 # attention / window-attention / performer accumulators in AGPRs and copies every element back
@@ -67,7 +63,7 @@ def _mtime(p: str) -> float:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
-    # a change of compile flags (EVT_LAB_DEFS, EVT_ARCH, ...) rebuilds every object
+    # a change of compile flags (EVT_ARCH, ...) rebuilds every object
     stamp = os.path.join(OBJ, "flags.txt")
     want = repr((FLAGS, PER_FILE_FLAGS))
     if not os.path.exists(stamp) or open(stamp).read() != want:

@@ -342,7 +342,7 @@ inline bool gemm_auto() {
   const int v = gemm_variant();
   return v == 0 || v == 30 || v == 31;
 }
-bool gemm_variant_supported(int v);  // compiled into this build (lab variants: EVT_GEMM_LAB)
+bool gemm_variant_supported(int v);  // one of the public variant numbers (gemm.hip)
 
 // ---- MXFP8 (mx8.hip): e4m3fn elements, e8m0 scale per 32 K, scales S[K/128][ld] dwords ----
 struct Mx8GemmParams {

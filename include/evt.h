@@ -498,9 +498,7 @@ int evt_attention_mx8(const void* qkv, int64_t ldq, void* q8, int64_t ldq8, uint
  * tile-persistent, 16 = stream-K persistent where it applies, 30 = the 128 x 384 persistent tiles
  * wherever the width allows (multiple of 384), 31 = automatic without them, 36 = automatic with the
  * persistent grids at one block per CU (no balancing of 2-4-round launches to fewer blocks: the
- * same tiles and arithmetic, bitwise the same outputs). Builds with
- * EVT_LAB=1 (-DEVT_GEMM_LAB) also accept the ablation / timeline variants 10, 11, 13, 15, 17-25,
- * 106, 108; other values return EVT_EINVAL. */
+ * same tiles and arithmetic, bitwise the same outputs). Other values return EVT_EINVAL. */
 int evt_set_gemm_variant(int variant);
 
 /* Number of encoder layers whose QKV GEMM stored its output head-major ([B][H][q | k | v][T][64],

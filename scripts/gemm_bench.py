@@ -1,7 +1,6 @@
 """GEMM microbenchmark on the GPU: model-shaped bf16 GEMMs, 128x128 vs 256x256 tile kernels,
-interleaved rounds in one process (HIP events), plus a cross-check of the two variants.
-Ablation / A-B variants (10, 11, 13, 15, 17-25, 106, 108) exist only in the lab build:
-  EVT_LAB=1 python -m edgevisiontransformer_amd.build && EVT_LIB=edgevisiontransformer_amd/libevt_hip_lab.so python scripts/gemm_bench.py ..."""
+interleaved rounds in one process (HIP events), plus a cross-check of the variants.
+    python scripts/gemm_bench.py [M [variants, e.g. 1,2,9]]   (evt_set_gemm_variant numbers)"""
 import ctypes
 import json
 import sys
@@ -16,7 +15,7 @@ _lib.ensure_device(0)
 S = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)  # noqa: E731
 P = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)  # noqa: E731
 M = int(sys.argv[1]) if len(sys.argv) > 1 else 512 * 197
-VARS = [int(v) for v in sys.argv[2].split(',')] if len(sys.argv) > 2 else [1, 2, 3]
+VARS = [int(v) for v in sys.argv[2].split(',')] if len(sys.argv) > 2 else [1, 2, 9]
 shapes = {"qkv": (768, 2304, 0), "out": (768, 768, 21), "fc1": (768, 3072, 3), "fc2": (3072, 768, 21),
           "nt3072": (3072, 768, 0), "nt768x3072": (768, 3072, 0)}
 import os

@@ -1,6 +1,6 @@
 """Round-6 probe driver: the 4-wave software-pipelined main loop (scripts/probe/gemm4w.hip) against
-the product persistent GEMM (evt_dense, flags 0 = plain bf16 stores; lab variant 17 = no epilogue
-when EVT_LIB points at a lab build) on the same operands, HIP events, median of 5 x 10 launches.
+the product persistent GEMM (evt_dense, flags 0 = plain bf16 stores) on the same operands, HIP
+events, median of 5 x 10 launches.
     python scripts/probe/gemm4w_bench.py [MxKxN ...]"""
 import ctypes
 import json
@@ -56,18 +56,13 @@ for sh in shapes:
             ms = timeit(lambda: probe.gemm4w_launch(P(A), P(W), P(C), M, N, K, var, store, S()))
             out[f"probe_v{var}_store{store}"] = {"ms": round(ms, 4), "tflops": round(fl / ms / 1e9, 1)}
     # the product persistent kernel (W packed [Npad][Kpad] = W itself here: N % 256 == 0)
-    for v in [0] + ([17] if os.environ.get("EVT_LIB") else []):
-        if lib.evt_set_gemm_variant(v) != 0:
-            continue
-        a = _lib.evt_dense_args()
-        a.flags, a.A, a.lda, a.Wp, a.Kpad, a.Npad = 0, A.data_ptr(), K, W.data_ptr(), K, N
-        a.C, a.ldc, a.M, a.N = Cp.data_ptr(), N, M, N
-        ms = timeit(lambda: _lib.check(lib.evt_dense(1, ctypes.byref(a), S())))
-        out[f"product_v{v}"] = {"ms": round(ms, 4), "tflops": round(fl / ms / 1e9, 1)}
-        if v == 0:
-            torch.cuda.synchronize()
-            out["probe_vs_product_maxdiff"] = float((C.float() - Cp.float()).abs().max())
-    lib.evt_set_gemm_variant(0)
+    a = _lib.evt_dense_args()
+    a.flags, a.A, a.lda, a.Wp, a.Kpad, a.Npad = 0, A.data_ptr(), K, W.data_ptr(), K, N
+    a.C, a.ldc, a.M, a.N = Cp.data_ptr(), N, M, N
+    ms = timeit(lambda: _lib.check(lib.evt_dense(1, ctypes.byref(a), S())))
+    out["product_v0"] = {"ms": round(ms, 4), "tflops": round(fl / ms / 1e9, 1)}
+    torch.cuda.synchronize()
+    out["probe_vs_product_maxdiff"] = float((C.float() - Cp.float()).abs().max())
     print(json.dumps(out), flush=True)
     del A, W, C, Cp
     torch.cuda.empty_cache()

@@ -1,6 +1,7 @@
 """Thin test helpers that call the op-level C ABI (include/evt.h) on torch device tensors."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import torch
@@ -8,6 +9,19 @@ import torch
 from edgevisiontransformer_amd import _lib
 
 TDT = {"f32": torch.float32, "bf16": torch.bfloat16}
+
+
+@contextlib.contextmanager
+def gemm_variant(v):
+    """Run the body's GEMM launches under evt_set_gemm_variant(v), which must be accepted; the
+    launches are finished and the automatic selection (0) is back when the block ends."""
+    lib = _lib.load_library()
+    assert lib.evt_set_gemm_variant(v) == _lib.EVT_OK, lib.evt_last_error()
+    try:
+        yield
+        torch.cuda.synchronize()
+    finally:
+        lib.evt_set_gemm_variant(0)
 
 
 def _p(t):

@@ -60,9 +60,13 @@ def test_host_validation_codes(lib):
     out_h = ctypes.c_void_p()
     assert lib.evt_vit_create(ctypes.byref(d), None, 0, None, ctypes.byref(out_h)) == _lib.EVT_EINVAL
     assert lib.evt_model_destroy(None) == 0
-    assert lib.evt_set_gemm_variant(20) == _lib.EVT_EINVAL  # lab-only ablation (product build)
-    assert b"lab builds" in lib.evt_last_error()
+    assert lib.evt_set_gemm_variant(20) == _lib.EVT_EINVAL  # a former ablation variant
+    msg = lib.evt_last_error()
+    assert b"0, 1, 2, 6, 8, 9, 16, 30, 31 or 36" in msg and b"lab" not in msg  # the supported set
     for v in (32, 33, 34, 35):  # removed in round 5 (measured-slower lab variants)
+        assert lib.evt_set_gemm_variant(v) == _lib.EVT_EINVAL
+    # the ablation / timeline / A-B numbers of the former diagnostic build
+    for v in (10, 11, 13, 15, 17, 18, 19, 21, 22, 23, 24, 25, 106, 108):
         assert lib.evt_set_gemm_variant(v) == _lib.EVT_EINVAL
     for v in (1, 2, 6, 8, 9, 16, 30, 31, 36, 0):
         assert lib.evt_set_gemm_variant(v) == 0

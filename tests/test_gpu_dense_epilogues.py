@@ -8,7 +8,6 @@ point, and ldq / ldo / scale of evt_attention(_hd).
 Every reference is fp64 torch on the operands as the kernel sees them: activations rounded to the
 kernel dtype, LN-folded weights as evt_pack_weight rounds them (fp32 W * gamma, then the dtype).
 f32 has one GEMM kernel (evt_set_gemm_variant selects among the bf16 ones), so f32 cases run once."""
-import contextlib
 import functools
 import math
 
@@ -36,17 +35,6 @@ STATS_TOL = dict(rtol=1e-4, atol=1e-2)
 def _dv(variants):
     """(dtype, variant) pairs: every bf16 kernel variant, the one f32 kernel."""
     return [("bf16", v) for v in variants] + [("f32", 0)]
-
-
-@contextlib.contextmanager
-def _variant(v):
-    lib = _lib.load_library()
-    assert lib.evt_set_gemm_variant(v) == _lib.EVT_OK
-    try:
-        yield
-        torch.cuda.synchronize()
-    finally:
-        lib.evt_set_gemm_variant(0)
 
 
 def _gelu_erf(x):
@@ -131,7 +119,7 @@ def _run_lnin(gpu, dtype, variant, flags, M, K, N, kind="plain", eps=1e-5, stats
     xq, g, be, W, bias = _lnin_host(dtype, M, K, N, kind)
     wp, kpad, npad, colsum, cvec = _lnin_weights(gpu, dtype, g, be, W, bias)
     A = _act_rows(gpu, dtype, xq, kpad)
-    with _variant(variant):
+    with _ops.gemm_variant(variant):
         C = _ops.dense(dtype, flags, A, wp, kpad, npad, M, N, bias=cvec, colsum=colsum,
                        stats_in=stats(xq).to(gpu), stats_out=stats_out, ln_width=K, ln_eps=eps)
     return C.double().cpu()
@@ -191,7 +179,7 @@ def test_set_49_classifier_on_cls_rows(gpu, dtype, variant, B, T, D, N):
     st = _stats32(xq)
     st[torch.arange(B * T) % T != 0] = float("nan")
     x = xq.to(_ops.TDT[dtype]).to(gpu)
-    with _variant(variant):
+    with _ops.gemm_variant(variant):
         C = _ops.dense(dtype, F49, x.view(B, T * D)[:, :D], wp, kpad, npad, B, N, bias=cvec,
                        colsum=colsum, stats_in=st.to(gpu), ln_width=D, stats_step=T)
     assert C.dtype == torch.float32
@@ -230,7 +218,7 @@ def _run_resln(gpu, dtype, variant, M, K, D, kind="plain", eps=1e-5, stats=_stat
     pa, pr, pc = pitch or (0, 0, 0)
     C = torch.full((M, D + pc), 7.0, dtype=_ops.TDT[dtype], device=gpu)
     st = torch.full((M, _nslots(D), 2), float("nan"), device=gpu)
-    with _variant(variant):
+    with _ops.gemm_variant(variant):
         _ops.dense(dtype, F197, _padded(gpu, Aq, dtype, pa, 1e4), wp, kpad, npad, M, D, ldc=D + pc,
                    C=C, bias=bias, resid=_padded(gpu, xq, dtype, pr, 1e4),
                    rstats=stats(xq).to(gpu), rgamma=g.float().to(gpu), rbeta=be.float().to(gpu),
@@ -265,7 +253,7 @@ def test_padded_pitches_lnin(gpu, dtype, variant, ldc_pad):
     wp, kpad, npad, colsum, cvec = _lnin_weights(gpu, dtype, g, be, W, bias)
     assert kpad == K
     C = torch.full((M, N + ldc_pad), 7.0, dtype=_ops.TDT[dtype], device=gpu)
-    with _variant(variant):
+    with _ops.gemm_variant(variant):
         _ops.dense(dtype, F33, _padded(gpu, xq, dtype, 64, 1e4), wp, kpad, npad, M, N,
                    ldc=N + ldc_pad, C=C, bias=cvec, colsum=colsum, stats_in=_stats32(xq).to(gpu),
                    ln_width=K)
@@ -307,7 +295,7 @@ def test_chained_stats(gpu, dtype, variant, M, D):
     wp, kpad2, npad2, colsum, cvec = _lnin_weights(gpu, dtype, g, be, W, bias)
     assert kpad == D and kpad2 == D
     st = torch.full((M, _nslots(D), 2), float("nan"), device=gpu)
-    with _variant(variant):
+    with _ops.gemm_variant(variant):
         X = _ops.dense(dtype, F197, Aq.to(_ops.TDT[dtype]).to(gpu), wp1, kpad, npad, M, D,
                        bias=bias1, resid=xq.to(_ops.TDT[dtype]).to(gpu),
                        rstats=_stats32(xq).to(gpu), rgamma=g1.float().to(gpu),

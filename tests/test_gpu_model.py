@@ -72,17 +72,12 @@ def test_batch_independence(gpu, dtype):
     re-plan), and at 37 images under the automatic selection (which may pick 256 x 256 tiles for
     the batch and 128 x 128 for one image) the rows follow their images through a roll of the
     batch bit for bit."""
-    from edgevisiontransformer_amd import _lib
+    from tests._ops import gemm_variant
     m = get_deit_tiny(dtype=dtype, seed=3, device=gpu)
     img = torch.from_numpy(make_images(37, seed=9)).to(gpu)
-    lib = _lib.load_library()
-    lib.evt_set_gemm_variant(1)  # every GEMM on the 128 x 128 kernel, whatever the batch
-    try:
+    with gemm_variant(1):  # every GEMM on the 128 x 128 kernel, whatever the batch
         full = m(img)
         parts = torch.cat([m(img[i:i + 1]) for i in (0, 17, 36)])
-        torch.cuda.synchronize()
-    finally:
-        lib.evt_set_gemm_variant(0)
     assert torch.equal(full[[0, 17, 36]], parts)
     auto = m(img)
     rolled = m(torch.roll(img, 11, 0))
@@ -139,23 +134,18 @@ def test_grid_balance_bitwise(gpu, which, batch):
     (launch_pers, round 6): only the tile -> block assignment changes, so the logits equal those
     of one block per CU (evt_set_gemm_variant 36) bit for bit. DeiT-base at 64 images: FC1 600
     tiles on 200 blocks, QKV 450 on 232; T2T-ViT-14 at 128 images: QKV / FC1 495 tiles on 248."""
-    from edgevisiontransformer_amd import _lib
     from edgevisiontransformer_amd.modeling.models import t2t_vit, vit
+    from tests._ops import gemm_variant
     if which == "deit_base":
         m = vit.get_deit_base(dtype="bf16", seed=3, device=gpu)
         img = torch.from_numpy(make_images(batch, seed=31)).to(gpu)
     else:
         m = t2t_vit.get_t2t_vit_14(dtype="bf16", seed=3, device=gpu)
         img = torch.from_numpy(make_images(batch, seed=31, layout="NHWC")).to(gpu)
-    lib = _lib.load_library()
     auto = m(img)
     torch.cuda.synchronize()
-    lib.evt_set_gemm_variant(36)
-    try:
+    with gemm_variant(36):
         flat = m(img)
-        torch.cuda.synchronize()
-    finally:
-        lib.evt_set_gemm_variant(0)
     assert torch.isfinite(auto).all()
     assert torch.equal(auto, flat)
 

@@ -35,14 +35,11 @@ def _gelu(x):
                                    (1000, 576, 192), (64, 64, 1000), (257, 3072, 768),
                                    (300, 128, 200)])
 @pytest.mark.parametrize("flags", [0, 3, 21, 17])
-@pytest.mark.parametrize("variant", [1, 2, 8, 9, 10, 0])
+@pytest.mark.parametrize("variant", [1, 2, 8, 9, 0])
 def test_dense(gpu, dtype, M, K, N, flags, variant):
     """variant 1: 128x128-tile kernel; 2: 256x256-tile kernel (bf16 only; f32 ignores it)."""
-    _lib.load_library().evt_set_gemm_variant(variant)
-    try:
+    with _ops.gemm_variant(variant):
         _dense_case(gpu, dtype, M, K, N, flags)
-    finally:
-        _lib.load_library().evt_set_gemm_variant(0)
 
 
 def _dense_case(gpu, dtype, M, K, N, flags):
@@ -104,12 +101,8 @@ def test_dense_huge_leading_dims(gpu, variant, resid):
     else:
         flags = _lib.EPI_BIAS | _lib.EPI_GELU
         C = torch.zeros((M, LD), dtype=torch.bfloat16, device=gpu)
-    _lib.load_library().evt_set_gemm_variant(variant)
-    try:
+    with _ops.gemm_variant(variant):
         _ops.dense("bf16", flags, A, wp, kpad, npad, M, N, ldc=LD, bias=bias, C=C, **kw)
-        torch.cuda.synchronize()
-    finally:
-        _lib.load_library().evt_set_gemm_variant(0)
     ref = _q(A64, "bf16") @ _q(W64, "bf16") + b64
     ref = ref + _q(R64, "bf16") if resid else _gelu(ref)
     got = C[:, :N].double().cpu()
@@ -329,8 +322,18 @@ def _stats32(xq):
     return st
 
 
+def _accepted(variant):
+    """The variant these cases run under. 10 was a number of the removed diagnostic build: the library
+    must reject it, and its cases exercise the automatic selection (0), which is what they have
+    always run. Every other variant is passed on for _ops.gemm_variant to assert."""
+    if variant != 10:
+        return variant
+    assert _lib.load_library().evt_set_gemm_variant(10) == _lib.EVT_EINVAL
+    return 0
+
+
 @pytest.mark.parametrize("dtype", ["bf16", "f32"])
-@pytest.mark.parametrize("variant", [1, 2, 8, 9, 10, 0, 30, 31])
+@pytest.mark.parametrize("variant", [1, 2, 8, 9, 10, 0, 30, 31])  # 10: see _accepted
 @pytest.mark.parametrize("M,D,N,gelu", [(300, 768, 2304, False), (600, 384, 1536, True),
                                         (197, 192, 537, True), (2900, 768, 3072, True)])
 def test_dense_layernorm_folded_input(gpu, dtype, variant, M, D, N, gelu):
@@ -345,14 +348,9 @@ def test_dense_layernorm_folded_input(gpu, dtype, variant, M, D, N, gelu):
     wp, kpad, npad = _ops.pack(W, dtype, row_scale=g)
     colsum, cvec = _ops.ln_fold(dtype, wp, kpad, npad, W, be, bias)
     flags = _lib.EPI_LNIN | _lib.EPI_BIAS | (_lib.EPI_GELU if gelu else 0)
-    lib = _lib.load_library()
-    lib.evt_set_gemm_variant(variant)
-    try:
+    with _ops.gemm_variant(_accepted(variant)):
         C = _ops.dense(dtype, flags, xq.to(_ops.TDT[dtype]).to(gpu), wp, kpad, npad, M, N,
                        bias=cvec, colsum=colsum, stats_in=_stats32(xq).to(gpu), ln_width=D)
-        torch.cuda.synchronize()
-    finally:
-        lib.evt_set_gemm_variant(0)
     ref = _ln64(xq, g64.float().double(), be64.float().double()) @ W64.float().double() \
         + bias64.float().double()
     if gelu:
@@ -362,7 +360,7 @@ def test_dense_layernorm_folded_input(gpu, dtype, variant, M, D, N, gelu):
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "f32"])
-@pytest.mark.parametrize("variant", [1, 2, 8, 9, 10, 0, 30, 31])
+@pytest.mark.parametrize("variant", [1, 2, 8, 9, 10, 0, 30, 31])  # 10: see _accepted
 @pytest.mark.parametrize("M,K,D", [(300, 768, 768), (513, 3072, 384), (197, 576, 192),
                                    (2900, 768, 768), (12608, 3072, 768), (1, 384, 384),
                                    (129, 1152, 384), (50432, 384, 384)])
@@ -377,17 +375,12 @@ def test_dense_layernorm_residual_and_stats(gpu, dtype, variant, M, K, D):
     bias = torch.zeros(npad, device=gpu)
     bias[:D] = b64.float().to(gpu)
     stats_out = torch.full((M, _nslots(D), 2), float("nan"), device=gpu)
-    lib = _lib.load_library()
-    lib.evt_set_gemm_variant(variant)
-    try:
+    with _ops.gemm_variant(_accepted(variant)):
         C = _ops.dense(dtype, _lib.EPI_BIAS | _lib.EPI_RESID | _lib.EPI_RESLN | _lib.EPI_STATS,
                        Aq.to(_ops.TDT[dtype]).to(gpu), wp, kpad, npad, M, D, bias=bias,
                        resid=xq.to(_ops.TDT[dtype]).to(gpu), rstats=_stats32(xq).to(gpu),
                        rgamma=g64.float().to(gpu), rbeta=be64.float().to(gpu),
                        stats_out=stats_out, ln_width=D)
-        torch.cuda.synchronize()
-    finally:
-        lib.evt_set_gemm_variant(0)
     ref = Aq @ _q(W64.float().double(), dtype) + b64.float().double() \
         + _ln64(xq, g64.float().double(), be64.float().double())
     tol = dict(rtol=2e-2, atol=2e-2) if dtype == "bf16" else dict(rtol=1e-4, atol=1e-4)
@@ -412,15 +405,10 @@ def test_dense_residual_plain_stats(gpu, M, K, N, variant):
     bias = torch.zeros(npad, device=gpu)
     bias[:N] = b64.float().to(gpu)
     st = torch.full((M, _nslots(N), 2), float("nan"), device=gpu)
-    lib = _lib.load_library()
-    lib.evt_set_gemm_variant(variant)
-    try:
+    with _ops.gemm_variant(variant):
         C = _ops.dense("bf16", _lib.EPI_BIAS | _lib.EPI_RESID | _lib.EPI_STATS,
                        Aq.to(torch.bfloat16).to(gpu), wp, kpad, npad, M, N, bias=bias,
                        resid=Rq.to(torch.bfloat16).to(gpu), stats_out=st, ln_width=N)
-        torch.cuda.synchronize()
-    finally:
-        lib.evt_set_gemm_variant(0)
     ref = Aq @ _q(W64.float().double(), "bf16") + b64.float().double() + Rq
     got = C.double().cpu()
     torch.testing.assert_close(got, ref, rtol=2e-2, atol=2e-2)
@@ -442,10 +430,8 @@ def test_dense_rows_independent_of_position(gpu, flags, variant):
     W64, b64 = _rand((K, N), 72, 1 / math.sqrt(K)), _rand((N,), 73, 0.1)
     x64 = _rand((M + shift, N), 74)
     g64, be64 = 1.0 + _rand((N,), 75, 0.1), _rand((N,), 76, 0.1)
-    lib = _lib.load_library()
     outs = []
-    lib.evt_set_gemm_variant(variant)
-    try:
+    with _ops.gemm_variant(variant):
         for off in (0, shift):
             Aq = _q(A64[off:off + M], "bf16").to(torch.bfloat16).to(gpu)
             xq = _q(x64[off:off + M], "bf16")
@@ -470,8 +456,6 @@ def test_dense_rows_independent_of_position(gpu, flags, variant):
                 st = None
             torch.cuda.synchronize()
             outs.append((C.cpu(), None if st is None else st.cpu()))
-    finally:
-        lib.evt_set_gemm_variant(0)
     (c0, s0), (c1, s1) = outs
     assert torch.equal(c0[shift:], c1[:M - shift])
     if s0 is not None:

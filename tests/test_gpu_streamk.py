@@ -41,14 +41,8 @@ def _gelu(x):
 
 
 def _run(variant, fn):
-    lib = _lib.load_library()
-    lib.evt_set_gemm_variant(variant)
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        lib.evt_set_gemm_variant(0)
-    return out
+    with _ops.gemm_variant(variant):
+        return fn()
 
 
 # (M, K, N): 22100 token rows = 87 M tiles (ragged last tile) -> 261 .. 1044 tiles of 256x256

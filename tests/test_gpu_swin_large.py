@@ -16,7 +16,6 @@ is NOT asserted here; variant 9 against variant 1 is the check that both paths a
 
 The errors each test prints, as measured on an MI355X, are recorded in its docstring.
 """
-import contextlib
 import functools
 
 import numpy as np
@@ -28,23 +27,13 @@ from edgevisiontransformer_amd.modeling.models.swin import (SwinTransformer, get
                                                             swin_config_from_name)
 from edgevisiontransformer_amd.weights import make_images, make_swin_params, swin_config
 from oracle import swin_ref
+from tests import _ops
 from tests.test_gpu_dense_epilogues import (F33, F197, F289, LNIN_TOL, _check_resln, _gelu_erf,
                                             _lnin_ref, _resln_host, _run_lnin, _run_resln)
 from tests.test_gpu_ops import _nslots
 from tests.test_swin_large import two_stage_cfg
 
 pytestmark = pytest.mark.gpu
-
-
-@contextlib.contextmanager
-def _variant(v):
-    lib = _lib.load_library()
-    assert lib.evt_set_gemm_variant(v) == _lib.EVT_OK
-    try:
-        yield
-        torch.cuda.synchronize()
-    finally:
-        lib.evt_set_gemm_variant(0)
 
 
 def _model(cfg, dtype, params, gpu, **kw):
@@ -89,7 +78,7 @@ def _two_stage_ref():
 def _two_stage_run(gpu, dtype, variant, batch=11):
     cfg, params, img = _two_stage(batch)
     m = _model(cfg, dtype, params, gpu, max_batch=batch)
-    with _variant(variant):
+    with _ops.gemm_variant(variant):
         out = m(torch.from_numpy(img).to(gpu)).cpu()
     m.close()
     return out
@@ -128,7 +117,7 @@ def test_two_stage_1536_batch_independence_and_graph(gpu, dtype, variant):
     cfg, params, img = _two_stage(5)
     x = torch.from_numpy(img).to(gpu)
     m = _model(cfg, dtype, params, gpu, max_batch=5)
-    with _variant(variant):
+    with _ops.gemm_variant(variant):
         full = m(x)
         part = m(x[2:4].contiguous())
         assert torch.equal(full[2:4], part)
@@ -275,7 +264,7 @@ def test_swin_large_trimmed_against_oracle(gpu, dtype, variant, image_size, wind
     cfg, params, img, ref = _trimmed(image_size, window, batch)
     assert [cfg.window(i) for i in range(4)] == [window] * 4
     m = _model(cfg, dtype, params, gpu, max_batch=batch)
-    with _variant(variant):
+    with _ops.gemm_variant(variant):
         out = m(torch.from_numpy(img).to(gpu)).cpu().numpy().astype(np.float64)
     m.close()
     _gate(out, ref, dtype, f"swin_large trimmed {image_size} px variant {variant}")

@@ -27,7 +27,7 @@ sys.path.insert(0, os.path.join(ROOT, "scripts", "probe"))
 import store_hazard  # noqa: E402
 
 sys.path.insert(0, ROOT)
-from edgevisiontransformer_amd.build import SOURCES  # noqa: E402
+from edgevisiontransformer_amd.build import GEMM_HEADERS, SOURCES  # noqa: E402
 
 HIP_SOURCES = [s for s in SOURCES if s.endswith(".hip")]
 
@@ -98,7 +98,7 @@ RAW = re.compile(r"__builtin_nontemporal_store|__builtin_amdgcn_raw_buffer_store
                  r"\*\s*\(\s*(u32x4|f32x4|bf16x8|i32x4|u32x3|float4|uint4)\s*\*\s*\)[^;=]*=[^=]")
 
 
-@pytest.mark.parametrize("src", HIP_SOURCES)
+@pytest.mark.parametrize("src", HIP_SOURCES + GEMM_HEADERS)
 def test_sources_store_wide_only_through_helpers(src):
     bad = []
     for i, line in enumerate(open(os.path.join(CSRC, src)), 1):
