@@ -218,6 +218,24 @@ ATTENTION_SIGNATURES = {
     "evt_attention_probs": (_I, [_I, _P, _I64, _I64, _I64, _I, _I, _I, _I, _I, _F, _I, _P, _P]),
 }
 
+class evt_head_stats_args(ctypes.Structure):
+    _fields_ = [("n_blocks", ctypes.c_int32), ("blocks", ctypes.POINTER(ctypes.c_int32)),
+                ("stats", ctypes.POINTER(ctypes.c_void_p))]
+
+
+# include/evt_head_stats.h constants: EVT_HEAD_STATS and the index of each statistic
+HEAD_STATS = 4
+HEAD_CONFIDENCE, HEAD_ENTROPY, HEAD_DISTANCE, HEAD_CLS_MASS = 0, 1, 2, 3
+# the entry points of include/evt_head_stats.h (evt.h includes it; bound like SIGNATURES)
+HEAD_STATS_SIGNATURES = {
+    "evt_head_stats_shape": (_I, [_P, _I, _PI, _PI, _PI, _PI]),
+    "evt_forward_head_stats": (_I, [_P, ctypes.POINTER(evt_image_args), _I,
+                                    ctypes.POINTER(evt_features_args),
+                                    ctypes.POINTER(evt_head_stats_args), _P]),
+    "evt_attention_head_stats": (_I, [_I, _P, _I64, _I64, _I64, _I, _I, _I, _I, _I, _F, _I, _I,
+                                      _P, _P]),
+}
+
 # the entry points of include/evt_window_attention.h (evt.h includes it; bound like SIGNATURES)
 WINDOW_ATTENTION_SIGNATURES = {
     "evt_window_attn_map_shape": (_I, [_P, _I, _PI, _PI, _PI]),
@@ -285,7 +303,7 @@ def load_library() -> ctypes.CDLL:
             for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **FEATURE_SIGNATURES,
                                       **IMAGE_SIGNATURES, **PREPROCESS_SIGNATURES,
                                       **ATTENTION_SIGNATURES, **WINDOW_ATTENTION_SIGNATURES,
-                                      **TAIL_SIGNATURES,
+                                      **TAIL_SIGNATURES, **HEAD_STATS_SIGNATURES,
                                       **CLASSIFY_SIGNATURES, **WORKSPACE_SIGNATURES,
                                       **PERFORMER_SIGNATURES}.items():
                 if lenient and not hasattr(lib, name):

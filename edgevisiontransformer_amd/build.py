@@ -27,6 +27,7 @@ HEADERS = GEMM_HEADERS + [
            os.path.join("..", "..", "include", "evt_image.h"),
            os.path.join("..", "..", "include", "evt_preprocess.h"),
            os.path.join("..", "..", "include", "evt_attention_maps.h"),
+           os.path.join("..", "..", "include", "evt_head_stats.h"),
            os.path.join("..", "..", "include", "evt_window_attention.h"),
            os.path.join("..", "..", "include", "evt_tail.h"),
            os.path.join("..", "..", "include", "evt_classify.h"),

@@ -323,6 +323,276 @@ hipError_t attn_probs_launch(int dtype, const AttnParams& p_in, int nq, float* o
   return launch_probs<float, 128>(p, nq, nqb, wide, out, s);
 }
 
+// ---- Head statistics (include/evt_head_stats.h) ------------------------------------------------
+//
+//   stats[b][h] = (confidence, entropy, distance, cls_mass)
+//
+// four reductions of the probabilities p_ij attn_probs_kernel forms, with no map store:
+//   confidence  mean_i max_j p_ij                           = mean_i 1 / l_i (the maximum's term is 2^0)
+//   entropy     mean_i -sum_j p_ij ln p_ij                  = mean_i ln l_i - (ln 2 / l_i) sum_j e_ij t_ij
+//   distance    mean_{i >= prefix} sum_{j >= prefix} p_ij d(i, j)
+//   cls_mass    mean_{i >= prefix} sum_{j < prefix} p_ij
+// with t_ij = (s_ij - m_i) c <= 0, e_ij = 2^t_ij, l_i = sum_j e_ij and d the Euclidean distance of
+// the patch-grid cells of tokens i and j (token t >= prefix: row (t - prefix) / grid_w, column
+// (t - prefix) % grid_w).
+//
+// TWO PASSES, as attn_probs_kernel: pass 1 is its pass 1 (m, l), pass 2 forms the scores again and
+// accumulates the three sums sum e t, sum_{j >= prefix} e d and sum_{j < prefix} e against the final
+// m, so nothing is rescaled. The score machinery (S^T = K Q^T on the MFMA, 64-key blocks, K staged
+// to LDS for bf16, operands from the rows for fp32, zero-padded head sizes, AttnParams layouts,
+// clamped rows, 64-bit offsets) is attn_probs_kernel's, restated here so that kernel's code and
+// bits stay what they are.
+//
+// Keys past N carry -inf scores: t = -inf, e = 0. They are selected out of the e t sum by index (a
+// product would be 0 * -inf = NaN; this file is compiled honouring NaN and inf); in the other two
+// sums their e = 0 multiplies a finite d. A finite t whose e underflows contributes exactly 0.
+// Key coordinates: one float-reciprocal division per lane per group of four consecutive keys per
+// block ((r + 0.5) * (1 / grid_w), exact for r < 2^22 as in the GEMM's gathered loaders), the other
+// three by stepping; d = sqrt(dy dy + dx dx) of small integers in fp32 (the sum exact, v_sqrt_f32).
+//
+// Determinism: one 4-wave workgroup per (image, head) walks the 64-query groups; a lane sums its
+// query's values over the groups in fp64 (a mean of T fp32 values then carries one rounding, and
+// q = 0 gives confidence = fl(1 / N) exactly), the wave's 16 queries are added by a butterfly, the
+// four waves through LDS in wave order. No atomics, no scratch; the four floats leave as one 16-B
+// store. Nothing depends on the batch position, and both qkv layouts stage the same values.
+namespace {
+
+template <typename T, int DP>
+__global__ __launch_bounds__(256) void head_stats_kernel(AttnParams p, int prefix, int gw,
+                                                         float inv_gw, float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __shared__ double red[4][4];
+  constexpr bool BF = sizeof(T) == 2;
+  constexpr int RB = DP * 2, NCH = DP / 8, SWM = k_swm<DP>(), KS = DP / 32, NG = DP / 64;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = lane >> 4, c16 = lane & 15;
+  EVT_LDS char* Ks = (EVT_LDS char*)smem;  // bf16: one K block, [64][DP]
+  const int bh = blockIdx.x;
+  const int b = bh / p.H, h = bh - b * p.H, hd = p.hd, N = p.N;
+  const T* slice = (const T*)p.qkv + b * p.sb + h * p.sh;  // q of the (image, head); k at + ko
+  const int nqt = (N + 15) >> 4, nkb = (N + KB - 1) / KB, nqb = (nqt + 3) >> 2;
+  const float c = p.scale_log2;
+  const T* qrow = slice;
+  u32x4 qf[BF ? KS : 1];
+
+  // bf16: key block kb of K into LDS, 16-B chunk ch of row r at chunk ch ^ (r & SWM)
+  auto stage = [&](int kb) {
+    for (int i = tid; i < KB * NCH; i += 256) {
+      const int row = i / NCH, ch = i - row * NCH;
+      const bf16* rp = (const bf16*)slice + (int64_t)min(kb * KB + row, N - 1) * p.ldq + p.ko;
+      *(EVT_LDS u32x4*)(Ks + row * RB + ((ch ^ (row & SWM)) << 4)) = chunk8(rp, ch * 8, hd);
+    }
+  };
+  // s[kt][j] = S^T[key = kb*64 + kt*16 + 4g + j][query = qt*16 + c16], -inf for keys past N
+  auto scores = [&](int kb, f32x4(&s)[NKT]) {
+    if constexpr (BF) {
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt) {
+        const int row = kt * 16 + c16;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          const u32x4 kf = *(const EVT_LDS u32x4*)(Ks + row * RB + (((4 * ks + g) ^ (row & SWM)) << 4));
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf),
+                                                        __builtin_bit_cast(bf16x8, qf[ks]), acc, 0, 0, 0);
+        }
+        s[kt] = acc;
+      }
+    } else {
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt) s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int kk = 0; kk < 4 * NG; ++kk) {
+        const int d0 = 16 * kk + 4 * g;
+        const f32x4 qv = chunk4((const float*)qrow, d0, hd);
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt) {
+          const float* krow =
+              (const float*)slice + (int64_t)min(kb * KB + kt * 16 + c16, N - 1) * p.ldq + p.ko;
+          const f32x4 kv = chunk4(krow, d0, hd);
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            s[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kv[e], qv[e], s[kt], 0, 0, 0);
+        }
+      }
+    }
+    if ((kb + 1) * KB > N) {  // wave-uniform: only the last block holds keys past N
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (kb * KB + kt * 16 + 4 * g + j >= N) s[kt][j] = -INFINITY;
+    }
+  };
+  // grid cell (row, column) of patch r = token - prefix, as floats (a query below prefix or past N
+  // gets a finite cell nobody reads)
+  auto cell = [&](int r, float& y, float& x) {
+    const int yi = (int)(((float)r + 0.5f) * inv_gw);
+    y = (float)yi;
+    x = (float)(r - yi * gw);
+  };
+
+  double a_conf = 0.0, a_ent = 0.0, a_dist = 0.0, a_cls = 0.0;  // this lane's query, over the groups
+  for (int qb = 0; qb < nqb; ++qb) {
+    const int qt = qb * 4 + wave, qi = qt * 16 + c16;
+    const bool active = qt < nqt;  // wave-uniform
+    if constexpr (!BF) {
+      if (!active) continue;  // no barrier in the fp32 loops
+    }
+    qrow = slice + (int64_t)min(qi, N - 1) * p.ldq;
+    if constexpr (BF) {
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) qf[ks] = chunk8((const bf16*)qrow, 32 * ks + 8 * g, hd);
+    }
+    // ---- pass 1: m = max_j s, l = sum_j 2^((s - m) c) (attn_probs_kernel's pass 1)
+    float m = -INFINITY, l = 0.f;
+    for (int kb = 0; kb < nkb; ++kb) {
+      if constexpr (BF) {
+        __syncthreads();  // every wave is done with the block staged before
+        stage(kb);
+        __syncthreads();
+        if (!active) continue;
+      }
+      f32x4 s[NKT];
+      scores(kb, s);
+      float bm = s[0][0];
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bm = fmaxf(bm, s[kt][j]);
+      bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
+      bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+      const float mn = fmaxf(m, bm);
+      float sum = 0.f;
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sum += ex2<BF>((s[kt][j] - mn) * c);
+      l = l * ex2<BF>((m - mn) * c) + sum;
+      m = mn;
+    }
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+
+    // ---- pass 2: sum_j e t, sum_{j >= prefix} e d, sum_{j < prefix} e with e = 2^t, t = (s - m) c
+    float qy, qx;
+    cell(qi - prefix, qy, qx);
+    float et = 0.f, ed = 0.f, ec = 0.f;
+    for (int kb = 0; kb < nkb; ++kb) {
+      if constexpr (BF) {
+        __syncthreads();
+        stage(kb);
+        __syncthreads();
+        if (!active) continue;
+      }
+      f32x4 s[NKT];
+      scores(kb, s);
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt) {
+        const int k0 = kb * KB + kt * 16 + 4 * g;  // this lane's four consecutive keys
+        float ky, kx;  // the cell of key max(k0, prefix): it steps once a key is a patch
+        cell(max(k0 - prefix, 0), ky, kx);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int key = k0 + j;
+          const float t = (s[kt][j] - m) * c;
+          const float e = ex2<BF>(t);
+          et += key < N ? e * t : 0.f;
+          const float dy = qy - ky, dx = qx - kx;
+          const float d = __builtin_amdgcn_sqrtf(dy * dy + dx * dx);
+          ed += key >= prefix ? e * d : 0.f;
+          ec += key < prefix ? e : 0.f;
+          if (key >= prefix) {  // the next key's cell
+            kx += 1.f;
+            if (kx >= (float)gw) {
+              kx = 0.f;
+              ky += 1.f;
+            }
+          }
+        }
+      }
+    }
+    et += __shfl_xor(et, 16, 64);
+    et += __shfl_xor(et, 32, 64);
+    ed += __shfl_xor(ed, 16, 64);
+    ed += __shfl_xor(ed, 32, 64);
+    ec += __shfl_xor(ec, 16, 64);
+    ec += __shfl_xor(ec, 32, 64);
+    if (active && qi < N) {  // l >= 1, et <= 0: 0 < 1 / l <= 1 and the entropy is >= 0
+      const float inv = 1.0f / l;
+      a_conf += (double)inv;
+      a_ent += (double)(logf(l) - (0.6931471805599453f * inv) * et);
+      if (qi >= prefix) {
+        a_dist += (double)(ed * inv);
+        a_cls += (double)fminf(ec * inv, 1.0f);
+      }
+    }
+  }
+  // the wave's 16 queries (the four lanes of a query hold the same values), then the four waves
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) {
+    a_conf += __shfl_xor(a_conf, o, 64);
+    a_ent += __shfl_xor(a_ent, o, 64);
+    a_dist += __shfl_xor(a_dist, o, 64);
+    a_cls += __shfl_xor(a_cls, o, 64);
+  }
+  if (lane == 0) {
+    red[wave][0] = a_conf;
+    red[wave][1] = a_ent;
+    red[wave][2] = a_dist;
+    red[wave][3] = a_cls;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double t[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) t[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+    const double nall = (double)N, npatch = (double)(N - prefix);
+    store_f32x4(out + (int64_t)bh * 4, f32x4{(float)(t[0] / nall), (float)(t[1] / nall),
+                                             (float)(t[2] / npatch), (float)(t[3] / npatch)});
+  }
+}
+
+template <typename T, int DP>
+hipError_t launch_head_stats(const AttnParams& p, int prefix, int gw, float* out, hipStream_t s) {
+  const size_t lds = sizeof(T) == 2 ? (size_t)KB * DP * 2 : 0;
+  hipLaunchKernelGGL((head_stats_kernel<T, DP>), dim3(p.B * p.H), dim3(256), lds, s, p, prefix, gw,
+                     1.0f / (float)gw, out);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t head_stats_launch(int dtype, const AttnParams& p_in, int prefix, int grid_w, float* out,
+                             hipStream_t s) {
+  if (p_in.B <= 0) return hipSuccess;
+  if (!p_in.qkv || !out || p_in.N <= 0 || p_in.N > EVT_ATTN_MAX_TOKENS || p_in.H <= 0 ||
+      p_in.hd <= 0 || p_in.hd > 128 || ((uintptr_t)out & 15) || prefix < 0 || prefix >= p_in.N ||
+      grid_w < 1 || (p_in.N - prefix) % grid_w)
+    return hipErrorInvalidValue;
+  // (s - m) c <= 0 and the -inf masks need c > 0
+  if (!(p_in.scale_log2 > 0.f && p_in.scale_log2 < INFINITY)) return hipErrorInvalidValue;
+  AttnParams p = p_in;
+  if (p.sb || p.sh || p.ko) {  // an explicit slice layout: bf16, h_k = 64, 16-B aligned pieces
+    if (dtype != DT_BF16 || p.hd != 64 || p.sb % 8 || p.sh % 8 || p.ldq % 8 || p.ko % 8 ||
+        p.ldq < 64 || p.ko < 0 || p.sb < 0 || p.sh < 0)
+      return hipErrorInvalidValue;
+  } else {
+    p.sb = (int64_t)p.N * p.ldq;
+    p.sh = p.hd;
+    p.ko = p.H * p.hd;
+  }
+  if ((int64_t)p.B * p.H > INT32_MAX) return hipErrorInvalidValue;
+  if (dtype == DT_BF16) {
+    if (p.hd <= 32) return launch_head_stats<bf16, 32>(p, prefix, grid_w, out, s);
+    if (p.hd <= 64) return launch_head_stats<bf16, 64>(p, prefix, grid_w, out, s);
+    if (p.hd <= 96) return launch_head_stats<bf16, 96>(p, prefix, grid_w, out, s);
+    return launch_head_stats<bf16, 128>(p, prefix, grid_w, out, s);
+  }
+  if (dtype != DT_F32) return hipErrorInvalidValue;
+  if (p.hd <= 64) return launch_head_stats<float, 64>(p, prefix, grid_w, out, s);
+  return launch_head_stats<float, 128>(p, prefix, grid_w, out, s);
+}
+
 // ---- Swin window attention maps (include/evt_window_attention.h) -------------------------------
 //
 //   out[b][win][h][q][k] = softmax_k(q_q . k_k 32^-0.5 + rpb[rel(q, k)][h] + mask(win, q, k))

@@ -141,6 +141,12 @@ bool attention_cls_ok(int dtype, const AttnParams& p);  // p.cls_only is honoure
 // and the MX8 fields unused; sb / sh / ko: bf16 h_k = 64 only). scale_log2 positive and finite,
 // out 16-byte aligned (hipErrorInvalidValue otherwise).
 hipError_t attn_probs_launch(int dtype, const AttnParams& p, int nq, float* out, hipStream_t s);
+// Head statistics (attn_maps.hip; include/evt_head_stats.h): out[b][h][0..3] = (confidence,
+// entropy, distance, cls_mass) of the same probabilities, fp32 contiguous [B][H][4]; p as
+// attn_probs_launch, `prefix` leading non-patch tokens (0 <= prefix < N), a patch grid of grid_w
+// columns ((N - prefix) % grid_w == 0). One launch, no scratch; out 16-byte aligned.
+hipError_t head_stats_launch(int dtype, const AttnParams& p, int prefix, int grid_w, float* out,
+                             hipStream_t s);
 
 
 // LayerNorm over rows of D (fp32 in) -> activation dtype out (eps 1e-5).

@@ -233,6 +233,26 @@ int attn_map(evt_model* m, ForwardCall& call, int block, const AttnParams& ap) {
   return EVT_OK;
 }
 
+// Columns of the patch grid behind an encoder's tokens 1 .. T - 1 (token 0 is the CLS token):
+// image_size / patch_size for a ViT, image_size / 16 after T2T-ViT's three soft splits
+static int patch_grid_w(const ModelCore& m) {
+  return m.family == FAM_T2T ? m.image_size / 16 : m.image_size / m.patch_size;
+}
+
+// At the same point of an evt_forward_head_stats call: the block's four statistics per head, if they
+// were asked for (attn_maps.hip; counted under EVT_PROF_HEAD)
+int head_stats(evt_model* m, ForwardCall& call, int block, const AttnParams& ap) {
+  const evt_head_stats_args* a = call.hstats;
+  if (!a || call.hstats_next >= a->n_blocks || a->blocks[call.hstats_next] != block) return EVT_OK;
+  ProfScope ps(m, EVT_PROF_HEAD, call.s);
+  const double bh = (double)ap.B * ap.H;
+  prof_work(m, 4.0 * bh * ap.N * (double)ap.N * ap.hd,  // the scores, twice
+            bh * (2.0 * ap.N * ap.hd * elem_size(m->dtype) + 4.0 * EVT_HEAD_STATS));
+  EVT_HIP(head_stats_launch(m->dtype, ap, 1, patch_grid_w(*m), a->stats[call.hstats_next++], call.s),
+          "head statistics");
+  return EVT_OK;
+}
+
 // The Swin counterpart (evt_forward_window_attention): while ws.qkv holds block `block`'s LN1-folded
 // QKV rows that `ap` describes, the block's window map, if it is the next one asked for
 bool window_attn_wanted(const ForwardCall& call, int block) {
@@ -725,6 +745,62 @@ int evt_forward_attention(evt_model* m, const evt_image_args* in, int B,
   call.feat = feat;
   call.attn = a;
   // one lane, on this handle's own workspace, whatever its lane count (as a features forward)
+  return forward(m, call, false);
+}
+
+// ---- head statistics (include/evt_head_stats.h) ---------------------------------------------
+
+int evt_head_stats_shape(const evt_model* m, int block, int* heads, int* tokens, int* prefix,
+                         int* grid_w) {
+  if (!m || !heads || !tokens || !prefix || !grid_w) return fail(EVT_EINVAL, "null argument");
+  EVT_RC(attn_family(m));
+  if (block < 0 || block >= (int)m->layers.size())
+    return fail(EVT_EINVAL, "block must be in [0, " + std::to_string(m->layers.size()) + ")");
+  const int gw = patch_grid_w(*m);
+  if (gw < 1 || (m->sh.T - 1) % gw)
+    return fail(EVT_EINVAL, "head statistics: the tokens after the CLS token are not a grid of "
+                            "image_size / patch rows");
+  *heads = m->layers[block].heads;
+  *tokens = m->sh.T;
+  *prefix = 1;
+  *grid_w = gw;
+  return EVT_OK;
+}
+
+int evt_forward_head_stats(evt_model* m, const evt_image_args* in, int B,
+                           const evt_features_args* feat, const evt_head_stats_args* a,
+                           void* stream) {
+  ImgAffine aff{};
+  if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and hs must be non-null");
+  EVT_RC(validate_image(m, in, &aff));
+  EVT_RC(attn_family(m));
+  if (a->n_blocks < 0 || a->n_blocks > 64) return fail(EVT_EINVAL, "n_blocks must be in [0, 64]");
+  if (a->n_blocks == 0 && !feat)
+    return fail(EVT_EINVAL, "no output requested: n_blocks is 0 and feat is NULL");
+  if (feat) EVT_RC(validate_features(m, feat, B));
+  else EVT_RC(check_batch(m, B));
+  if (a->n_blocks > 0) {
+    if (!a->blocks || !a->stats)
+      return fail(EVT_EINVAL, "n_blocks > 0 needs the blocks and stats arrays");
+    const int nb = (int)m->layers.size(), gw = patch_grid_w(*m);
+    if (gw < 1 || (m->sh.T - 1) % gw)
+      return fail(EVT_EINVAL, "head statistics: the tokens after the CLS token are not a grid of "
+                              "image_size / patch rows");
+    for (int i = 0; i < a->n_blocks; ++i) {
+      if (a->blocks[i] < 0 || a->blocks[i] >= nb)
+        return fail(EVT_EINVAL, "head statistics block " + std::to_string(a->blocks[i]) +
+                                    " is outside [0, " + std::to_string(nb) + ")");
+      if (i > 0 && a->blocks[i] <= a->blocks[i - 1])
+        return fail(EVT_EINVAL, "head statistics blocks must be strictly increasing");
+      if (!a->stats[i]) return fail(EVT_EINVAL, "stats pointer " + std::to_string(i) + " is NULL");
+      if ((uintptr_t)a->stats[i] & 15)
+        return fail(EVT_EINVAL, "head statistics must be 16-byte aligned");
+    }
+  }
+  ForwardCall call = image_call(in, aff, B, feat ? feat->logits : nullptr, stream);
+  call.feat = feat;
+  call.hstats = a;
+  // one lane, on this handle's own workspace, whatever its lane count (as evt_forward_attention)
   return forward(m, call, false);
 }
 

@@ -397,6 +397,44 @@ int evt_attention_probs(int dtype, const void* qkv, int64_t ldq, int64_t sb, int
   return EVT_OK;
 }
 
+// include/evt_head_stats.h: evt_attention_probs' checks of (qkv, layout, shape, scale, out), then
+// the patch geometry
+int evt_attention_head_stats(int dtype, const void* qkv, int64_t ldq, int64_t sb, int64_t sh,
+                             int ko, int B, int N, int H, int head_dim, float scale, int prefix,
+                             int grid_w, float* out, void* stream) {
+  if (dtype != EVT_DTYPE_F32 && dtype != EVT_DTYPE_BF16)
+    return fail(EVT_EINVAL, "attention_head_stats: dtype must be EVT_DTYPE_F32 or EVT_DTYPE_BF16");
+  if (!qkv || !out || B < 0 || N <= 0 || N > EVT_ATTN_MAX_TOKENS || H <= 0 || head_dim <= 0 ||
+      head_dim > 128)
+    return fail(EVT_EINVAL, "attention_head_stats: bad shape (N <= 4096, head size in [1, 128])");
+  if (!(scale > 0.f && scale < INFINITY))
+    return fail(EVT_EINVAL, "attention_head_stats: the scale must be positive and finite");
+  if (prefix < 0 || prefix >= N || grid_w < 1 || (N - prefix) % grid_w)
+    return fail(EVT_EINVAL, "attention_head_stats: needs 0 <= prefix < N, grid_w >= 1 and "
+                            "(N - prefix) % grid_w == 0");
+  if ((uintptr_t)out & 15)
+    return fail(EVT_EINVAL, "attention_head_stats: out must be 16-byte aligned");
+  const int64_t vec = dtype == DT_BF16 ? 8 : 4;
+  if (sb || sh || ko) {
+    if (dtype != DT_BF16 || head_dim != 64 || sb < 0 || sh < 0 || ko < 0 || sb % 8 || sh % 8 ||
+        ko % 8 || ldq % 8 || ldq < 64 || ((uintptr_t)qkv & 15))
+      return fail(EVT_EINVAL, "attention_head_stats: a slice layout needs bf16, head size 64 and "
+                              "non-negative strides that are multiples of 8");
+  } else {
+    if (ldq < 3 * (int64_t)H * head_dim)
+      return fail(EVT_EINVAL, "attention_head_stats: ldq must be at least 3*H*head_dim");
+    if (head_dim % vec == 0 && (ldq % vec || ((uintptr_t)qkv & 15)))
+      return fail(EVT_EINVAL,
+                  "attention_head_stats: qkv rows must be 16-B aligned for this head size");
+  }
+  AttnParams p{qkv, ldq, nullptr, 0, N, H, B, scale * 1.4426950408889634f};
+  p.hd = head_dim;
+  p.sb = sb; p.sh = sh; p.ko = ko;
+  EVT_HIP(head_stats_launch(dtype, p, prefix, grid_w, out, (hipStream_t)stream),
+          "attention_head_stats");
+  return EVT_OK;
+}
+
 int evt_window_attention_probs(int dtype, const void* qkv, int64_t ldq, const float* rpb, int B,
                                int R, int window, int C, int H, int shift, float* out,
                                void* stream) {

@@ -80,3 +80,39 @@ def evaluate(model, loader: Iterable, topk: int = 5, transform=None,
 
 def _ratio(a: int, b: int) -> float:
     return a / b if b else 0.0
+
+
+def collect_head_stats(model, loader: Iterable, transform=None, blocks=None):
+    """Dataset means of the per-head attention statistics (modeling/models/head_stats.py): one
+    fp64 [H_i, 4] array per block (`blocks=None`: every block; negative indices and any order as
+    `head_stats`), columns in HEAD_STATS order (confidence, entropy, distance, cls_mass).
+
+    `loader` yields what `evaluate` takes: (images, target) tuples, of which the target is not
+    read, or the images alone. Each batch's [B, H_i, 4] is summed over its images (a torch sum
+    over the batch axis) into a per-block fp64 device tensor that lives for the whole loop; the
+    host reads once, at the end. Every image weighs the same, whatever its batch's size."""
+    import torch
+
+    from .modeling.models.features import resolve_taps
+    device = model.device
+    on_device = torch.cuda.device(device) if device.type == "cuda" else contextlib.nullcontext()
+    nb = model.num_blocks
+    idx = resolve_taps(range(nb) if blocks is None else blocks, nb)
+    heads = [model.head_stats_shape(i)[0] for i in idx]
+    sums = [torch.zeros((h, 4), dtype=torch.float64, device=device) for h in heads]
+    bufs, seen = None, 0
+    for item in loader:
+        images = item[0] if isinstance(item, tuple) else item
+        x = _device_batch(model, images, transform)
+        b = x.shape[0]
+        if bufs is None or bufs[0].shape[0] < b:  # one set of buffers for the loop
+            bufs = [torch.empty((b, h, 4), dtype=torch.float32, device=device) for h in heads]
+        views = [t[:b] for t in bufs]
+        with on_device:
+            model.head_stats_into(x, blocks=idx, stat_tensors=views)
+            for s, v in zip(sums, views):
+                s += v.sum(dim=0, dtype=torch.float64)
+        seen += b
+    if not seen:
+        raise ValueError("collect_head_stats: the loader gave no images")
+    return [(s / seen).cpu().numpy() for s in sums]

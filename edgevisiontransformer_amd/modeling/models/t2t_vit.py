@@ -82,6 +82,10 @@ class T2T_ViT(Classification):
         c = self.cfg
         return [(c.heads, c.tokens)] * c.depth
 
+    # -- head statistics (head_stats.py): the S/16 token grid of soft_split2 behind the CLS token -
+    def _patch_grid_w(self):
+        return self.cfg.image_size // 16
+
 
 def get_t2t_vit_7(**kw) -> T2T_ViT:
     return T2T_ViT(hidden_size=256, depth=7, num_heads=4, mlp_ratio=2, **kw)

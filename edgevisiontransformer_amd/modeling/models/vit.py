@@ -130,6 +130,10 @@ class ViT(Classification):
         c = self.cfg
         return [(int(h), c.tokens) for h in list(c.heads)[:c.depth]]
 
+    # -- head statistics (head_stats.py): token 0 is the CLS token, the rest the patch grid ------
+    def _patch_grid_w(self):
+        return self.cfg.image_size // self.cfg.patch_size
+
 
 class ViT_Pruned(ViT):
     """Head/FFN-pruned ViT (reference `ViT_Pruned`, vit.py:58-75)."""

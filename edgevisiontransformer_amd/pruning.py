@@ -73,6 +73,32 @@ def load_head_importance(path: str) -> np.ndarray:
     return np.asarray(rows, dtype=np.float64)
 
 
+def importance_from_head_stats(stats: Sequence[np.ndarray], kind: str = "confidence") -> np.ndarray:
+    """The [layers, heads] importance table `heads_from_importance` takes, from per-block head
+    statistics: `stats[l]` is a [H, 4] array (`collect_head_stats`) or a [B, H, 4] one (`head_stats`,
+    averaged over its images here), `kind` one of HEAD_STATS (modeling/models/head_stats.py). The
+    value is the statistic itself: with "confidence" (Voita et al.) a higher value is a more
+    important head. ValueError: an unknown `kind`, no blocks, or blocks whose head counts differ (a
+    pruned model: a table has one width)."""
+    names = ("confidence", "entropy", "distance", "cls_mass")
+    if kind not in names:
+        raise ValueError(f"kind must be one of {names}, got {kind!r}")
+    rows = []
+    for l, s in enumerate(stats):
+        a = np.asarray(s, dtype=np.float64)
+        if a.ndim == 3:
+            a = a.mean(axis=0)
+        if a.ndim != 2 or a.shape[1] != len(names):
+            raise ValueError(f"stats[{l}] must be [H, 4] or [B, H, 4], got {a.shape}")
+        rows.append(a[:, names.index(kind)])
+    if not rows:
+        raise ValueError("no blocks given")
+    if len({len(r) for r in rows}) != 1:
+        raise ValueError(f"head counts differ between blocks ({[len(r) for r in rows]}): an "
+                         "importance table needs the same number of heads in every layer")
+    return np.stack(rows)
+
+
 def heads_from_importance(importance: np.ndarray, keep_per_layer: Optional[Sequence[int]] = None,
                           keep_total: Optional[int] = None) -> List[List[int]]:
     """Kept heads per layer, most important first kept: either a per-layer count, or a global

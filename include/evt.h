@@ -517,6 +517,7 @@ int evt_model_qkv_layout(const evt_model* m, int* headmajor_layers);
 #include "evt_image.h"     /* evt_forward_image, evt_graph_capture_image, evt_patchify_u8, evt_unfold_u8 */
 #include "evt_preprocess.h"  /* evt_resize_geometry, evt_resize_plan_*, evt_resize_crop_u8 */
 #include "evt_attention_maps.h"  /* evt_forward_attention, evt_attn_map_shape, evt_attention_probs */
+#include "evt_head_stats.h"  /* evt_forward_head_stats, evt_head_stats_shape, evt_attention_head_stats */
 #include "evt_window_attention.h"  /* evt_forward_window_attention, evt_window_attn_map_shape, evt_window_attention_probs */
 #include "evt_classify.h"  /* evt_classify, evt_forward_classify */
 #include "evt_tail.h"      /* evt_model_tail_mode (the encoder's CLS tail) */
