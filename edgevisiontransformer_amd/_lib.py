@@ -236,6 +236,24 @@ HEAD_STATS_SIGNATURES = {
                                       _P, _P]),
 }
 
+class evt_rollout_args(ctypes.Structure):
+    _fields_ = [("start", ctypes.c_int32), ("mode", ctypes.c_int32), ("out", ctypes.c_void_p),
+                ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t)]
+
+
+# include/evt_rollout.h constants
+ROLLOUT_CLS, ROLLOUT_ALL = 0, 1
+# the entry points of include/evt_rollout.h (evt.h includes it; bound like SIGNATURES)
+ROLLOUT_SIGNATURES = {
+    "evt_rollout_shape": (_I, [_P, _PI, _PI]),
+    "evt_rollout_scratch_bytes": (_I, [_P, _I, _I, ctypes.POINTER(ctypes.c_size_t)]),
+    "evt_forward_rollout": (_I, [_P, ctypes.POINTER(evt_image_args), _I,
+                                 ctypes.POINTER(evt_features_args),
+                                 ctypes.POINTER(evt_rollout_args), _P]),
+    "evt_attention_rollout_step": (_I, [_I, _P, _I64, _I64, _I64, _I, _I, _I, _I, _I, _F, _P, _P,
+                                        _P, ctypes.c_size_t, _P]),
+}
+
 # the entry points of include/evt_window_attention.h (evt.h includes it; bound like SIGNATURES)
 WINDOW_ATTENTION_SIGNATURES = {
     "evt_window_attn_map_shape": (_I, [_P, _I, _PI, _PI, _PI]),
@@ -304,6 +322,7 @@ def load_library() -> ctypes.CDLL:
                                       **IMAGE_SIGNATURES, **PREPROCESS_SIGNATURES,
                                       **ATTENTION_SIGNATURES, **WINDOW_ATTENTION_SIGNATURES,
                                       **TAIL_SIGNATURES, **HEAD_STATS_SIGNATURES,
+                                      **ROLLOUT_SIGNATURES,
                                       **CLASSIFY_SIGNATURES, **WORKSPACE_SIGNATURES,
                                       **PERFORMER_SIGNATURES}.items():
                 if lenient and not hasattr(lib, name):

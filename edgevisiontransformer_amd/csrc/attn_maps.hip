@@ -593,6 +593,260 @@ hipError_t head_stats_launch(int dtype, const AttnParams& p_in, int prefix, int 
   return launch_head_stats<float, 128>(p, prefix, grid_w, out, s);
 }
 
+// ---- Head mean (include/evt_rollout.h) ---------------------------------------------------------
+//
+//   out[b][i][j] = (sum_h p[b][h][i][j]) * fl(1 / H)
+//
+// the mean over the heads of the probabilities attn_probs_kernel forms, fp32 [B][N][N], with no
+// per-head map stored: the A operand of an attention-rollout step (rollout.hip). A workgroup (4
+// waves) takes (image, 64 queries), a wave one 16-query tile, and loops over the heads inside:
+//
+//   pass 1  for every head: the running max m and sum l over the 64-key blocks (attn_probs_kernel's
+//           pass 1); m and 1 / l of the wave's 16 queries go to a per-wave LDS table [H][16][2]
+//   pass 2  for every key block: for h = 0 .. H - 1 in that order the scores again,
+//           p = 2^((s - m_h) c) / l_h (the same expression, so the same bits, as the export) added
+//           to an fp32 accumulator that starts at 0; then one product with fl(1 / H), the block
+//           through the wave's LDS tile and out by row segments
+//
+// A [16 x N] accumulator per wave does not fit anywhere for N up to 4096, hence the key block as
+// the outer loop of pass 2 and the table; bf16 stages the same number of K blocks (H nkb per pass)
+// as a loop with the head outside would, and reloads the q fragments per (block, head) from L2.
+// The score machinery is attn_probs_kernel's, restated (that kernel's code and bits stay what they
+// are). The head sum has one order, nothing is atomic, nothing depends on the batch position, and
+// both qkv layouts stage the same values: results are bitwise reproducible and layout independent.
+// Every p is in [0, 1], so the sum is in [0, H] and the mean in [0, 1] up to one rounding; keys
+// past N get -inf scores, contribute 2^-inf = 0 and are not stored.
+//
+// Stores: the dword row-segment form that won for the export (a lane per float, 256 contiguous
+// bytes per wave instruction), plain rather than non-temporal: the rollout step reads the buffer
+// next. Every row and output offset is 64-bit.
+namespace {
+
+template <typename T, int DP>
+__global__ __launch_bounds__(256) void head_mean_kernel(AttnParams p, int nqb, float inv_h,
+                                                        float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr bool BF = sizeof(T) == 2;
+  constexpr int RB = DP * 2, NCH = DP / 8, SWM = k_swm<DP>(), KS = DP / 32, NG = DP / 64;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = lane >> 4, c16 = lane & 15;
+  const int H = p.H, hd = p.hd, N = p.N;
+  EVT_LDS float* Ps = (EVT_LDS float*)smem + wave * PTILE;  // this wave's [16 queries][64 keys]
+  EVT_LDS char* Ks = (EVT_LDS char*)smem + 4 * PTILE * 4;   // bf16: one K block, [64][DP]
+  // this wave's (m, 1 / l) of head h, query c16 at [(h * 16 + c16) * 2]
+  EVT_LDS float* St = (EVT_LDS float*)(smem + 4 * PTILE * 4 + (BF ? KB * DP * 2 : 0)) + wave * 32 * H;
+  int b, qb;  // workgroups of one image read the same K: on one XCD (speed only), as attn_probs_kernel
+  {
+    const int full = (p.B >> 3) * 8 * nqb, L = blockIdx.x;
+    if (L < full) {
+      b = (L & 7) + 8 * (L / (8 * nqb));
+      qb = (L >> 3) % nqb;
+    } else {
+      b = (p.B & ~7) + (L - full) / nqb;
+      qb = (L - full) % nqb;
+    }
+  }
+  const T* image = (const T*)p.qkv + b * p.sb;
+  const T* slice = image;  // q of the (image, head); k at + ko
+  const int nqt = (N + 15) >> 4, nkb = (N + KB - 1) / KB;
+  const int qt = qb * 4 + wave;
+  const bool active = qt < nqt;  // wave-uniform
+  if constexpr (!BF) {
+    if (!active) return;  // no barrier in the fp32 kernel
+  }
+  const int64_t qoff = (int64_t)min(qt * 16 + c16, N - 1) * p.ldq;
+  const T* qrow = slice + qoff;
+  const float c = p.scale_log2;
+  u32x4 qf[BF ? KS : 1];
+
+  // head h's slice, this lane's q row of it and, for bf16, its q fragments
+  auto head = [&](int h) {
+    slice = image + h * p.sh;
+    qrow = slice + qoff;
+    if constexpr (BF) {
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) qf[ks] = chunk8((const bf16*)qrow, 32 * ks + 8 * g, hd);
+    }
+  };
+  // bf16: key block kb of K into LDS, 16-B chunk ch of row r at chunk ch ^ (r & SWM)
+  auto stage = [&](int kb) {
+    for (int i = tid; i < KB * NCH; i += 256) {
+      const int row = i / NCH, ch = i - row * NCH;
+      const bf16* rp = (const bf16*)slice + (int64_t)min(kb * KB + row, N - 1) * p.ldq + p.ko;
+      *(EVT_LDS u32x4*)(Ks + row * RB + ((ch ^ (row & SWM)) << 4)) = chunk8(rp, ch * 8, hd);
+    }
+  };
+  // s[kt][j] = S^T[key = kb*64 + kt*16 + 4g + j][query = qt*16 + c16], -inf for keys past N
+  auto scores = [&](int kb, f32x4(&s)[NKT]) {
+    if constexpr (BF) {
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt) {
+        const int row = kt * 16 + c16;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          const u32x4 kf = *(const EVT_LDS u32x4*)(Ks + row * RB + (((4 * ks + g) ^ (row & SWM)) << 4));
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf),
+                                                        __builtin_bit_cast(bf16x8, qf[ks]), acc, 0, 0, 0);
+        }
+        s[kt] = acc;
+      }
+    } else {
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt) s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int kk = 0; kk < 4 * NG; ++kk) {
+        const int d0 = 16 * kk + 4 * g;
+        const f32x4 qv = chunk4((const float*)qrow, d0, hd);
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt) {
+          const float* krow =
+              (const float*)slice + (int64_t)min(kb * KB + kt * 16 + c16, N - 1) * p.ldq + p.ko;
+          const f32x4 kv = chunk4(krow, d0, hd);
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            s[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kv[e], qv[e], s[kt], 0, 0, 0);
+        }
+      }
+    }
+    if ((kb + 1) * KB > N) {  // wave-uniform: only the last block holds keys past N
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (kb * KB + kt * 16 + 4 * g + j >= N) s[kt][j] = -INFINITY;
+    }
+  };
+
+  // ---- pass 1, head by head: m = max_j s, l = sum_j 2^((s - m) c) (attn_probs_kernel's pass 1)
+  for (int h = 0; h < H; ++h) {
+    head(h);
+    float m = -INFINITY, l = 0.f;
+    for (int kb = 0; kb < nkb; ++kb) {
+      if constexpr (BF) {
+        __syncthreads();  // every wave is done with the block staged before
+        stage(kb);
+        __syncthreads();
+        if (!active) continue;
+      }
+      f32x4 s[NKT];
+      scores(kb, s);
+      float bm = s[0][0];
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bm = fmaxf(bm, s[kt][j]);
+      bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
+      bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+      const float mn = fmaxf(m, bm);
+      float sum = 0.f;
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sum += ex2<BF>((s[kt][j] - mn) * c);
+      l = l * ex2<BF>((m - mn) * c) + sum;
+      m = mn;
+    }
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    if (active && g == 0) *(EVT_LDS f32x2*)(St + (h * 16 + c16) * 2) = f32x2{m, 1.0f / l};
+  }
+  // the table is this wave's alone: LDS operations of a wave complete in order
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+  // ---- pass 2, key block by key block: sum_h p in head order, times fl(1 / H), stored by rows
+  const int64_t row0 = ((int64_t)b * N + (int64_t)qt * 16) * N;  // element offset of the tile's row 0
+  for (int kb = 0; kb < nkb; ++kb) {
+    f32x4 acc[NKT];
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) acc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int h = 0; h < H; ++h) {
+      head(h);
+      if constexpr (BF) {
+        __syncthreads();
+        stage(kb);
+        __syncthreads();
+        if (!active) continue;
+      }
+      f32x4 s[NKT];
+      scores(kb, s);
+      const f32x2 ml = *(const EVT_LDS f32x2*)(St + (h * 16 + c16) * 2);
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float pv = ex2<BF>((s[kt][j] - ml[0]) * c) * ml[1];  // the export's value, rounded
+          acc[kt][j] += pv;                                          // on its own, then added
+        }
+    }
+    if (!active) continue;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+      *(EVT_LDS f32x4*)(Ps + c16 * PROW + kt * 16 + 4 * g) = acc[kt] * inv_h;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int nk = min(KB, N - kb * KB);  // keys of this block
+    for (int r = 0; r < 16 && qt * 16 + r < N; ++r) {
+      const float v = Ps[r * PROW + lane];
+      if (lane < nk) out[row0 + (int64_t)r * N + kb * KB + lane] = v;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+size_t head_mean_lds(int elem, int DP, int H) {
+  return 4 * PTILE * 4 + (elem == 2 ? (size_t)KB * DP * 2 : 0) + (size_t)4 * 32 * H * sizeof(float);
+}
+
+template <typename T, int DP>
+hipError_t launch_head_mean(const AttnParams& p, int nqb, float* out, hipStream_t s) {
+  const size_t lds = head_mean_lds(sizeof(T), DP, p.H);
+  if (lds > 64 * 1024) {  // many heads: the table takes the LDS past the default limit
+    const hipError_t e = hipFuncSetAttribute((const void*)head_mean_kernel<T, DP>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL((head_mean_kernel<T, DP>), dim3(p.B * nqb), dim3(256), lds, s, p, nqb,
+                     1.0f / (float)p.H, out);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t head_mean_launch(int dtype, const AttnParams& p_in, float* out, hipStream_t s) {
+  if (p_in.B <= 0) return hipSuccess;
+  if (!p_in.qkv || !out || p_in.N <= 0 || p_in.N > EVT_ATTN_MAX_TOKENS || p_in.H <= 0 ||
+      p_in.hd <= 0 || p_in.hd > 128 || ((uintptr_t)out & 15))
+    return hipErrorInvalidValue;
+  // (s - m) c <= 0 and the -inf masks need c > 0
+  if (!(p_in.scale_log2 > 0.f && p_in.scale_log2 < INFINITY)) return hipErrorInvalidValue;
+  if (head_mean_lds(2, 128, p_in.H) > 160 * 1024) return hipErrorInvalidValue;  // H <= 254
+  AttnParams p = p_in;
+  if (p.sb || p.sh || p.ko) {  // an explicit slice layout: bf16, h_k = 64, 16-B aligned pieces
+    if (dtype != DT_BF16 || p.hd != 64 || p.sb % 8 || p.sh % 8 || p.ldq % 8 || p.ko % 8 ||
+        p.ldq < 64 || p.ko < 0 || p.sb < 0 || p.sh < 0)
+      return hipErrorInvalidValue;
+  } else {
+    p.sb = (int64_t)p.N * p.ldq;
+    p.sh = p.hd;
+    p.ko = p.H * p.hd;
+  }
+  const int nqb = ((p.N + 15) / 16 + 3) / 4;
+  if ((int64_t)p.B * nqb > INT32_MAX) return hipErrorInvalidValue;
+  if (dtype == DT_BF16) {
+    if (p.hd <= 32) return launch_head_mean<bf16, 32>(p, nqb, out, s);
+    if (p.hd <= 64) return launch_head_mean<bf16, 64>(p, nqb, out, s);
+    if (p.hd <= 96) return launch_head_mean<bf16, 96>(p, nqb, out, s);
+    return launch_head_mean<bf16, 128>(p, nqb, out, s);
+  }
+  if (dtype != DT_F32) return hipErrorInvalidValue;
+  if (p.hd <= 64) return launch_head_mean<float, 64>(p, nqb, out, s);
+  return launch_head_mean<float, 128>(p, nqb, out, s);
+}
+
 // ---- Swin window attention maps (include/evt_window_attention.h) -------------------------------
 //
 //   out[b][win][h][q][k] = softmax_k(q_q . k_k 32^-0.5 + rpb[rel(q, k)][h] + mask(win, q, k))

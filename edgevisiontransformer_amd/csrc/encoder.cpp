@@ -169,6 +169,7 @@ int run_encoder(evt_model* m, ForwardCall& call) {
     }
     EVT_RC(attn_map(m, call, block, ap));
     EVT_RC(head_stats(m, call, block, ap));
+    EVT_RC(rollout_step(m, call, block, ap));
     // out-proj + bias + LN1(x) residual -> xm (+ stats); STANDARD: + x
     DenseCall co;
     co.flags = m->standard ? (EPI_BIAS | EPI_RESID | EPI_STATS)

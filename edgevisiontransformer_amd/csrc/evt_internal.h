@@ -147,6 +147,20 @@ hipError_t attn_probs_launch(int dtype, const AttnParams& p, int nq, float* out,
 // columns ((N - prefix) % grid_w == 0). One launch, no scratch; out 16-byte aligned.
 hipError_t head_stats_launch(int dtype, const AttnParams& p, int prefix, int grid_w, float* out,
                              hipStream_t s);
+// Attention rollout (include/evt_rollout.h). head_mean_launch (attn_maps.hip): out[b][i][j] =
+// (sum_h p[b][h][i][j]) * fl(1 / H) of the same probabilities, heads added in index order, fp32
+// contiguous [B][N][N]; p as attn_probs_launch, out 16-byte aligned, H <= 254.
+hipError_t head_mean_launch(int dtype, const AttnParams& p, float* out, hipStream_t s);
+// rollout_step_launch (rollout.hip): r_out[b] = 0.5 (r_in[b] + abar[b] @ r_in[b]) on [B][N][N]
+// fp32, exact fp32 MFMA; r_in == nullptr: r_out = 0.5 (abar + I) and nothing else is read. nq = N
+// writes [B][N][N], nq = 1 row 0 of every image as [B][N] (bitwise row 0 of the nq = N result).
+// r_in must not overlap r_out. N <= EVT_ATTN_MAX_TOKENS.
+hipError_t rollout_step_launch(const float* abar, const float* r_in, float* r_out, int B, int N,
+                               int nq, hipStream_t s);
+// bytes of one [B][N][N] fp32 rollout buffer inside the caller's scratch (a multiple of 256)
+inline size_t rollout_buf_bytes(int B, int N) {
+  return (((size_t)B * N * N * sizeof(float)) + 255) & ~(size_t)255;
+}
 
 
 // LayerNorm over rows of D (fp32 in) -> activation dtype out (eps 1e-5).

@@ -253,6 +253,35 @@ int head_stats(evt_model* m, ForwardCall& call, int block, const AttnParams& ap)
   return EVT_OK;
 }
 
+// Scratch layout of a rollout call (include/evt_rollout.h): the head mean, then up to two rollout
+// buffers that alternate (a step cannot run in place); the last step writes the caller's output
+static int rollout_bufs(int depth) { return 1 + std::min(depth - 1, 2); }
+
+// At the same point of an evt_forward_rollout call, from block `start` on: the block's head mean
+// into the scratch and one rollout step on it (attn_maps.hip, rollout.hip; two launches, counted
+// under EVT_PROF_HEAD). Step 0 reads no rollout (R = I); the last block writes a->out, in
+// EVT_ROLLOUT_CLS mode its row 0 alone.
+int rollout_step(evt_model* m, ForwardCall& call, int block, const AttnParams& ap) {
+  const evt_rollout_args* a = call.rollout;
+  if (!a || block < a->start) return EVT_OK;
+  const int step = block - a->start, N = ap.N;
+  const bool last = block + 1 == (int)m->layers.size();
+  const size_t buf = rollout_buf_bytes(ap.B, N);
+  float* abar = (float*)a->scratch;
+  auto r = [&](int i) { return (float*)((char*)a->scratch + (size_t)(1 + (i & 1)) * buf); };
+  const int nq = last && a->mode == EVT_ROLLOUT_CLS ? 1 : N;
+  ProfScope ps(m, EVT_PROF_HEAD, call.s);
+  const double bh = (double)ap.B * ap.H, bnn = (double)ap.B * N * N;
+  prof_work(m, 4.0 * bh * N * (double)N * ap.hd + (step ? 2.0 * ap.B * nq * (double)N * N : 0.0),
+            bh * 2.0 * N * ap.hd * elem_size(m->dtype) + 4.0 * (2.0 * bnn + (step ? bnn : 0.0)) +
+                4.0 * ap.B * nq * (double)N * (step ? 2.0 : 1.0));
+  EVT_HIP(head_mean_launch(m->dtype, ap, abar, call.s), "rollout head mean");
+  EVT_HIP(rollout_step_launch(abar, step ? r(step - 1) : nullptr, last ? a->out : r(step), ap.B, N,
+                              nq, call.s),
+          "rollout step");
+  return EVT_OK;
+}
+
 // The Swin counterpart (evt_forward_window_attention): while ws.qkv holds block `block`'s LN1-folded
 // QKV rows that `ap` describes, the block's window map, if it is the next one asked for
 bool window_attn_wanted(const ForwardCall& call, int block) {
@@ -800,6 +829,61 @@ int evt_forward_head_stats(evt_model* m, const evt_image_args* in, int B,
   ForwardCall call = image_call(in, aff, B, feat ? feat->logits : nullptr, stream);
   call.feat = feat;
   call.hstats = a;
+  // one lane, on this handle's own workspace, whatever its lane count (as evt_forward_attention)
+  return forward(m, call, false);
+}
+
+// ---- attention rollout (include/evt_rollout.h) ----------------------------------------------
+
+static int rollout_family(const evt_model* m) {
+  if (m->family == FAM_SWIN)
+    return fail(EVT_EINVAL, "attention rollout: Swin's windowed attention does not compose this way "
+                            "(per-window maps: evt_forward_window_attention)");
+  EVT_RC(attn_family(m));
+  return EVT_OK;
+}
+
+int evt_rollout_shape(const evt_model* m, int* tokens, int* blocks) {
+  if (!m || !tokens || !blocks) return fail(EVT_EINVAL, "null argument");
+  EVT_RC(rollout_family(m));
+  *tokens = m->sh.T;
+  *blocks = (int)m->layers.size();
+  return EVT_OK;
+}
+
+int evt_rollout_scratch_bytes(const evt_model* m, int B, int mode, size_t* bytes) {
+  if (!m || !bytes) return fail(EVT_EINVAL, "null argument");
+  EVT_RC(rollout_family(m));
+  if (mode != EVT_ROLLOUT_CLS && mode != EVT_ROLLOUT_ALL)
+    return fail(EVT_EINVAL, "rollout mode must be EVT_ROLLOUT_CLS or EVT_ROLLOUT_ALL");
+  EVT_RC(check_batch(m, B));
+  *bytes = (size_t)rollout_bufs((int)m->layers.size()) * rollout_buf_bytes(B, m->sh.T);
+  return EVT_OK;
+}
+
+int evt_forward_rollout(evt_model* m, const evt_image_args* in, int B,
+                        const evt_features_args* feat, const evt_rollout_args* a, void* stream) {
+  ImgAffine aff{};
+  if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and ro must be non-null");
+  EVT_RC(validate_image(m, in, &aff));
+  EVT_RC(rollout_family(m));
+  if (feat) EVT_RC(validate_features(m, feat, B));
+  else EVT_RC(check_batch(m, B));
+  const int depth = (int)m->layers.size();
+  if (a->start < 0 || a->start >= depth)
+    return fail(EVT_EINVAL, "rollout start must be in [0, " + std::to_string(depth) + ")");
+  if (a->mode != EVT_ROLLOUT_CLS && a->mode != EVT_ROLLOUT_ALL)
+    return fail(EVT_EINVAL, "rollout mode must be EVT_ROLLOUT_CLS or EVT_ROLLOUT_ALL");
+  if (!a->out || !a->scratch) return fail(EVT_EINVAL, "rollout out and scratch must be non-null");
+  if (((uintptr_t)a->out | (uintptr_t)a->scratch) & 15)
+    return fail(EVT_EINVAL, "rollout out and scratch must be 16-byte aligned");
+  const size_t need = (size_t)rollout_bufs(depth) * rollout_buf_bytes(B, m->sh.T);
+  if (a->scratch_bytes < need)
+    return fail(EVT_EINVAL, "rollout scratch_bytes is " + std::to_string(a->scratch_bytes) +
+                                ", this call needs " + std::to_string(need));
+  ForwardCall call = image_call(in, aff, B, feat ? feat->logits : nullptr, stream);
+  call.feat = feat;
+  call.rollout = a;
   // one lane, on this handle's own workspace, whatever its lane count (as evt_forward_attention)
   return forward(m, call, false);
 }

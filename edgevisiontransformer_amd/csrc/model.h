@@ -229,6 +229,7 @@ struct ForwardCall {
   int attn_next = 0;              // the next entry of attn's block list
   const evt_head_stats_args* hstats = nullptr;  // evt_forward_head_stats blocks (null: none)
   int hstats_next = 0;            // the next entry of hstats' block list
+  const evt_rollout_args* rollout = nullptr;  // evt_forward_rollout (null: none)
   hipStream_t s = nullptr;
   // images [b0, b1) of a logits-only call, on stream `lane`: the input advances by whole images
   // (4 bytes per element of an fp32 batch, 1 of a uint8 one), the logits by rows
@@ -364,6 +365,8 @@ int feat_tap(evt_model* m, ForwardCall& call, int block, int64_t ldx, int rows, 
 int attn_map(evt_model* m, ForwardCall& call, int block, const AttnParams& ap);
 // evt_forward_head_stats: block's statistics, if the call asks for them next (beside attn_map)
 int head_stats(evt_model* m, ForwardCall& call, int block, const AttnParams& ap);
+// evt_forward_rollout: block's head mean and rollout step, from the call's start block on
+int rollout_step(evt_model* m, ForwardCall& call, int block, const AttnParams& ap);
 // evt_forward_window_attention (Swin): whether the call asks for block's map next, and the export
 bool window_attn_wanted(const ForwardCall& call, int block);
 int window_attn_map(evt_model* m, ForwardCall& call, int block, int w, const SwinAttnParams& ap);

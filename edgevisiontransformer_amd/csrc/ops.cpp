@@ -435,6 +435,52 @@ int evt_attention_head_stats(int dtype, const void* qkv, int64_t ldq, int64_t sb
   return EVT_OK;
 }
 
+// include/evt_rollout.h: evt_attention_probs' checks of (qkv, layout, shape, scale), then the
+// rollout buffers and the scratch; two launches (the head mean into the scratch, then the step)
+int evt_attention_rollout_step(int dtype, const void* qkv, int64_t ldq, int64_t sb, int64_t sh,
+                               int ko, int B, int N, int H, int head_dim, float scale,
+                               const float* r_in, float* r_out, void* scratch, size_t scratch_bytes,
+                               void* stream) {
+  if (dtype != EVT_DTYPE_F32 && dtype != EVT_DTYPE_BF16)
+    return fail(EVT_EINVAL, "attention_rollout_step: dtype must be EVT_DTYPE_F32 or EVT_DTYPE_BF16");
+  if (!qkv || !r_out || !scratch || B < 0 || N <= 0 || N > EVT_ATTN_MAX_TOKENS || H <= 0 ||
+      H > 254 || head_dim <= 0 || head_dim > 128)
+    return fail(EVT_EINVAL, "attention_rollout_step: bad shape (N <= 4096, H <= 254, head size in "
+                            "[1, 128]) or a NULL qkv, r_out or scratch");
+  if (!(scale > 0.f && scale < INFINITY))
+    return fail(EVT_EINVAL, "attention_rollout_step: the scale must be positive and finite");
+  if (((uintptr_t)r_in | (uintptr_t)r_out | (uintptr_t)scratch) & 15)
+    return fail(EVT_EINVAL, "attention_rollout_step: r_in, r_out and scratch must be 16-byte aligned");
+  const size_t bytes = (size_t)B * N * N * sizeof(float);
+  if (scratch_bytes < bytes)
+    return fail(EVT_EINVAL, "attention_rollout_step: scratch_bytes must be at least B*N*N*4");
+  const uintptr_t ri = (uintptr_t)r_in, ro = (uintptr_t)r_out;
+  if (r_in && (ri == ro || (ri < ro + bytes && ro < ri + bytes)))
+    return fail(EVT_EINVAL, "attention_rollout_step: r_in must not overlap r_out (a step cannot run "
+                            "in place)");
+  const int64_t vec = dtype == DT_BF16 ? 8 : 4;
+  if (sb || sh || ko) {
+    if (dtype != DT_BF16 || head_dim != 64 || sb < 0 || sh < 0 || ko < 0 || sb % 8 || sh % 8 ||
+        ko % 8 || ldq % 8 || ldq < 64 || ((uintptr_t)qkv & 15))
+      return fail(EVT_EINVAL, "attention_rollout_step: a slice layout needs bf16, head size 64 and "
+                              "non-negative strides that are multiples of 8");
+  } else {
+    if (ldq < 3 * (int64_t)H * head_dim)
+      return fail(EVT_EINVAL, "attention_rollout_step: ldq must be at least 3*H*head_dim");
+    if (head_dim % vec == 0 && (ldq % vec || ((uintptr_t)qkv & 15)))
+      return fail(EVT_EINVAL,
+                  "attention_rollout_step: qkv rows must be 16-B aligned for this head size");
+  }
+  AttnParams p{qkv, ldq, nullptr, 0, N, H, B, scale * 1.4426950408889634f};
+  p.hd = head_dim;
+  p.sb = sb; p.sh = sh; p.ko = ko;
+  EVT_HIP(head_mean_launch(dtype, p, (float*)scratch, (hipStream_t)stream),
+          "attention_rollout_step (head mean)");
+  EVT_HIP(rollout_step_launch((const float*)scratch, r_in, r_out, B, N, N, (hipStream_t)stream),
+          "attention_rollout_step");
+  return EVT_OK;
+}
+
 int evt_window_attention_probs(int dtype, const void* qkv, int64_t ldq, const float* rpb, int B,
                                int R, int window, int C, int H, int shift, float* out,
                                void* stream) {
