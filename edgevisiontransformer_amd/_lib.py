@@ -236,6 +236,24 @@ HEAD_STATS_SIGNATURES = {
                                       _P, _P]),
 }
 
+class evt_ffn_stats_args(ctypes.Structure):
+    _fields_ = [("n_blocks", ctypes.c_int32), ("blocks", ctypes.POINTER(ctypes.c_int32)),
+                ("stats", ctypes.POINTER(ctypes.c_void_p))]
+
+
+# include/evt_ffn_stats.h constants: EVT_FFN_STATS and the index of each statistic
+FFN_STATS = 4
+FFN_MEAN, FFN_MEAN_ABS, FFN_MEAN_SQ, FFN_MAX_ABS = 0, 1, 2, 3
+# the entry points of include/evt_ffn_stats.h (evt.h includes it; bound like SIGNATURES)
+FFN_STATS_SIGNATURES = {
+    "evt_ffn_stats_shape": (_I, [_P, _I, _PI, _PI]),
+    "evt_forward_ffn_stats": (_I, [_P, ctypes.POINTER(evt_image_args), _I,
+                                   ctypes.POINTER(evt_features_args),
+                                   ctypes.POINTER(evt_ffn_stats_args), _P]),
+    "evt_ffn_neuron_stats": (_I, [_I, _P, _I64, _I, _I, _I, _P, _P]),
+}
+
+
 class evt_rollout_args(ctypes.Structure):
     _fields_ = [("start", ctypes.c_int32), ("mode", ctypes.c_int32), ("out", ctypes.c_void_p),
                 ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t)]
@@ -322,7 +340,7 @@ def load_library() -> ctypes.CDLL:
                                       **IMAGE_SIGNATURES, **PREPROCESS_SIGNATURES,
                                       **ATTENTION_SIGNATURES, **WINDOW_ATTENTION_SIGNATURES,
                                       **TAIL_SIGNATURES, **HEAD_STATS_SIGNATURES,
-                                      **ROLLOUT_SIGNATURES,
+                                      **ROLLOUT_SIGNATURES, **FFN_STATS_SIGNATURES,
                                       **CLASSIFY_SIGNATURES, **WORKSPACE_SIGNATURES,
                                       **PERFORMER_SIGNATURES}.items():
                 if lenient and not hasattr(lib, name):

@@ -15,9 +15,9 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libevt_hip.so")
 OBJ = os.path.join(HERE, "build_obj")
 SOURCES = ["gemm.hip", "attention.hip", "norm.hip", "t2t.hip", "swin.hip", "mx8.hip",
-           "features.hip", "preprocess.hip", "attn_maps.hip", "rollout.hip", "model.cpp",
-           "encoder.cpp", "model_vit.cpp", "model_t2t.cpp", "model_swin.cpp", "ops.cpp",
-           "resize_plan.cpp"]
+           "features.hip", "preprocess.hip", "attn_maps.hip", "rollout.hip", "ffn_stats.hip",
+           "model.cpp", "encoder.cpp", "model_vit.cpp", "model_t2t.cpp", "model_swin.cpp",
+           "ops.cpp", "resize_plan.cpp"]
 # the GEMM kernels, one header per kernel, all included by gemm.hip (one translation unit)
 GEMM_HEADERS = ["gemm_epi.h", "gemm_nt.h", "gemm_big8.h", "gemm_big.h", "gemm_pers.h",
                 "gemm_p384.h", "gemm_sk.h"]
@@ -29,6 +29,7 @@ HEADERS = GEMM_HEADERS + [
            os.path.join("..", "..", "include", "evt_preprocess.h"),
            os.path.join("..", "..", "include", "evt_attention_maps.h"),
            os.path.join("..", "..", "include", "evt_head_stats.h"),
+           os.path.join("..", "..", "include", "evt_ffn_stats.h"),
            os.path.join("..", "..", "include", "evt_rollout.h"),
            os.path.join("..", "..", "include", "evt_window_attention.h"),
            os.path.join("..", "..", "include", "evt_tail.h"),

@@ -157,6 +157,10 @@ int run_encoder(evt_model* m, ForwardCall& call) {
       const evt_features_args* a = call.feat;
       full = a->tokens || (a->n_taps > 0 && a->tap_blocks[a->n_taps - 1] == block);
     }
+    // the last block's FFN statistics are those of the full-row FC1 launch (evt_ffn_stats.h)
+    if (last && call.fstats && call.fstats->n_blocks > 0 &&
+        call.fstats->blocks[call.fstats->n_blocks - 1] == block)
+      full = true;
     if (last) m->tail_mode = full ? 3 : 1;
     {
       ProfScope ps(m, EVT_PROF_ATTENTION, s);
@@ -217,6 +221,7 @@ int run_encoder(evt_model* m, ForwardCall& call) {
       if (full) EVT_RC(dense(m, L.fc1, c1, s));
       if (last) EVT_RC(dense(m, L.fc1, tail(c1), s));
     }
+    if (full) EVT_RC(ffn_stats(m, call, block, L, rows));
     {
       ProfScope ps(m, EVT_PROF_FC2, s);
       if (full) EVT_RC(dense(m, L.fc2, c2, s));

@@ -162,6 +162,15 @@ inline size_t rollout_buf_bytes(int B, int N) {
   return (((size_t)B * N * N * sizeof(float)) + 255) & ~(size_t)255;
 }
 
+// FFN neuron statistics (ffn_stats.hip; include/evt_ffn_stats.h): out[b][j][0..3] = (mean, mean_abs,
+// mean_sq, max_abs) over the T rows of image b of column j < F of the row-major matrix h (B T rows,
+// pitch ld elements, dtype bf16 or f32), fp32 contiguous [B][F][4]. One launch, no scratch; h and
+// out 16-byte aligned, ld >= F and a multiple of 16 bytes of elements, 1 <= T <= 4096
+// (hipErrorInvalidValue otherwise).
+constexpr int FFN_STATS_MAX_TOKENS = 4096;  // EVT_FFN_STATS_MAX_TOKENS of the header
+hipError_t ffn_stats_launch(int dtype, const void* h, int64_t ld, int B, int T, int F, float* out,
+                            hipStream_t s);
+
 
 // LayerNorm over rows of D (fp32 in) -> activation dtype out (eps 1e-5).
 hipError_t layernorm_launch(int dtype, const float* x, int64_t ldx, void* y, int64_t ldy,

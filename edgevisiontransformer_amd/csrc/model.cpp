@@ -253,6 +253,21 @@ int head_stats(evt_model* m, ForwardCall& call, int block, const AttnParams& ap)
   return EVT_OK;
 }
 
+// Between the full-row FC1 and FC2 of an evt_forward_ffn_stats call, while ws.hbuf holds block
+// `block`'s hidden rows: the block's four statistics per neuron, if they were asked for
+// (ffn_stats.hip; counted under EVT_PROF_HEAD)
+int ffn_stats(evt_model* m, ForwardCall& call, int block, const Layer& L, int rows) {
+  const evt_ffn_stats_args* a = call.fstats;
+  if (!a || call.fstats_next >= a->n_blocks || a->blocks[call.fstats_next] != block) return EVT_OK;
+  ProfScope ps(m, EVT_PROF_HEAD, call.s);
+  prof_work(m, 5.0 * rows * (double)L.ffn,  // |a|, three adds (one fused with a^2) and a max
+            (double)rows * L.ffn * elem_size(m->dtype) + 4.0 * call.B * L.ffn * EVT_FFN_STATS);
+  EVT_HIP(ffn_stats_launch(m->dtype, m->ws.hbuf, L.ffn_st, call.B, rows / call.B, L.ffn,
+                           a->stats[call.fstats_next++], call.s),
+          "ffn statistics");
+  return EVT_OK;
+}
+
 // Scratch layout of a rollout call (include/evt_rollout.h): the head mean, then up to two rollout
 // buffers that alternate (a step cannot run in place); the last step writes the caller's output
 static int rollout_bufs(int depth) { return 1 + std::min(depth - 1, 2); }
@@ -829,6 +844,63 @@ int evt_forward_head_stats(evt_model* m, const evt_image_args* in, int B,
   ForwardCall call = image_call(in, aff, B, feat ? feat->logits : nullptr, stream);
   call.feat = feat;
   call.hstats = a;
+  // one lane, on this handle's own workspace, whatever its lane count (as evt_forward_attention)
+  return forward(m, call, false);
+}
+
+// ---- FFN neuron statistics (include/evt_ffn_stats.h) ----------------------------------------
+
+// the users of run_encoder: Swin's fused MLP never stores its hidden rows, the MX8 encoder keeps
+// them quantised
+static int ffn_stats_family(const evt_model* m) {
+  if (m->family == FAM_SWIN)
+    return fail(EVT_EINVAL, "FFN statistics: Swin's fused MLP does not store its hidden rows");
+  if (m->mx8)
+    return fail(EVT_EINVAL, "FFN statistics are not available on an EVT_DTYPE_MX8 model (its "
+                            "hidden rows are kept quantised)");
+  return EVT_OK;
+}
+
+int evt_ffn_stats_shape(const evt_model* m, int block, int* neurons, int* tokens) {
+  if (!m || !neurons || !tokens) return fail(EVT_EINVAL, "null argument");
+  EVT_RC(ffn_stats_family(m));
+  if (block < 0 || block >= (int)m->layers.size())
+    return fail(EVT_EINVAL, "block must be in [0, " + std::to_string(m->layers.size()) + ")");
+  *neurons = m->layers[block].ffn;
+  *tokens = m->sh.T;
+  return EVT_OK;
+}
+
+int evt_forward_ffn_stats(evt_model* m, const evt_image_args* in, int B,
+                          const evt_features_args* feat, const evt_ffn_stats_args* a,
+                          void* stream) {
+  ImgAffine aff{};
+  if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and fs must be non-null");
+  EVT_RC(validate_image(m, in, &aff));
+  EVT_RC(ffn_stats_family(m));
+  if (a->n_blocks < 0 || a->n_blocks > 64) return fail(EVT_EINVAL, "n_blocks must be in [0, 64]");
+  if (a->n_blocks == 0 && !feat)
+    return fail(EVT_EINVAL, "no output requested: n_blocks is 0 and feat is NULL");
+  if (feat) EVT_RC(validate_features(m, feat, B));
+  else EVT_RC(check_batch(m, B));
+  if (a->n_blocks > 0) {
+    if (!a->blocks || !a->stats)
+      return fail(EVT_EINVAL, "n_blocks > 0 needs the blocks and stats arrays");
+    const int nb = (int)m->layers.size();
+    for (int i = 0; i < a->n_blocks; ++i) {
+      if (a->blocks[i] < 0 || a->blocks[i] >= nb)
+        return fail(EVT_EINVAL, "FFN statistics block " + std::to_string(a->blocks[i]) +
+                                    " is outside [0, " + std::to_string(nb) + ")");
+      if (i > 0 && a->blocks[i] <= a->blocks[i - 1])
+        return fail(EVT_EINVAL, "FFN statistics blocks must be strictly increasing");
+      if (!a->stats[i]) return fail(EVT_EINVAL, "stats pointer " + std::to_string(i) + " is NULL");
+      if ((uintptr_t)a->stats[i] & 15)
+        return fail(EVT_EINVAL, "FFN statistics must be 16-byte aligned");
+    }
+  }
+  ForwardCall call = image_call(in, aff, B, feat ? feat->logits : nullptr, stream);
+  call.feat = feat;
+  call.fstats = a;
   // one lane, on this handle's own workspace, whatever its lane count (as evt_forward_attention)
   return forward(m, call, false);
 }

@@ -229,6 +229,8 @@ struct ForwardCall {
   int attn_next = 0;              // the next entry of attn's block list
   const evt_head_stats_args* hstats = nullptr;  // evt_forward_head_stats blocks (null: none)
   int hstats_next = 0;            // the next entry of hstats' block list
+  const evt_ffn_stats_args* fstats = nullptr;  // evt_forward_ffn_stats blocks (null: none)
+  int fstats_next = 0;            // the next entry of fstats' block list
   const evt_rollout_args* rollout = nullptr;  // evt_forward_rollout (null: none)
   hipStream_t s = nullptr;
   // images [b0, b1) of a logits-only call, on stream `lane`: the input advances by whole images
@@ -365,6 +367,9 @@ int feat_tap(evt_model* m, ForwardCall& call, int block, int64_t ldx, int rows, 
 int attn_map(evt_model* m, ForwardCall& call, int block, const AttnParams& ap);
 // evt_forward_head_stats: block's statistics, if the call asks for them next (beside attn_map)
 int head_stats(evt_model* m, ForwardCall& call, int block, const AttnParams& ap);
+// evt_forward_ffn_stats: block's neuron statistics of the `rows` hidden rows the full-row FC1 left in
+// ws.hbuf, if the call asks for them next (between FC1 and FC2)
+int ffn_stats(evt_model* m, ForwardCall& call, int block, const Layer& L, int rows);
 // evt_forward_rollout: block's head mean and rollout step, from the call's start block on
 int rollout_step(evt_model* m, ForwardCall& call, int block, const AttnParams& ap);
 // evt_forward_window_attention (Swin): whether the call asks for block's map next, and the export

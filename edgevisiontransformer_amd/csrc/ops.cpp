@@ -435,6 +435,24 @@ int evt_attention_head_stats(int dtype, const void* qkv, int64_t ldq, int64_t sb
   return EVT_OK;
 }
 
+// include/evt_ffn_stats.h
+int evt_ffn_neuron_stats(int dtype, const void* h, int64_t ld, int B, int T, int F, float* out,
+                         void* stream) {
+  if (dtype != EVT_DTYPE_F32 && dtype != EVT_DTYPE_BF16)
+    return fail(EVT_EINVAL, "ffn_neuron_stats: dtype must be EVT_DTYPE_F32 or EVT_DTYPE_BF16");
+  if (!h || !out || B < 1 || T < 1 || T > EVT_FFN_STATS_MAX_TOKENS || F < 1)
+    return fail(EVT_EINVAL, "ffn_neuron_stats: bad shape (B >= 1, 1 <= T <= 4096, F >= 1)");
+  static_assert(EVT_FFN_STATS_MAX_TOKENS == FFN_STATS_MAX_TOKENS, "header and kernel agree");
+  const int64_t vec = dtype == DT_BF16 ? 8 : 4;
+  if (ld < F || ld % vec)
+    return fail(EVT_EINVAL, "ffn_neuron_stats: ld must be at least F and the row pitch a multiple "
+                            "of 16 bytes");
+  if (((uintptr_t)h | (uintptr_t)out) & 15)
+    return fail(EVT_EINVAL, "ffn_neuron_stats: h and out must be 16-byte aligned");
+  EVT_HIP(ffn_stats_launch(dtype, h, ld, B, T, F, out, (hipStream_t)stream), "ffn_neuron_stats");
+  return EVT_OK;
+}
+
 // include/evt_rollout.h: evt_attention_probs' checks of (qkv, layout, shape, scale), then the
 // rollout buffers and the scratch; two launches (the head mean into the scratch, then the step)
 int evt_attention_rollout_step(int dtype, const void* qkv, int64_t ldq, int64_t sb, int64_t sh,

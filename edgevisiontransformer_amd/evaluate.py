@@ -116,3 +116,44 @@ def collect_head_stats(model, loader: Iterable, transform=None, blocks=None):
     if not seen:
         raise ValueError("collect_head_stats: the loader gave no images")
     return [(s / seen).cpu().numpy() for s in sums]
+
+
+def collect_ffn_stats(model, loader: Iterable, transform=None, blocks=None):
+    """Dataset statistics of the FFN neurons (modeling/models/ffn_stats.py): one fp64 [F_i, 4]
+    array per block (`blocks=None`: every block; negative indices and any order as `ffn_stats`),
+    columns in FFN_STATS order. mean, mean_abs and mean_sq are the means over the dataset's images
+    of the per-image values (every image has the same number of tokens, so they are the means over
+    all tokens of the dataset); max_abs is the maximum over the dataset.
+
+    `loader` yields what `evaluate` takes: (images, target) tuples, of which the target is not
+    read, or the images alone. Each batch's [B, F_i, 4] is reduced over its images on the device
+    (an fp64 sum of columns 0-2, a maximum of column 3) into per-block fp64 device tensors that
+    live for the whole loop; the host reads once, at the end. Every image weighs the same, whatever
+    its batch's size."""
+    import torch
+
+    from .modeling.models.features import resolve_taps
+    device = model.device
+    on_device = torch.cuda.device(device) if device.type == "cuda" else contextlib.nullcontext()
+    nb = model.num_blocks
+    idx = resolve_taps(range(nb) if blocks is None else blocks, nb)
+    widths = [model.ffn_stats_shape(i)[0] for i in idx]
+    sums = [torch.zeros((f, 3), dtype=torch.float64, device=device) for f in widths]
+    tops = [torch.zeros((f,), dtype=torch.float64, device=device) for f in widths]
+    bufs, seen = None, 0
+    for item in loader:
+        images = item[0] if isinstance(item, tuple) else item
+        x = _device_batch(model, images, transform)
+        b = x.shape[0]
+        if bufs is None or bufs[0].shape[0] < b:  # one set of buffers for the loop
+            bufs = [torch.empty((b, f, 4), dtype=torch.float32, device=device) for f in widths]
+        views = [t[:b] for t in bufs]
+        with on_device:
+            model.ffn_stats_into(x, blocks=idx, stat_tensors=views)
+            for s, top, v in zip(sums, tops, views):
+                s += v[:, :, :3].sum(dim=0, dtype=torch.float64)
+                torch.maximum(top, v[:, :, 3].amax(dim=0).double(), out=top)
+        seen += b
+    if not seen:
+        raise ValueError("collect_ffn_stats: the loader gave no images")
+    return [torch.cat([s / seen, top[:, None]], dim=1).cpu().numpy() for s, top in zip(sums, tops)]

@@ -24,7 +24,7 @@ import torch
 
 from ... import _lib
 from ...images import Uint8Images
-from .rollout import AttentionRollout
+from .ffn_stats import FFNStats
 
 VALUES = {"prob": _lib.CLASSIFY_PROB, "logit": _lib.CLASSIFY_LOGIT}
 MAX_CLASSES = 1 << 20
@@ -84,9 +84,9 @@ def classify_reference(logits, k: int, labels=None) -> Dict[str, np.ndarray]:
     return out
 
 
-class Classification(AttentionRollout):
+class Classification(FFNStats):
     """What ViT, T2T_ViT and SwinTransformer derive from: the classification outputs on top of the
-    attention rollout, head statistics, attention maps and feature outputs. Needs nothing of the
+    FFN statistics, attention rollout, head statistics, attention maps and feature outputs. Needs nothing of the
     model class but `cfg.num_classes`."""
 
     def _int_tensor(self, name: str, t, shape, dtype) -> int:

@@ -86,6 +86,11 @@ class T2T_ViT(Classification):
     def _patch_grid_w(self):
         return self.cfg.image_size // 16
 
+    # -- FFN statistics (ffn_stats.py): the encoder blocks' MLPs, not the token performers' -----
+    def _ffn_geometry(self):
+        c = self.cfg
+        return [(c.mlp_dim, c.tokens)] * c.depth
+
 
 def get_t2t_vit_7(**kw) -> T2T_ViT:
     return T2T_ViT(hidden_size=256, depth=7, num_heads=4, mlp_ratio=2, **kw)

@@ -134,6 +134,11 @@ class ViT(Classification):
     def _patch_grid_w(self):
         return self.cfg.image_size // self.cfg.patch_size
 
+    # -- FFN statistics (ffn_stats.py): a pruned model's FFN widths differ per block ------------
+    def _ffn_geometry(self):
+        c = self.cfg
+        return [(int(f), c.tokens) for f in list(c.ffn)[:c.depth]]
+
 
 class ViT_Pruned(ViT):
     """Head/FFN-pruned ViT (reference `ViT_Pruned`, vit.py:58-75)."""

@@ -132,6 +132,74 @@ def ffn_keep_by_norm(params: Dict[str, np.ndarray], layer: int, keep: int) -> Li
     return sorted(int(i) for i in np.argsort(-score, kind="stable")[:keep])
 
 
+def ffn_importance_from_stats(stats: Sequence[np.ndarray],
+                              params: Optional[Dict[str, np.ndarray]] = None,
+                              kind: str = "energy") -> List[np.ndarray]:
+    """Per-layer FFN neuron importances (one fp64 [F_l] array per layer; the widths may differ) from
+    the activation statistics of every block: `stats[l]` is a [F, 4] array (`collect_ffn_stats`) or
+    a [B, F, 4] one (`ffn_stats`: mean, mean_abs and mean_sq are averaged over its images, max_abs
+    is their maximum), columns in FFN_STATS order (modeling/models/ffn_stats.py). `kind`:
+
+        "energy"    mean_sq_j * ||params["l{l}.fc2_w"][j, :]||^2: the mean squared norm of what the
+                    neuron adds to the block's output
+        "mean_abs"  the statistic itself
+        "max_abs"   the statistic itself (0: a neuron dead on the whole sample)
+
+    A higher value is a more important neuron. ValueError: an unknown `kind`, no blocks, a
+    malformed array, "energy" without `params` or with an FC2 of another width."""
+    kinds = ("energy", "mean_abs", "max_abs")
+    if kind not in kinds:
+        raise ValueError(f"kind must be one of {kinds}, got {kind!r}")
+    if kind == "energy" and params is None:
+        raise ValueError('kind "energy" needs the parameter dict (the FC2 row norms)')
+    out = []
+    for l, s in enumerate(stats):
+        a = np.asarray(s, dtype=np.float64)
+        if a.ndim == 3 and a.shape[0] > 0:
+            a = np.concatenate([a[..., :3].mean(axis=0), a[..., 3:].max(axis=0)], axis=-1)
+        if a.ndim != 2 or a.shape[1] != 4 or a.shape[0] < 1:
+            raise ValueError(f"stats[{l}] must be [F, 4] or [B, F, 4], got {np.shape(s)}")
+        if kind == "energy":
+            w2 = np.asarray(params[f"l{l}.fc2_w"], dtype=np.float64)
+            if w2.ndim != 2 or w2.shape[0] != a.shape[0]:
+                raise ValueError(f"layer {l}: fc2_w has {w2.shape[0]} rows, the statistics "
+                                 f"{a.shape[0]} neurons")
+            out.append(a[:, 2] * (w2 * w2).sum(axis=1))
+        else:
+            out.append(a[:, 1 if kind == "mean_abs" else 3].copy())
+    if not out:
+        raise ValueError("no blocks given")
+    return out
+
+
+def ffn_keep_from_importance(importance: Sequence[np.ndarray],
+                             keep_per_layer: Optional[Sequence[int]] = None,
+                             fraction: Optional[float] = None) -> List[List[int]]:
+    """Kept FFN neurons per layer, as sorted index lists ready to be `kept_ffn` of
+    `prune_vit_params`: the most important `keep_per_layer[l]` of layer l, or
+    int(fraction * F_l) of them (the `d{fraction}` of a prune encoding), at least one per layer
+    either way. Ties go to the lower index. Exactly one of the two forms must be given."""
+    if (keep_per_layer is None) == (fraction is None):
+        raise ValueError("give exactly one of keep_per_layer and fraction")
+    layers = [np.asarray(v, dtype=np.float64) for v in importance]
+    if not layers or any(v.ndim != 1 or v.size < 1 for v in layers):
+        raise ValueError("importance must be a non-empty sequence of non-empty 1-D arrays")
+    if any(np.isnan(v).any() for v in layers):
+        raise ValueError("importance holds NaN")
+    if keep_per_layer is not None:
+        counts = [int(k) for k in keep_per_layer]
+        if len(counts) != len(layers):
+            raise ValueError("one keep count per layer")
+        if any(k < 0 or k > v.size for k, v in zip(counts, layers)):
+            raise ValueError(f"keep counts {counts} outside 0 .. the layers' widths")
+    else:
+        if not 0.0 <= fraction <= 1.0:
+            raise ValueError(f"fraction must be in [0, 1], got {fraction!r}")
+        counts = [int(fraction * v.size) for v in layers]
+    return [sorted(int(i) for i in np.argsort(-v, kind="stable")[:max(1, k)])
+            for k, v in zip(counts, layers)]
+
+
 def prune_vit_params(params: Dict[str, np.ndarray], cfg: ViTConfig, kept_heads: List[List[int]],
                      kept_ffn: Optional[List[List[int]]] = None,
                      head_size: int = 64) -> Tuple[Dict[str, np.ndarray], ViTConfig]:
