@@ -25,6 +25,7 @@
 //
 // More than 256 tokens per image (up to EVT_ATTN_MAX_TOKENS): the streaming kernels further down
 // (attn_long_*), the same products over 64-key blocks with an online softmax.
+#include "attn_scores.h"  // k_swm, chunk8, chunk4
 #include "common.h"
 #include "evt_internal.h"
 
@@ -406,30 +407,13 @@ __global__ __launch_bounds__(64 * ATTN_F32_WAVES) void attn_f32_kernel(AttnParam
 // bf16: one workgroup (4 waves) per (image, head). K and V rows are staged to LDS with the head
 // feature axis zero-padded to DP (h_k rounded up to 32, one k-step of v_mfma_f32_16x16x32_bf16),
 // rows of DP * 2 bytes, 16-B chunk c of row r at chunk c ^ (r & SWM) (SWM: 7 / 3 when the chunk
-// count is a power of two >= 8 / = 4, else unswizzled). S^T = K Q^T takes DP / 32 MFMA steps per
-// 16-key tile, O^T = V^T P^T DP / 16 output tiles with V^T from ds_read_b64_tr_b16.
-template <int DP>
-constexpr int gen_swm() {
-  constexpr int nch = DP / 8;
-  return nch == 4 ? 3 : ((nch >= 8 && (nch & (nch - 1)) == 0) ? 7 : 0);
-}
-
-// 8 consecutive head features [d0, d0 + 8) of row `row` (bf16), zero past h_k
-__device__ __forceinline__ u32x4 gen_chunk(const bf16* row, int d0, int hd) {
-  if ((hd & 7) == 0) {
-    if (d0 < hd) return *(const u32x4*)(row + d0);
-    return u32x4{0u, 0u, 0u, 0u};
-  }
-  bf16x8 v;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) v[e] = d0 + e < hd ? row[d0 + e] : (bf16)0.f;
-  return __builtin_bit_cast(u32x4, v);
-}
-
+// count is a power of two >= 8 / = 4, else unswizzled: k_swm). S^T = K Q^T takes DP / 32 MFMA steps
+// per 16-key tile, O^T = V^T P^T DP / 16 output tiles with V^T from ds_read_b64_tr_b16. Rows are
+// read in zero-padded chunks (chunk8; fp32: chunk4), shared with the map kernels (attn_scores.h).
 template <int NKT, int DP>
 __global__ __launch_bounds__(256) void attn_gen_bf16_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int NP = NKT * 16, NCH = DP / 8, RB = DP * 2, SWM = gen_swm<DP>(), KS = DP / 32;
+  constexpr int NP = NKT * 16, NCH = DP / 8, RB = DP * 2, SWM = k_swm<DP>(), KS = DP / 32;
   EVT_LDS char* Ks = (EVT_LDS char*)smem;
   EVT_LDS char* Vs = Ks + NP * RB;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -439,8 +423,8 @@ __global__ __launch_bounds__(256) void attn_gen_bf16_kernel(AttnParams p) {
     const int row = i / NCH, ch = i - row * NCH;
     const bf16* rp = qkv + (int64_t)min(row, p.N - 1) * p.ldq;
     const int so = row * RB + ((ch ^ (row & SWM)) << 4);
-    *(EVT_LDS u32x4*)(Ks + so) = gen_chunk(rp + (p.H + h) * hd, ch * 8, hd);
-    *(EVT_LDS u32x4*)(Vs + so) = gen_chunk(rp + (2 * p.H + h) * hd, ch * 8, hd);
+    *(EVT_LDS u32x4*)(Ks + so) = chunk8(rp + (p.H + h) * hd, ch * 8, hd);
+    *(EVT_LDS u32x4*)(Vs + so) = chunk8(rp + (2 * p.H + h) * hd, ch * 8, hd);
   }
   __syncthreads();
   const int g = lane >> 4, c16 = lane & 15;
@@ -450,7 +434,7 @@ __global__ __launch_bounds__(256) void attn_gen_bf16_kernel(AttnParams p) {
     const bf16* qrow = qkv + (int64_t)min(qt * 16 + c16, p.N - 1) * p.ldq + h * hd;
     u32x4 qf[KS];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = gen_chunk(qrow, 32 * ks + 8 * g, hd);
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = chunk8(qrow, 32 * ks + 8 * g, hd);
     f32x4 s[NKT];
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
@@ -537,14 +521,6 @@ __global__ __launch_bounds__(256) void attn_gen_bf16_kernel(AttnParams p) {
 // straight from the qkv rows (L2-resident per head): S^T = K Q^T on v_mfma_f32_16x16x4_f32 over
 // 16-feature chunks, O^T = V^T P^T with MFMA row m of output tile (grp, dt) = head feature
 // 64 grp + 4 m + dt; NG = ceil(h_k / 64) feature groups.
-__device__ __forceinline__ f32x4 gen_load4(const float* row, int d0, int hd) {
-  if ((hd & 3) == 0) return d0 < hd ? *(const f32x4*)(row + d0) : f32x4{0.f, 0.f, 0.f, 0.f};
-  f32x4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = d0 + e < hd ? row[d0 + e] : 0.f;
-  return v;
-}
-
 template <int NKT, int NG>
 __global__ __launch_bounds__(256) void attn_gen_f32_kernel(AttnParams p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -559,11 +535,11 @@ __global__ __launch_bounds__(256) void attn_gen_f32_kernel(AttnParams p) {
     for (int kt = 0; kt < NKT; ++kt) s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int kk = 0; kk < 4 * NG; ++kk) {
       const int d0 = 16 * kk + 4 * g;
-      const f32x4 qf = gen_load4(qrow, d0, hd);
+      const f32x4 qf = chunk4(qrow, d0, hd);
 #pragma unroll
       for (int kt = 0; kt < NKT; ++kt) {
         const float* krow = qkv + (int64_t)min(kt * 16 + c16, p.N - 1) * p.ldq + (p.H + h) * hd;
-        const f32x4 kf = gen_load4(krow, d0, hd);
+        const f32x4 kf = chunk4(krow, d0, hd);
 #pragma unroll
         for (int e = 0; e < 4; ++e) s[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[e], qf[e], s[kt], 0, 0, 0);
       }
@@ -604,7 +580,7 @@ __global__ __launch_bounds__(256) void attn_gen_f32_kernel(AttnParams p) {
         const float* vrow = qkv + (int64_t)key * p.ldq + (2 * p.H + h) * hd;
 #pragma unroll
         for (int gr = 0; gr < NG; ++gr) {
-          const f32x4 v = gen_load4(vrow, 64 * gr + 4 * c16, hd);
+          const f32x4 v = chunk4(vrow, 64 * gr + 4 * c16, hd);
 #pragma unroll
           for (int dt = 0; dt < 4; ++dt)
             o[gr][dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[dt], s[kt][e], o[gr][dt], 0, 0, 0);
@@ -912,7 +888,7 @@ __global__ __launch_bounds__(256, 2) void attn_long_bf16_kernel(AttnParams p, in
 template <int DP>
 __global__ __launch_bounds__(256) void attn_long_gen_bf16_kernel(AttnParams p, int nqb) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int NCH = DP / 8, RB = DP * 2, SWM = gen_swm<DP>(), KS = DP / 32;
+  constexpr int NCH = DP / 8, RB = DP * 2, SWM = k_swm<DP>(), KS = DP / 32;
   EVT_LDS char* Ks = (EVT_LDS char*)smem;
   EVT_LDS char* Vs = Ks + LONG_KB * RB;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -927,7 +903,7 @@ __global__ __launch_bounds__(256) void attn_long_gen_bf16_kernel(AttnParams p, i
   const bf16* qrow = qkv + (int64_t)min(qt * 16 + c16, p.N - 1) * p.ldq + h * hd;
   u32x4 qf[KS];
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) qf[ks] = gen_chunk(qrow, 32 * ks + 8 * g, hd);
+  for (int ks = 0; ks < KS; ++ks) qf[ks] = chunk8(qrow, 32 * ks + 8 * g, hd);
   f32x4 o[DP / 16];
 #pragma unroll
   for (int dt = 0; dt < DP / 16; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -938,8 +914,8 @@ __global__ __launch_bounds__(256) void attn_long_gen_bf16_kernel(AttnParams p, i
       const int row = i / NCH, ch = i - row * NCH;
       const bf16* rp = qkv + (int64_t)min(kb * LONG_KB + row, p.N - 1) * p.ldq;
       const int so = row * RB + ((ch ^ (row & SWM)) << 4);
-      *(EVT_LDS u32x4*)(Ks + so) = gen_chunk(rp + (p.H + h) * hd, ch * 8, hd);
-      *(EVT_LDS u32x4*)(Vs + so) = gen_chunk(rp + (2 * p.H + h) * hd, ch * 8, hd);
+      *(EVT_LDS u32x4*)(Ks + so) = chunk8(rp + (p.H + h) * hd, ch * 8, hd);
+      *(EVT_LDS u32x4*)(Vs + so) = chunk8(rp + (2 * p.H + h) * hd, ch * 8, hd);
     }
     __syncthreads();
     if (!active) continue;
@@ -1029,11 +1005,11 @@ __global__ __launch_bounds__(256) void attn_long_f32_kernel(AttnParams p, int nq
     for (int kt = 0; kt < LONG_NKT; ++kt) s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int kk = 0; kk < 4 * NG; ++kk) {
       const int d0 = 16 * kk + 4 * g;
-      const f32x4 qf = gen_load4(qrow, d0, hd);
+      const f32x4 qf = chunk4(qrow, d0, hd);
 #pragma unroll
       for (int kt = 0; kt < LONG_NKT; ++kt) {
         const float* krow = qkv + (int64_t)min(key0 + kt * 16 + c16, p.N - 1) * p.ldq + (p.H + h) * hd;
-        const f32x4 kf = gen_load4(krow, d0, hd);
+        const f32x4 kf = chunk4(krow, d0, hd);
 #pragma unroll
         for (int e = 0; e < 4; ++e) s[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[e], qf[e], s[kt], 0, 0, 0);
       }
@@ -1054,7 +1030,7 @@ __global__ __launch_bounds__(256) void attn_long_f32_kernel(AttnParams p, int nq
         const float* vrow = qkv + (int64_t)key * p.ldq + (2 * p.H + h) * hd;
 #pragma unroll
         for (int gr = 0; gr < NG; ++gr) {
-          const f32x4 v = gen_load4(vrow, 64 * gr + 4 * c16, hd);
+          const f32x4 v = chunk4(vrow, 64 * gr + 4 * c16, hd);
 #pragma unroll
           for (int dt = 0; dt < 4; ++dt)
             o[gr][dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[dt], s[kt][e], o[gr][dt], 0, 0, 0);

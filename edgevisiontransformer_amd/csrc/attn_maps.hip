@@ -17,6 +17,10 @@
 //           attn_long_*_kernel without the O accumulators)
 //   pass 2  the scores again, p = 2^((s - m) c) / l, stored
 //
+// The scores and pass 1 are AttnScores (attn_scores.h), the one definition this kernel shares
+// with the head statistics and the head mean below: what those two call "the export's" m, l and
+// scores is the same code. Each kernel here holds only its own pass 2.
+//
 // Recomputing costs twice the MFMA work and no trip of fp32 scores through memory; ALL mode is
 // bound by its B H N^2 4 bytes of stores, CLS mode by the read of K. MFMA columns are independent
 // and the CLS row is column 0 of tile 0 of the same kernel, so out_cls == out_all[:, :, 0] bitwise
@@ -36,6 +40,7 @@
 // them). A row of N floats starts 16-byte aligned only when its element offset is a multiple of
 // 4 (N = 197, 257, 577: one row in four), so two forms exist:
 //   dword  a lane per key, 64 consecutive floats (256 B) of one row per instruction
+//          (store_tile_rows, attn_scores.h)
 //   wide   a lane per aligned group of 4 keys, four rows per instruction: 16-B stores
 //          (store4_nt) for the aligned body of the row's segment, 4-B stores for the at most 3
 //          floats before it and after it
@@ -49,6 +54,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "attn_scores.h"
 #include "common.h"
 #include "evt_internal.h"
 
@@ -56,176 +62,56 @@ namespace evt {
 
 namespace {
 
-constexpr int KB = 64;         // keys per block
-constexpr int NKT = KB / 16;   // 16-key MFMA tiles per block
-constexpr int PROW = KB + 4;   // floats per row of a wave's P tile (rows 4 banks apart)
-constexpr int PTILE = 16 * PROW;
+using namespace scores;  // attn_scores.h
 
-// swizzle mask of the staged K rows (DP * 2 bytes each), as attention.hip gen_swm
-template <int DP>
-constexpr int k_swm() {
-  constexpr int nch = DP / 8;
-  return nch == 4 ? 3 : ((nch >= 8 && (nch & (nch - 1)) == 0) ? 7 : 0);
+// A wave's P tile (and head_mean_kernel's (m, 1 / l) table) is its own: LDS operations of a wave
+// complete in order, so a wave-level fence orders the writes before the reads (wave_lds_written)
+// and the reads before the next block's writes (wave_lds_read).
+__device__ __forceinline__ void wave_lds_written() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-
-// 8 consecutive head features [d0, d0 + 8) of a bf16 row, zero past h_k
-__device__ __forceinline__ u32x4 chunk8(const bf16* row, int d0, int hd) {
-  if ((hd & 7) == 0) {
-    if (d0 < hd) return *(const u32x4*)(row + d0);
-    return u32x4{0u, 0u, 0u, 0u};
-  }
-  bf16x8 v;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) v[e] = d0 + e < hd ? row[d0 + e] : (bf16)0.f;
-  return __builtin_bit_cast(u32x4, v);
-}
-
-// 4 consecutive head features of an fp32 row, zero past h_k
-__device__ __forceinline__ f32x4 chunk4(const float* row, int d0, int hd) {
-  if ((hd & 3) == 0) return d0 < hd ? *(const f32x4*)(row + d0) : f32x4{0.f, 0.f, 0.f, 0.f};
-  f32x4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = d0 + e < hd ? row[d0 + e] : 0.f;
-  return v;
-}
-
-template <bool FAST>
-__device__ __forceinline__ float ex2(float x) {
-  return FAST ? __builtin_amdgcn_exp2f(x) : exp2f(x);
+__device__ __forceinline__ void wave_lds_read() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
 }
 
 // T: bf16 (DP = h_k padded to 32 / 64 / 96 / 128) or float (DP = 64 / 128: feature groups of 64).
-// nqb: 64-query groups per (image, head). Workgroups of one (image, head) read the same K: the
-// block index is unswizzled as in attn_long_bf16_kernel so that they run on one XCD (speed only).
+// nqb: 64-query groups per (image, head).
 template <typename T, int DP, bool WIDE>
 __global__ __launch_bounds__(256) void attn_probs_kernel(AttnParams p, int nq, int nqb,
                                                          float* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool BF = sizeof(T) == 2;
-  constexpr int RB = DP * 2, NCH = DP / 8, SWM = k_swm<DP>(), KS = DP / 32, NG = DP / 64;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int g = lane >> 4, c16 = lane & 15;
+  AttnScores<T, DP> sc(p, (EVT_LDS char*)smem + 4 * PTILE * 4);  // bf16: one K block, [64][DP]
+  const int lane = sc.lane, wave = sc.tid >> 6, g = sc.g, c16 = sc.c16, N = sc.N, nkb = sc.nkb;
   EVT_LDS float* Ps = (EVT_LDS float*)smem + wave * PTILE;  // this wave's [16 queries][64 keys]
-  EVT_LDS char* Ks = (EVT_LDS char*)smem + 4 * PTILE * 4;   // bf16: one K block, [64][DP]
   int bh, qb;
-  {
-    const int BH = p.B * p.H, full = (BH >> 3) * 8 * nqb, L = blockIdx.x;
-    if (L < full) {
-      bh = (L & 7) + 8 * (L / (8 * nqb));
-      qb = (L >> 3) % nqb;
-    } else {
-      bh = (BH & ~7) + (L - full) / nqb;
-      qb = (L - full) % nqb;
-    }
-  }
-  const int b = bh / p.H, h = bh - b * p.H, hd = p.hd, N = p.N;
-  const T* slice = (const T*)p.qkv + b * p.sb + h * p.sh;  // q of the (image, head); k at + ko
-  const int nqt = (nq + 15) >> 4, nkb = (N + KB - 1) / KB;
+  unswizzle_block(blockIdx.x, p.B * p.H, nqb, bh, qb);
+  const int b = bh / p.H, h = bh - b * p.H;
+  const int nqt = (nq + 15) >> 4;
   const int qt = qb * 4 + wave;
   const bool active = qt < nqt;  // wave-uniform
   if constexpr (!BF) {
     if (!active) return;  // no barrier in the fp32 kernel
   }
-  const T* qrow = slice + (int64_t)min(qt * 16 + c16, N - 1) * p.ldq;
+  sc.set_image(b);
+  sc.set_tile(qt);
+  sc.head(h);
   const float c = p.scale_log2;
 
-  u32x4 qf[BF ? KS : 1];
-  if constexpr (BF) {
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = chunk8((const bf16*)qrow, 32 * ks + 8 * g, hd);
-  }
-  // bf16: key block kb of K into LDS, 16-B chunk ch of row r at chunk ch ^ (r & SWM)
-  auto stage = [&](int kb) {
-    for (int i = tid; i < KB * NCH; i += 256) {
-      const int row = i / NCH, ch = i - row * NCH;
-      const bf16* rp = (const bf16*)slice + (int64_t)min(kb * KB + row, N - 1) * p.ldq + p.ko;
-      *(EVT_LDS u32x4*)(Ks + row * RB + ((ch ^ (row & SWM)) << 4)) = chunk8(rp, ch * 8, hd);
-    }
-  };
-  // s[kt][j] = S^T[key = kb*64 + kt*16 + 4g + j][query = qt*16 + c16], -inf for keys past N
-  auto scores = [&](int kb, f32x4(&s)[NKT]) {
-    if constexpr (BF) {
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt) {
-        const int row = kt * 16 + c16;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          const u32x4 kf = *(const EVT_LDS u32x4*)(Ks + row * RB + (((4 * ks + g) ^ (row & SWM)) << 4));
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf),
-                                                        __builtin_bit_cast(bf16x8, qf[ks]), acc, 0, 0, 0);
-        }
-        s[kt] = acc;
-      }
-    } else {
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt) s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      for (int kk = 0; kk < 4 * NG; ++kk) {
-        const int d0 = 16 * kk + 4 * g;
-        const f32x4 qv = chunk4((const float*)qrow, d0, hd);
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt) {
-          const float* krow =
-              (const float*)slice + (int64_t)min(kb * KB + kt * 16 + c16, N - 1) * p.ldq + p.ko;
-          const f32x4 kv = chunk4(krow, d0, hd);
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            s[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kv[e], qv[e], s[kt], 0, 0, 0);
-        }
-      }
-    }
-    if ((kb + 1) * KB > N) {  // wave-uniform: only the last block holds keys past N
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (kb * KB + kt * 16 + 4 * g + j >= N) s[kt][j] = -INFINITY;
-    }
-  };
-
-  // ---- pass 1: m = max_j s, l = sum_j 2^((s - m) c). Every block holds a valid key, so its
-  // maximum is finite; on the first block m = -inf and 2^(-inf) = 0 drops the empty sum.
-  float m = -INFINITY, l = 0.f;
-  for (int kb = 0; kb < nkb; ++kb) {
-    if constexpr (BF) {
-      if (kb) __syncthreads();  // every wave is done with the previous block
-      stage(kb);
-      __syncthreads();
-      if (!active) continue;
-    }
-    f32x4 s[NKT];
-    scores(kb, s);
-    float bm = s[0][0];
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bm = fmaxf(bm, s[kt][j]);
-    bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
-    bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-    const float mn = fmaxf(m, bm);
-    float sum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) sum += ex2<BF>((s[kt][j] - mn) * c);
-    l = l * ex2<BF>((m - mn) * c) + sum;  // the lane's partial sum; the four lanes of a query
-    m = mn;                               // hold the same m
-  }
-  l += __shfl_xor(l, 16, 64);
-  l += __shfl_xor(l, 32, 64);
+  // ---- pass 1; nothing is staged yet, so no barrier ahead of its first block
+  float m, l;
+  sc.template pass1<false>(active, m, l);
   const float inv = 1.0f / l;
 
   // ---- pass 2: p = 2^((s - m) c) / l, through the wave's LDS tile, stored by rows
   const int64_t row0 = ((int64_t)bh * nq + (int64_t)qt * 16) * N;  // element offset of the tile's row 0
   for (int kb = 0; kb < nkb; ++kb) {
-    if constexpr (BF) {
-      __syncthreads();
-      stage(kb);
-      __syncthreads();
-      if (!active) continue;
-    }
+    if (!sc.template stage_block<true>(kb, active)) continue;
     f32x4 s[NKT];
-    scores(kb, s);
+    sc.scores(kb, s);
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
       f32x4 pv;
@@ -233,16 +119,10 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(AttnParams p, int nq, i
       for (int j = 0; j < 4; ++j) pv[j] = ex2<BF>((s[kt][j] - m) * c) * inv;
       *(EVT_LDS f32x4*)(Ps + c16 * PROW + kt * 16 + 4 * g) = pv;
     }
-    // the tile is this wave's alone: LDS operations of a wave complete in order
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_written();
     const int nk = min(KB, N - kb * KB);  // keys of this block
     if constexpr (!WIDE) {
-      for (int r = 0; r < 16 && qt * 16 + r < nq; ++r) {
-        const float v = Ps[r * PROW + lane];
-        if (lane < nk) store1_nt(out + row0 + (int64_t)r * N + kb * KB + lane, v);
-      }
+      store_tile_rows<true>(Ps, out + row0, qt * 16, nq, kb * KB, nk, N, lane);
     } else {
       const int rr = lane >> 4, ql = lane & 15;
 #pragma unroll
@@ -268,20 +148,53 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(AttnParams p, int nq, i
         }
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_read();
   }
 }
 
-template <typename T, int DP>
-hipError_t launch_probs(const AttnParams& p, int nq, int nqb, bool wide, float* out, hipStream_t s) {
-  const size_t lds = 4 * PTILE * 4 + (sizeof(T) == 2 ? (size_t)KB * DP * 2 : 0);
-  const dim3 grid(p.B * p.H * nqb), block(256);
-  if (wide)
-    hipLaunchKernelGGL((attn_probs_kernel<T, DP, true>), grid, block, lds, s, p, nq, nqb, out);
-  else
-    hipLaunchKernelGGL((attn_probs_kernel<T, DP, false>), grid, block, lds, s, p, nq, nqb, out);
-  return hipGetLastError();
+// What the three launchers below ask of their parameters alike; fills the default slice layout.
+// c > 0: (s - m) c <= 0 and the -inf masks need it.
+bool prepare(int dtype, const AttnParams& p_in, const float* out, AttnParams& p) {
+  if (!p_in.qkv || !out || p_in.N <= 0 || p_in.N > EVT_ATTN_MAX_TOKENS || p_in.H <= 0 ||
+      p_in.hd <= 0 || p_in.hd > 128 || ((uintptr_t)out & 15) ||
+      (dtype != DT_BF16 && dtype != DT_F32))
+    return false;
+  if (!(p_in.scale_log2 > 0.f && p_in.scale_log2 < INFINITY)) return false;
+  p = p_in;
+  if (p.sb || p.sh || p.ko) {  // an explicit slice layout: bf16, h_k = 64, 16-B aligned pieces
+    if (dtype != DT_BF16 || p.hd != 64 || p.sb % 8 || p.sh % 8 || p.ldq % 8 || p.ko % 8 ||
+        p.ldq < 64 || p.ko < 0 || p.sb < 0 || p.sh < 0)
+      return false;
+  } else {
+    p.sb = (int64_t)p.N * p.ldq;
+    p.sh = p.hd;
+    p.ko = p.H * p.hd;
+  }
+  return true;
+}
+
+template <typename T, int DP_>
+struct Variant {
+  using type = T;
+  static constexpr int DP = DP_;
+};
+
+// f(Variant<T, DP>) of the instantiation for a (prepared) dtype and head size
+template <typename F>
+hipError_t dispatch(int dtype, int hd, F&& f) {
+  if (dtype == DT_BF16) {
+    if (hd <= 32) return f(Variant<bf16, 32>{});
+    if (hd <= 64) return f(Variant<bf16, 64>{});
+    if (hd <= 96) return f(Variant<bf16, 96>{});
+    return f(Variant<bf16, 128>{});
+  }
+  if (hd <= 64) return f(Variant<float, 64>{});
+  return f(Variant<float, 128>{});
+}
+
+// LDS bytes of the waves' four P tiles (a kernel that stores rows) and, for bf16, one K block
+constexpr size_t score_lds(size_t elem, int DP, bool tiles) {
+  return (tiles ? 4 * PTILE * 4 : 0) + (elem == 2 ? (size_t)KB * DP * 2 : 0);
 }
 
 // the store form (file header): dword unless EVT_ATTN_MAPS_STORE=wide asks for the other one
@@ -294,33 +207,22 @@ bool wide_stores() {
 
 hipError_t attn_probs_launch(int dtype, const AttnParams& p_in, int nq, float* out, hipStream_t s) {
   if (p_in.B <= 0) return hipSuccess;
-  if (!p_in.qkv || !out || p_in.N <= 0 || p_in.N > EVT_ATTN_MAX_TOKENS || p_in.H <= 0 ||
-      p_in.hd <= 0 || p_in.hd > 128 || (nq != 1 && nq != p_in.N) || ((uintptr_t)out & 15))
-    return hipErrorInvalidValue;
-  // (s - m) c <= 0 and the -inf masks need c > 0
-  if (!(p_in.scale_log2 > 0.f && p_in.scale_log2 < INFINITY)) return hipErrorInvalidValue;
-  AttnParams p = p_in;
-  if (p.sb || p.sh || p.ko) {  // an explicit slice layout: bf16, h_k = 64, 16-B aligned pieces
-    if (dtype != DT_BF16 || p.hd != 64 || p.sb % 8 || p.sh % 8 || p.ldq % 8 || p.ko % 8 ||
-        p.ldq < 64 || p.ko < 0 || p.sb < 0 || p.sh < 0)
-      return hipErrorInvalidValue;
-  } else {
-    p.sb = (int64_t)p.N * p.ldq;
-    p.sh = p.hd;
-    p.ko = p.H * p.hd;
-  }
+  AttnParams p;
+  if (!prepare(dtype, p_in, out, p) || (nq != 1 && nq != p.N)) return hipErrorInvalidValue;
   const int nqb = ((nq + 15) / 16 + 3) / 4;
   if ((int64_t)p.B * p.H * nqb > INT32_MAX) return hipErrorInvalidValue;
   const bool wide = wide_stores();
-  if (dtype == DT_BF16) {
-    if (p.hd <= 32) return launch_probs<bf16, 32>(p, nq, nqb, wide, out, s);
-    if (p.hd <= 64) return launch_probs<bf16, 64>(p, nq, nqb, wide, out, s);
-    if (p.hd <= 96) return launch_probs<bf16, 96>(p, nq, nqb, wide, out, s);
-    return launch_probs<bf16, 128>(p, nq, nqb, wide, out, s);
-  }
-  if (dtype != DT_F32) return hipErrorInvalidValue;
-  if (p.hd <= 64) return launch_probs<float, 64>(p, nq, nqb, wide, out, s);
-  return launch_probs<float, 128>(p, nq, nqb, wide, out, s);
+  return dispatch(dtype, p.hd, [&](auto v) {
+    using V = decltype(v);
+    using T = typename V::type;
+    const dim3 grid(p.B * p.H * nqb), block(256);
+    const size_t lds = score_lds(sizeof(T), V::DP, true);
+    if (wide)
+      hipLaunchKernelGGL((attn_probs_kernel<T, V::DP, true>), grid, block, lds, s, p, nq, nqb, out);
+    else
+      hipLaunchKernelGGL((attn_probs_kernel<T, V::DP, false>), grid, block, lds, s, p, nq, nqb, out);
+    return hipGetLastError();
+  });
 }
 
 // ---- Head statistics (include/evt_head_stats.h) ------------------------------------------------
@@ -336,12 +238,10 @@ hipError_t attn_probs_launch(int dtype, const AttnParams& p_in, int nq, float* o
 // the patch-grid cells of tokens i and j (token t >= prefix: row (t - prefix) / grid_w, column
 // (t - prefix) % grid_w).
 //
-// TWO PASSES, as attn_probs_kernel: pass 1 is its pass 1 (m, l), pass 2 forms the scores again and
-// accumulates the three sums sum e t, sum_{j >= prefix} e d and sum_{j < prefix} e against the final
-// m, so nothing is rescaled. The score machinery (S^T = K Q^T on the MFMA, 64-key blocks, K staged
-// to LDS for bf16, operands from the rows for fp32, zero-padded head sizes, AttnParams layouts,
-// clamped rows, 64-bit offsets) is attn_probs_kernel's, restated here so that kernel's code and
-// bits stay what they are.
+// TWO PASSES, as attn_probs_kernel: pass 1 is AttnScores::pass1 (m, l), the code the export runs;
+// pass 2 forms the scores again, through the same AttnScores::scores, and accumulates the three
+// sums sum e t, sum_{j >= prefix} e d and sum_{j < prefix} e against the final m, so nothing is
+// rescaled. This kernel's own: the cell geometry, those sums and the fp64 reduction.
 //
 // Keys past N carry -inf scores: t = -inf, e = 0. They are selected out of the e t sum by index (a
 // product would be 0 * -inf = NaN; this file is compiled honouring NaN and inf); in the other two
@@ -363,66 +263,15 @@ __global__ __launch_bounds__(256) void head_stats_kernel(AttnParams p, int prefi
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ double red[4][4];
   constexpr bool BF = sizeof(T) == 2;
-  constexpr int RB = DP * 2, NCH = DP / 8, SWM = k_swm<DP>(), KS = DP / 32, NG = DP / 64;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int g = lane >> 4, c16 = lane & 15;
-  EVT_LDS char* Ks = (EVT_LDS char*)smem;  // bf16: one K block, [64][DP]
+  AttnScores<T, DP> sc(p, (EVT_LDS char*)smem);  // bf16: one K block, [64][DP]
+  const int tid = sc.tid, lane = sc.lane, wave = tid >> 6, g = sc.g, c16 = sc.c16;
+  const int N = sc.N, nkb = sc.nkb;
   const int bh = blockIdx.x;
-  const int b = bh / p.H, h = bh - b * p.H, hd = p.hd, N = p.N;
-  const T* slice = (const T*)p.qkv + b * p.sb + h * p.sh;  // q of the (image, head); k at + ko
-  const int nqt = (N + 15) >> 4, nkb = (N + KB - 1) / KB, nqb = (nqt + 3) >> 2;
+  const int b = bh / p.H, h = bh - b * p.H;
+  sc.set_image(b);
+  const int nqt = (N + 15) >> 4, nqb = (nqt + 3) >> 2;
   const float c = p.scale_log2;
-  const T* qrow = slice;
-  u32x4 qf[BF ? KS : 1];
 
-  // bf16: key block kb of K into LDS, 16-B chunk ch of row r at chunk ch ^ (r & SWM)
-  auto stage = [&](int kb) {
-    for (int i = tid; i < KB * NCH; i += 256) {
-      const int row = i / NCH, ch = i - row * NCH;
-      const bf16* rp = (const bf16*)slice + (int64_t)min(kb * KB + row, N - 1) * p.ldq + p.ko;
-      *(EVT_LDS u32x4*)(Ks + row * RB + ((ch ^ (row & SWM)) << 4)) = chunk8(rp, ch * 8, hd);
-    }
-  };
-  // s[kt][j] = S^T[key = kb*64 + kt*16 + 4g + j][query = qt*16 + c16], -inf for keys past N
-  auto scores = [&](int kb, f32x4(&s)[NKT]) {
-    if constexpr (BF) {
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt) {
-        const int row = kt * 16 + c16;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          const u32x4 kf = *(const EVT_LDS u32x4*)(Ks + row * RB + (((4 * ks + g) ^ (row & SWM)) << 4));
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf),
-                                                        __builtin_bit_cast(bf16x8, qf[ks]), acc, 0, 0, 0);
-        }
-        s[kt] = acc;
-      }
-    } else {
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt) s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      for (int kk = 0; kk < 4 * NG; ++kk) {
-        const int d0 = 16 * kk + 4 * g;
-        const f32x4 qv = chunk4((const float*)qrow, d0, hd);
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt) {
-          const float* krow =
-              (const float*)slice + (int64_t)min(kb * KB + kt * 16 + c16, N - 1) * p.ldq + p.ko;
-          const f32x4 kv = chunk4(krow, d0, hd);
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            s[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kv[e], qv[e], s[kt], 0, 0, 0);
-        }
-      }
-    }
-    if ((kb + 1) * KB > N) {  // wave-uniform: only the last block holds keys past N
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (kb * KB + kt * 16 + 4 * g + j >= N) s[kt][j] = -INFINITY;
-    }
-  };
   // grid cell (row, column) of patch r = token - prefix, as floats (a query below prefix or past N
   // gets a finite cell nobody reads)
   auto cell = [&](int r, float& y, float& x) {
@@ -438,54 +287,20 @@ __global__ __launch_bounds__(256) void head_stats_kernel(AttnParams p, int prefi
     if constexpr (!BF) {
       if (!active) continue;  // no barrier in the fp32 loops
     }
-    qrow = slice + (int64_t)min(qi, N - 1) * p.ldq;
-    if constexpr (BF) {
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) qf[ks] = chunk8((const bf16*)qrow, 32 * ks + 8 * g, hd);
-    }
-    // ---- pass 1: m = max_j s, l = sum_j 2^((s - m) c) (attn_probs_kernel's pass 1)
-    float m = -INFINITY, l = 0.f;
-    for (int kb = 0; kb < nkb; ++kb) {
-      if constexpr (BF) {
-        __syncthreads();  // every wave is done with the block staged before
-        stage(kb);
-        __syncthreads();
-        if (!active) continue;
-      }
-      f32x4 s[NKT];
-      scores(kb, s);
-      float bm = s[0][0];
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bm = fmaxf(bm, s[kt][j]);
-      bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
-      bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-      const float mn = fmaxf(m, bm);
-      float sum = 0.f;
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) sum += ex2<BF>((s[kt][j] - mn) * c);
-      l = l * ex2<BF>((m - mn) * c) + sum;
-      m = mn;
-    }
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
+    sc.set_tile(qt);
+    sc.head(h);
+    // ---- pass 1; an earlier query group has staged a block before, so a barrier ahead of each
+    float m, l;
+    sc.template pass1<true>(active, m, l);
 
     // ---- pass 2: sum_j e t, sum_{j >= prefix} e d, sum_{j < prefix} e with e = 2^t, t = (s - m) c
     float qy, qx;
     cell(qi - prefix, qy, qx);
     float et = 0.f, ed = 0.f, ec = 0.f;
     for (int kb = 0; kb < nkb; ++kb) {
-      if constexpr (BF) {
-        __syncthreads();
-        stage(kb);
-        __syncthreads();
-        if (!active) continue;
-      }
+      if (!sc.template stage_block<true>(kb, active)) continue;
       f32x4 s[NKT];
-      scores(kb, s);
+      sc.scores(kb, s);
 #pragma unroll
       for (int kt = 0; kt < NKT; ++kt) {
         const int k0 = kb * KB + kt * 16 + 4 * g;  // this lane's four consecutive keys
@@ -552,45 +367,24 @@ __global__ __launch_bounds__(256) void head_stats_kernel(AttnParams p, int prefi
   }
 }
 
-template <typename T, int DP>
-hipError_t launch_head_stats(const AttnParams& p, int prefix, int gw, float* out, hipStream_t s) {
-  const size_t lds = sizeof(T) == 2 ? (size_t)KB * DP * 2 : 0;
-  hipLaunchKernelGGL((head_stats_kernel<T, DP>), dim3(p.B * p.H), dim3(256), lds, s, p, prefix, gw,
-                     1.0f / (float)gw, out);
-  return hipGetLastError();
-}
-
 }  // namespace
 
 hipError_t head_stats_launch(int dtype, const AttnParams& p_in, int prefix, int grid_w, float* out,
                              hipStream_t s) {
   if (p_in.B <= 0) return hipSuccess;
-  if (!p_in.qkv || !out || p_in.N <= 0 || p_in.N > EVT_ATTN_MAX_TOKENS || p_in.H <= 0 ||
-      p_in.hd <= 0 || p_in.hd > 128 || ((uintptr_t)out & 15) || prefix < 0 || prefix >= p_in.N ||
-      grid_w < 1 || (p_in.N - prefix) % grid_w)
+  AttnParams p;
+  if (!prepare(dtype, p_in, out, p) || prefix < 0 || prefix >= p.N || grid_w < 1 ||
+      (p.N - prefix) % grid_w)
     return hipErrorInvalidValue;
-  // (s - m) c <= 0 and the -inf masks need c > 0
-  if (!(p_in.scale_log2 > 0.f && p_in.scale_log2 < INFINITY)) return hipErrorInvalidValue;
-  AttnParams p = p_in;
-  if (p.sb || p.sh || p.ko) {  // an explicit slice layout: bf16, h_k = 64, 16-B aligned pieces
-    if (dtype != DT_BF16 || p.hd != 64 || p.sb % 8 || p.sh % 8 || p.ldq % 8 || p.ko % 8 ||
-        p.ldq < 64 || p.ko < 0 || p.sb < 0 || p.sh < 0)
-      return hipErrorInvalidValue;
-  } else {
-    p.sb = (int64_t)p.N * p.ldq;
-    p.sh = p.hd;
-    p.ko = p.H * p.hd;
-  }
   if ((int64_t)p.B * p.H > INT32_MAX) return hipErrorInvalidValue;
-  if (dtype == DT_BF16) {
-    if (p.hd <= 32) return launch_head_stats<bf16, 32>(p, prefix, grid_w, out, s);
-    if (p.hd <= 64) return launch_head_stats<bf16, 64>(p, prefix, grid_w, out, s);
-    if (p.hd <= 96) return launch_head_stats<bf16, 96>(p, prefix, grid_w, out, s);
-    return launch_head_stats<bf16, 128>(p, prefix, grid_w, out, s);
-  }
-  if (dtype != DT_F32) return hipErrorInvalidValue;
-  if (p.hd <= 64) return launch_head_stats<float, 64>(p, prefix, grid_w, out, s);
-  return launch_head_stats<float, 128>(p, prefix, grid_w, out, s);
+  return dispatch(dtype, p.hd, [&](auto v) {
+    using V = decltype(v);
+    using T = typename V::type;
+    hipLaunchKernelGGL((head_stats_kernel<T, V::DP>), dim3(p.B * p.H), dim3(256),
+                       score_lds(sizeof(T), V::DP, false), s, p, prefix, grid_w,
+                       1.0f / (float)grid_w, out);
+    return hipGetLastError();
+  });
 }
 
 // ---- Head mean (include/evt_rollout.h) ---------------------------------------------------------
@@ -601,25 +395,25 @@ hipError_t head_stats_launch(int dtype, const AttnParams& p_in, int prefix, int 
 // per-head map stored: the A operand of an attention-rollout step (rollout.hip). A workgroup (4
 // waves) takes (image, 64 queries), a wave one 16-query tile, and loops over the heads inside:
 //
-//   pass 1  for every head: the running max m and sum l over the 64-key blocks (attn_probs_kernel's
-//           pass 1); m and 1 / l of the wave's 16 queries go to a per-wave LDS table [H][16][2]
-//   pass 2  for every key block: for h = 0 .. H - 1 in that order the scores again,
-//           p = 2^((s - m_h) c) / l_h (the same expression, so the same bits, as the export) added
-//           to an fp32 accumulator that starts at 0; then one product with fl(1 / H), the block
-//           through the wave's LDS tile and out by row segments
+//   pass 1  for every head: AttnScores::pass1, the export's (m, l) from the export's code; m and
+//           1 / l of the wave's 16 queries go to a per-wave LDS table [H][16][2]
+//   pass 2  for every key block: for h = 0 .. H - 1 in that order the scores again
+//           (AttnScores::scores), p = 2^((s - m_h) c) / l_h (the export's expression on the
+//           export's m, l and s, so the same bits) added to an fp32 accumulator that starts at 0;
+//           then one product with fl(1 / H), the block through the wave's LDS tile and out by row
+//           segments
 //
 // A [16 x N] accumulator per wave does not fit anywhere for N up to 4096, hence the key block as
 // the outer loop of pass 2 and the table; bf16 stages the same number of K blocks (H nkb per pass)
 // as a loop with the head outside would, and reloads the q fragments per (block, head) from L2.
-// The score machinery is attn_probs_kernel's, restated (that kernel's code and bits stay what they
-// are). The head sum has one order, nothing is atomic, nothing depends on the batch position, and
+// This kernel's own: the table, the head loop inside each key block and the fl(1 / H) product.
+// The head sum has one order, nothing is atomic, nothing depends on the batch position, and
 // both qkv layouts stage the same values: results are bitwise reproducible and layout independent.
 // Every p is in [0, 1], so the sum is in [0, H] and the mean in [0, 1] up to one rounding; keys
 // past N get -inf scores, contribute 2^-inf = 0 and are not stored.
 //
-// Stores: the dword row-segment form that won for the export (a lane per float, 256 contiguous
-// bytes per wave instruction), plain rather than non-temporal: the rollout step reads the buffer
-// next. Every row and output offset is 64-bit.
+// Stores: the dword row-segment form that won for the export (store_tile_rows), plain rather than
+// non-temporal: the rollout step reads the buffer next. Every row and output offset is 64-bit.
 namespace {
 
 template <typename T, int DP>
@@ -627,133 +421,32 @@ __global__ __launch_bounds__(256) void head_mean_kernel(AttnParams p, int nqb, f
                                                         float* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool BF = sizeof(T) == 2;
-  constexpr int RB = DP * 2, NCH = DP / 8, SWM = k_swm<DP>(), KS = DP / 32, NG = DP / 64;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int g = lane >> 4, c16 = lane & 15;
-  const int H = p.H, hd = p.hd, N = p.N;
+  AttnScores<T, DP> sc(p, (EVT_LDS char*)smem + 4 * PTILE * 4);  // bf16: one K block, [64][DP]
+  const int lane = sc.lane, wave = sc.tid >> 6, g = sc.g, c16 = sc.c16;
+  const int H = p.H, N = sc.N, nkb = sc.nkb;
   EVT_LDS float* Ps = (EVT_LDS float*)smem + wave * PTILE;  // this wave's [16 queries][64 keys]
-  EVT_LDS char* Ks = (EVT_LDS char*)smem + 4 * PTILE * 4;   // bf16: one K block, [64][DP]
   // this wave's (m, 1 / l) of head h, query c16 at [(h * 16 + c16) * 2]
   EVT_LDS float* St = (EVT_LDS float*)(smem + 4 * PTILE * 4 + (BF ? KB * DP * 2 : 0)) + wave * 32 * H;
-  int b, qb;  // workgroups of one image read the same K: on one XCD (speed only), as attn_probs_kernel
-  {
-    const int full = (p.B >> 3) * 8 * nqb, L = blockIdx.x;
-    if (L < full) {
-      b = (L & 7) + 8 * (L / (8 * nqb));
-      qb = (L >> 3) % nqb;
-    } else {
-      b = (p.B & ~7) + (L - full) / nqb;
-      qb = (L - full) % nqb;
-    }
-  }
-  const T* image = (const T*)p.qkv + b * p.sb;
-  const T* slice = image;  // q of the (image, head); k at + ko
-  const int nqt = (N + 15) >> 4, nkb = (N + KB - 1) / KB;
+  int b, qb;  // workgroups of one image read the same K
+  unswizzle_block(blockIdx.x, p.B, nqb, b, qb);
+  const int nqt = (N + 15) >> 4;
   const int qt = qb * 4 + wave;
   const bool active = qt < nqt;  // wave-uniform
   if constexpr (!BF) {
     if (!active) return;  // no barrier in the fp32 kernel
   }
-  const int64_t qoff = (int64_t)min(qt * 16 + c16, N - 1) * p.ldq;
-  const T* qrow = slice + qoff;
+  sc.set_image(b);
+  sc.set_tile(qt);
   const float c = p.scale_log2;
-  u32x4 qf[BF ? KS : 1];
 
-  // head h's slice, this lane's q row of it and, for bf16, its q fragments
-  auto head = [&](int h) {
-    slice = image + h * p.sh;
-    qrow = slice + qoff;
-    if constexpr (BF) {
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) qf[ks] = chunk8((const bf16*)qrow, 32 * ks + 8 * g, hd);
-    }
-  };
-  // bf16: key block kb of K into LDS, 16-B chunk ch of row r at chunk ch ^ (r & SWM)
-  auto stage = [&](int kb) {
-    for (int i = tid; i < KB * NCH; i += 256) {
-      const int row = i / NCH, ch = i - row * NCH;
-      const bf16* rp = (const bf16*)slice + (int64_t)min(kb * KB + row, N - 1) * p.ldq + p.ko;
-      *(EVT_LDS u32x4*)(Ks + row * RB + ((ch ^ (row & SWM)) << 4)) = chunk8(rp, ch * 8, hd);
-    }
-  };
-  // s[kt][j] = S^T[key = kb*64 + kt*16 + 4g + j][query = qt*16 + c16], -inf for keys past N
-  auto scores = [&](int kb, f32x4(&s)[NKT]) {
-    if constexpr (BF) {
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt) {
-        const int row = kt * 16 + c16;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          const u32x4 kf = *(const EVT_LDS u32x4*)(Ks + row * RB + (((4 * ks + g) ^ (row & SWM)) << 4));
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf),
-                                                        __builtin_bit_cast(bf16x8, qf[ks]), acc, 0, 0, 0);
-        }
-        s[kt] = acc;
-      }
-    } else {
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt) s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      for (int kk = 0; kk < 4 * NG; ++kk) {
-        const int d0 = 16 * kk + 4 * g;
-        const f32x4 qv = chunk4((const float*)qrow, d0, hd);
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt) {
-          const float* krow =
-              (const float*)slice + (int64_t)min(kb * KB + kt * 16 + c16, N - 1) * p.ldq + p.ko;
-          const f32x4 kv = chunk4(krow, d0, hd);
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            s[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kv[e], qv[e], s[kt], 0, 0, 0);
-        }
-      }
-    }
-    if ((kb + 1) * KB > N) {  // wave-uniform: only the last block holds keys past N
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (kb * KB + kt * 16 + 4 * g + j >= N) s[kt][j] = -INFINITY;
-    }
-  };
-
-  // ---- pass 1, head by head: m = max_j s, l = sum_j 2^((s - m) c) (attn_probs_kernel's pass 1)
+  // ---- pass 1, head by head; the head before has staged a block, so a barrier ahead of each
   for (int h = 0; h < H; ++h) {
-    head(h);
-    float m = -INFINITY, l = 0.f;
-    for (int kb = 0; kb < nkb; ++kb) {
-      if constexpr (BF) {
-        __syncthreads();  // every wave is done with the block staged before
-        stage(kb);
-        __syncthreads();
-        if (!active) continue;
-      }
-      f32x4 s[NKT];
-      scores(kb, s);
-      float bm = s[0][0];
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bm = fmaxf(bm, s[kt][j]);
-      bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
-      bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-      const float mn = fmaxf(m, bm);
-      float sum = 0.f;
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) sum += ex2<BF>((s[kt][j] - mn) * c);
-      l = l * ex2<BF>((m - mn) * c) + sum;
-      m = mn;
-    }
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
+    sc.head(h);
+    float m, l;
+    sc.template pass1<true>(active, m, l);
     if (active && g == 0) *(EVT_LDS f32x2*)(St + (h * 16 + c16) * 2) = f32x2{m, 1.0f / l};
   }
-  // the table is this wave's alone: LDS operations of a wave complete in order
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_written();  // the table is this wave's alone, as its tile
 
   // ---- pass 2, key block by key block: sum_h p in head order, times fl(1 / H), stored by rows
   const int64_t row0 = ((int64_t)b * N + (int64_t)qt * 16) * N;  // element offset of the tile's row 0
@@ -762,15 +455,10 @@ __global__ __launch_bounds__(256) void head_mean_kernel(AttnParams p, int nqb, f
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) acc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int h = 0; h < H; ++h) {
-      head(h);
-      if constexpr (BF) {
-        __syncthreads();
-        stage(kb);
-        __syncthreads();
-        if (!active) continue;
-      }
+      sc.head(h);
+      if (!sc.template stage_block<true>(kb, active)) continue;
       f32x4 s[NKT];
-      scores(kb, s);
+      sc.scores(kb, s);
       const f32x2 ml = *(const EVT_LDS f32x2*)(St + (h * 16 + c16) * 2);
 #pragma unroll
       for (int kt = 0; kt < NKT; ++kt)
@@ -784,67 +472,39 @@ __global__ __launch_bounds__(256) void head_mean_kernel(AttnParams p, int nqb, f
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt)
       *(EVT_LDS f32x4*)(Ps + c16 * PROW + kt * 16 + 4 * g) = acc[kt] * inv_h;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_written();
     const int nk = min(KB, N - kb * KB);  // keys of this block
-    for (int r = 0; r < 16 && qt * 16 + r < N; ++r) {
-      const float v = Ps[r * PROW + lane];
-      if (lane < nk) out[row0 + (int64_t)r * N + kb * KB + lane] = v;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    store_tile_rows<false>(Ps, out + row0, qt * 16, N, kb * KB, nk, N, lane);
+    wave_lds_read();
   }
 }
 
 size_t head_mean_lds(int elem, int DP, int H) {
-  return 4 * PTILE * 4 + (elem == 2 ? (size_t)KB * DP * 2 : 0) + (size_t)4 * 32 * H * sizeof(float);
-}
-
-template <typename T, int DP>
-hipError_t launch_head_mean(const AttnParams& p, int nqb, float* out, hipStream_t s) {
-  const size_t lds = head_mean_lds(sizeof(T), DP, p.H);
-  if (lds > 64 * 1024) {  // many heads: the table takes the LDS past the default limit
-    const hipError_t e = hipFuncSetAttribute((const void*)head_mean_kernel<T, DP>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((head_mean_kernel<T, DP>), dim3(p.B * nqb), dim3(256), lds, s, p, nqb,
-                     1.0f / (float)p.H, out);
-  return hipGetLastError();
+  return score_lds(elem, DP, true) + (size_t)4 * 32 * H * sizeof(float);  // + the (m, 1 / l) tables
 }
 
 }  // namespace
 
 hipError_t head_mean_launch(int dtype, const AttnParams& p_in, float* out, hipStream_t s) {
   if (p_in.B <= 0) return hipSuccess;
-  if (!p_in.qkv || !out || p_in.N <= 0 || p_in.N > EVT_ATTN_MAX_TOKENS || p_in.H <= 0 ||
-      p_in.hd <= 0 || p_in.hd > 128 || ((uintptr_t)out & 15))
-    return hipErrorInvalidValue;
-  // (s - m) c <= 0 and the -inf masks need c > 0
-  if (!(p_in.scale_log2 > 0.f && p_in.scale_log2 < INFINITY)) return hipErrorInvalidValue;
-  if (head_mean_lds(2, 128, p_in.H) > 160 * 1024) return hipErrorInvalidValue;  // H <= 254
-  AttnParams p = p_in;
-  if (p.sb || p.sh || p.ko) {  // an explicit slice layout: bf16, h_k = 64, 16-B aligned pieces
-    if (dtype != DT_BF16 || p.hd != 64 || p.sb % 8 || p.sh % 8 || p.ldq % 8 || p.ko % 8 ||
-        p.ldq < 64 || p.ko < 0 || p.sb < 0 || p.sh < 0)
-      return hipErrorInvalidValue;
-  } else {
-    p.sb = (int64_t)p.N * p.ldq;
-    p.sh = p.hd;
-    p.ko = p.H * p.hd;
-  }
+  AttnParams p;
+  if (!prepare(dtype, p_in, out, p)) return hipErrorInvalidValue;
+  if (head_mean_lds(2, 128, p.H) > 160 * 1024) return hipErrorInvalidValue;  // H <= 254
   const int nqb = ((p.N + 15) / 16 + 3) / 4;
   if ((int64_t)p.B * nqb > INT32_MAX) return hipErrorInvalidValue;
-  if (dtype == DT_BF16) {
-    if (p.hd <= 32) return launch_head_mean<bf16, 32>(p, nqb, out, s);
-    if (p.hd <= 64) return launch_head_mean<bf16, 64>(p, nqb, out, s);
-    if (p.hd <= 96) return launch_head_mean<bf16, 96>(p, nqb, out, s);
-    return launch_head_mean<bf16, 128>(p, nqb, out, s);
-  }
-  if (dtype != DT_F32) return hipErrorInvalidValue;
-  if (p.hd <= 64) return launch_head_mean<float, 64>(p, nqb, out, s);
-  return launch_head_mean<float, 128>(p, nqb, out, s);
+  return dispatch(dtype, p.hd, [&](auto v) {
+    using V = decltype(v);
+    using T = typename V::type;
+    const size_t lds = head_mean_lds(sizeof(T), V::DP, p.H);
+    if (lds > 64 * 1024) {  // many heads: the table takes the LDS past the default limit
+      const hipError_t e = hipFuncSetAttribute((const void*)head_mean_kernel<T, V::DP>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((head_mean_kernel<T, V::DP>), dim3(p.B * nqb), dim3(256), lds, s, p, nqb,
+                       1.0f / (float)p.H, out);
+    return hipGetLastError();
+  });
 }
 
 // ---- Swin window attention maps (include/evt_window_attention.h) -------------------------------

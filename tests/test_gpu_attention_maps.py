@@ -81,8 +81,10 @@ def _op_inputs(B, H, N, hd, dtype, gain):
     return qkv, ref
 
 
-def _probs(dtype, qkv, B, N, H, hd, nq, gpu, head_major=False):
-    """evt_attention_probs into a guarded NaN-filled buffer -> [B, H, nq, N]."""
+def _probs(dtype, qkv, B, N, H, hd, nq, gpu, head_major=False, scale=None):
+    """evt_attention_probs into a guarded NaN-filled buffer -> [B, H, nq, N]. scale: hd^-0.5
+    unless given."""
+    scale = hd ** -0.5 if scale is None else scale
     if head_major:  # [B][H][q | k | v][N][64]
         qkv = qkv.view(B, N, 3, H, 64).permute(0, 3, 2, 1, 4).contiguous()
         ldq, sb, sh, ko = 64, 3 * H * N * 64, 3 * N * 64, N * 64
@@ -91,7 +93,7 @@ def _probs(dtype, qkv, B, N, H, hd, nq, gpu, head_major=False):
     holder, dev = _embed(qkv, gpu)
     flat, out = _buffer((B, H, nq, N), gpu)
     _lib.check(_lib.load_library().evt_attention_probs(
-        _lib.DTYPE[dtype], _p(dev), ldq, sb, sh, ko, B, N, H, hd, hd ** -0.5, nq, _p(out), _s()))
+        _lib.DTYPE[dtype], _p(dev), ldq, sb, sh, ko, B, N, H, hd, scale, nq, _p(out), _s()))
     torch.cuda.synchronize()
     assert _written(flat), "NaN left in the output (or read past qkv) or guard words overwritten"
     del holder

@@ -31,6 +31,7 @@ from edgevisiontransformer_amd.modeling.models.vit import ViT
 from edgevisiontransformer_amd.weights import make_swin_params, swin_config
 from tests import _rollout_probes as rp
 from tests._ops import TDT, _p, _s
+from tests.test_gpu_attention_maps import _op_inputs, _probs
 from tests.test_gpu_features import _buffer, _written
 from tests.test_gpu_head_stats import MODELS, _embed, _image
 
@@ -120,6 +121,34 @@ def test_rollout_op_head_sizes(gpu, case, dtype):
 @pytest.mark.parametrize("n", rp.BIG)
 def test_rollout_op_big(gpu, n):
     _op_case("bf16", n, 64, gpu, b=1, h=1)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("case", [(2, 3, 65, 64), (1, 3, 197, 64), (1, 2, 65, 80), (1, 2, 17, 20)],
+                         ids=lambda c: "x".join(map(str, c)))
+def test_head_mean_is_head_ordered_sum_of_export(gpu, case, dtype):
+    """head_mean_kernel and attn_probs_kernel form their probabilities with one score core
+    (csrc/attn_scores.h), so the head mean (the scratch of a step with r_in = NULL holds Abar,
+    include/evt_rollout.h) is, bit for bit, the fp32 sum of the exported maps in head order from
+    0, times fl(1 / H)."""
+    b, h, n, hd = case
+    qkv, _ = _op_inputs(b, h, n, hd, dtype, 1.0)
+    scale = rp.ap.scale_of(hd)  # one scale for both entry points
+    p = _probs(dtype, qkv, b, n, h, hd, n, gpu, scale=scale).cpu().numpy()
+    holder, dev = _embed(qkv, gpu)
+    flat, out = _buffer((b, n, n), gpu)
+    sflat, scratch = _buffer((b, n, n), gpu)
+    _lib.check(_lib.load_library().evt_attention_rollout_step(
+        _lib.DTYPE[dtype], _p(dev), qkv.shape[1], 0, 0, 0, b, n, h, hd, scale, None,
+        _p(out), _p(scratch), b * n * n * 4, _s()))
+    torch.cuda.synchronize()
+    assert _written(flat) and _written(sflat)
+    del holder
+    acc = np.zeros((b, n, n), np.float32)
+    for i in range(h):
+        acc = acc + p[:, i]
+    want = acc * (np.float32(1) / np.float32(h))
+    assert want.dtype == np.float32 and np.array_equal(scratch.cpu().numpy(), want)
 
 
 def test_rollout_op_rejects_in_place(gpu):
