@@ -272,6 +272,26 @@ ROLLOUT_SIGNATURES = {
                                         _P, ctypes.c_size_t, _P]),
 }
 
+class evt_token_pruning_args(ctypes.Structure):
+    _fields_ = [("n_blocks", ctypes.c_int32), ("scores", ctypes.POINTER(ctypes.c_void_p)),
+                ("kept", ctypes.POINTER(ctypes.c_void_p))]
+
+
+# include/evt_token_pruning.h constant
+TOKEN_SCHEDULE_MAX = 64
+# the entry points of include/evt_token_pruning.h (evt.h includes it; bound like SIGNATURES)
+TOKEN_PRUNING_SIGNATURES = {
+    "evt_model_set_token_schedule": (_I, [_P, _I, _PI32, _PI32, _P]),
+    "evt_model_token_schedule": (_I, [_P, _PI, _PI32, _PI32, _I]),
+    "evt_model_tokens_at": (_I, [_P, _I, _PI]),
+    "evt_forward_token_pruning": (_I, [_P, ctypes.POINTER(evt_image_args), _I,
+                                       ctypes.POINTER(evt_features_args),
+                                       ctypes.POINTER(evt_token_pruning_args), _P]),
+    "evt_token_scores": (_I, [_I, _P, _I64, _I64, _I64, _I, _I, _I, _I, _I, _F, _P, _P]),
+    "evt_token_select": (_I, [_P, _I, _I, _I, _P, _P]),
+    "evt_token_gather": (_I, [_I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
+}
+
 # the entry points of include/evt_window_attention.h (evt.h includes it; bound like SIGNATURES)
 WINDOW_ATTENTION_SIGNATURES = {
     "evt_window_attn_map_shape": (_I, [_P, _I, _PI, _PI, _PI]),
@@ -342,7 +362,7 @@ def load_library() -> ctypes.CDLL:
                                       **TAIL_SIGNATURES, **HEAD_STATS_SIGNATURES,
                                       **ROLLOUT_SIGNATURES, **FFN_STATS_SIGNATURES,
                                       **CLASSIFY_SIGNATURES, **WORKSPACE_SIGNATURES,
-                                      **PERFORMER_SIGNATURES}.items():
+                                      **PERFORMER_SIGNATURES, **TOKEN_PRUNING_SIGNATURES}.items():
                 if lenient and not hasattr(lib, name):
                     continue
                 fn = getattr(lib, name)

@@ -16,6 +16,7 @@ LIB = os.path.join(HERE, "libevt_hip.so")
 OBJ = os.path.join(HERE, "build_obj")
 SOURCES = ["gemm.hip", "attention.hip", "norm.hip", "t2t.hip", "swin.hip", "mx8.hip",
            "features.hip", "preprocess.hip", "attn_maps.hip", "rollout.hip", "ffn_stats.hip",
+           "token_pruning.hip",
            "model.cpp", "encoder.cpp", "model_vit.cpp", "model_t2t.cpp", "model_swin.cpp",
            "ops.cpp", "resize_plan.cpp"]
 # the GEMM kernels, one header per kernel, all included by gemm.hip (one translation unit)
@@ -32,6 +33,7 @@ HEADERS = GEMM_HEADERS + [
            os.path.join("..", "..", "include", "evt_head_stats.h"),
            os.path.join("..", "..", "include", "evt_ffn_stats.h"),
            os.path.join("..", "..", "include", "evt_rollout.h"),
+           os.path.join("..", "..", "include", "evt_token_pruning.h"),
            os.path.join("..", "..", "include", "evt_window_attention.h"),
            os.path.join("..", "..", "include", "evt_tail.h"),
            os.path.join("..", "..", "include", "evt_classify.h"),
@@ -46,7 +48,8 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-re
 # attention / window-attention / performer accumulators in AGPRs and copies every element back
 # (v_accvgpr_read) before the softmax / GELU VALU work (96 copies per window-attention wave).
 PER_FILE_FLAGS = {s: ["-mllvm", "-amdgpu-mfma-vgpr-form=true"]
-                  for s in ("attention.hip", "swin.hip", "t2t.hip", "attn_maps.hip")}
+                  for s in ("attention.hip", "swin.hip", "t2t.hip", "attn_maps.hip",
+                           "token_pruning.hip")}
 # attention.hip: no NaN operands either (scores of finite bf16 / fp32 q, k; masked keys are -inf):
 # the softmax max runs on the raw MFMA results without a canonicalising v_max per element
 PER_FILE_FLAGS["attention.hip"] = PER_FILE_FLAGS["attention.hip"] + ["-fno-honor-nans"]

@@ -152,51 +152,6 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(AttnParams p, int nq, i
   }
 }
 
-// What the three launchers below ask of their parameters alike; fills the default slice layout.
-// c > 0: (s - m) c <= 0 and the -inf masks need it.
-bool prepare(int dtype, const AttnParams& p_in, const float* out, AttnParams& p) {
-  if (!p_in.qkv || !out || p_in.N <= 0 || p_in.N > EVT_ATTN_MAX_TOKENS || p_in.H <= 0 ||
-      p_in.hd <= 0 || p_in.hd > 128 || ((uintptr_t)out & 15) ||
-      (dtype != DT_BF16 && dtype != DT_F32))
-    return false;
-  if (!(p_in.scale_log2 > 0.f && p_in.scale_log2 < INFINITY)) return false;
-  p = p_in;
-  if (p.sb || p.sh || p.ko) {  // an explicit slice layout: bf16, h_k = 64, 16-B aligned pieces
-    if (dtype != DT_BF16 || p.hd != 64 || p.sb % 8 || p.sh % 8 || p.ldq % 8 || p.ko % 8 ||
-        p.ldq < 64 || p.ko < 0 || p.sb < 0 || p.sh < 0)
-      return false;
-  } else {
-    p.sb = (int64_t)p.N * p.ldq;
-    p.sh = p.hd;
-    p.ko = p.H * p.hd;
-  }
-  return true;
-}
-
-template <typename T, int DP_>
-struct Variant {
-  using type = T;
-  static constexpr int DP = DP_;
-};
-
-// f(Variant<T, DP>) of the instantiation for a (prepared) dtype and head size
-template <typename F>
-hipError_t dispatch(int dtype, int hd, F&& f) {
-  if (dtype == DT_BF16) {
-    if (hd <= 32) return f(Variant<bf16, 32>{});
-    if (hd <= 64) return f(Variant<bf16, 64>{});
-    if (hd <= 96) return f(Variant<bf16, 96>{});
-    return f(Variant<bf16, 128>{});
-  }
-  if (hd <= 64) return f(Variant<float, 64>{});
-  return f(Variant<float, 128>{});
-}
-
-// LDS bytes of the waves' four P tiles (a kernel that stores rows) and, for bf16, one K block
-constexpr size_t score_lds(size_t elem, int DP, bool tiles) {
-  return (tiles ? 4 * PTILE * 4 : 0) + (elem == 2 ? (size_t)KB * DP * 2 : 0);
-}
-
 // the store form (file header): dword unless EVT_ATTN_MAPS_STORE=wide asks for the other one
 bool wide_stores() {
   const char* e = std::getenv("EVT_ATTN_MAPS_STORE");

@@ -1,5 +1,6 @@
 // The score core of the ViT attention-map kernels (attn_maps.hip: attn_probs_kernel,
-// head_stats_kernel, head_mean_kernel), defined once so that the three form the same scores and
+// head_stats_kernel, head_mean_kernel; token_pruning.hip: token_scores_kernel), defined once so
+// that they form the same scores and
 // the same softmax statistics (m, l), bit for bit, by construction:
 //
 //   S^T = K Q^T on the MFMA (one query per lane column, four consecutive keys per lane) over
@@ -10,7 +11,7 @@
 //
 // Also here: the helpers attention.hip's any-head-size kernels share with it (k_swm, chunk8,
 // chunk4), the XCD unswizzle of a (group, 64-query block) grid and the row-segment store of a
-// wave's P tile.
+// wave's P tile; and what the kernels' launchers share (prepare, dispatch, score_lds).
 //
 // The file is compiled with -ffp-contract=on: a floating-point expression contracts only within
 // itself, so every expression below keeps its boundaries (l = l * ex2(..) + sum is one).
@@ -228,6 +229,54 @@ struct AttnScores {
     l_out = l;
   }
 };
+
+// ---- the launchers' side (attn_maps.hip, token_pruning.hip) ----
+
+// What the launchers of these kernels ask of their parameters alike; fills the default slice
+// layout. c > 0: (s - m) c <= 0 and the -inf masks need it. align: bytes `out` is aligned to.
+inline bool prepare(int dtype, const AttnParams& p_in, const float* out, AttnParams& p,
+                    int align = 16) {
+  if (!p_in.qkv || !out || p_in.N <= 0 || p_in.N > EVT_ATTN_MAX_TOKENS || p_in.H <= 0 ||
+      p_in.hd <= 0 || p_in.hd > 128 || ((uintptr_t)out & (uintptr_t)(align - 1)) ||
+      (dtype != DT_BF16 && dtype != DT_F32))
+    return false;
+  if (!(p_in.scale_log2 > 0.f && p_in.scale_log2 < INFINITY)) return false;
+  p = p_in;
+  if (p.sb || p.sh || p.ko) {  // an explicit slice layout: bf16, h_k = 64, 16-B aligned pieces
+    if (dtype != DT_BF16 || p.hd != 64 || p.sb % 8 || p.sh % 8 || p.ldq % 8 || p.ko % 8 ||
+        p.ldq < 64 || p.ko < 0 || p.sb < 0 || p.sh < 0)
+      return false;
+  } else {
+    p.sb = (int64_t)p.N * p.ldq;
+    p.sh = p.hd;
+    p.ko = p.H * p.hd;
+  }
+  return true;
+}
+
+template <typename T, int DP_>
+struct Variant {
+  using type = T;
+  static constexpr int DP = DP_;
+};
+
+// f(Variant<T, DP>) of the instantiation for a (prepared) dtype and head size
+template <typename F>
+hipError_t dispatch(int dtype, int hd, F&& f) {
+  if (dtype == DT_BF16) {
+    if (hd <= 32) return f(Variant<bf16, 32>{});
+    if (hd <= 64) return f(Variant<bf16, 64>{});
+    if (hd <= 96) return f(Variant<bf16, 96>{});
+    return f(Variant<bf16, 128>{});
+  }
+  if (hd <= 64) return f(Variant<float, 64>{});
+  return f(Variant<float, 128>{});
+}
+
+// LDS bytes of the waves' four P tiles (a kernel that stores rows) and, for bf16, one K block
+constexpr size_t score_lds(size_t elem, int DP, bool tiles) {
+  return (tiles ? 4 * PTILE * 4 : 0) + (elem == 2 ? (size_t)KB * DP * 2 : 0);
+}
 
 }  // namespace scores
 }  // namespace evt

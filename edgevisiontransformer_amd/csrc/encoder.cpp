@@ -105,13 +105,59 @@ int dense_head(const evt_model* m, const DenseW& w, const DenseCall& c, hipStrea
   return EVT_OK;
 }
 
+// After a scheduled block's FC2 (include/evt_token_pruning.h): the CLS-attention scores of the q and
+// k the block left in ws.qkv (`ap`), the K kept patch tokens, and the stream rows and statistics
+// of the kept tokens packed from x / sx into xm / sm, idle at block end, whose roles then swap
+// (vit_run puts the handle's pointers back when the call has been enqueued). Scores and the kept
+// table live in the FFN hidden buffer, idle too, or where the call exports them. Three launches,
+// counted under EVT_PROF_HEAD.
+static int token_prune(evt_model* m, ForwardCall& call, const AttnParams& ap, int K, int entry) {
+  const int B = call.B, T = ap.N, D = m->D, slots = stats_slots(D);
+  hipStream_t s = call.s;
+  const size_t sbytes = (size_t)round_up((int64_t)B * T * sizeof(float), 16);
+  if (sbytes + (size_t)B * (K + 1) * sizeof(int32_t) > m->ws.hbuf_bytes)
+    return fail(EVT_EINVAL, "token pruning: the FFN hidden buffer is too small for the scores");
+  float* sc = (float*)m->ws.hbuf;
+  int32_t* kept = (int32_t*)((char*)m->ws.hbuf + sbytes);
+  if (const evt_token_pruning_args* a = call.tprune) {
+    if (a->scores && a->scores[entry]) sc = a->scores[entry];
+    if (a->kept && a->kept[entry]) kept = a->kept[entry];
+  }
+  const double es = (double)elem_size(m->dtype);
+  {
+    ProfScope ps(m, EVT_PROF_HEAD, s);
+    const double nkb = (T + 63) / 64;  // pass 1 once per key block of an image, then the block
+    prof_work(m, 2.0 * B * ap.H * 16.0 * (double)T * ap.hd * (nkb + 1),
+              (double)B * ap.H * T * ap.hd * es * (nkb + 1) + 4.0 * B * T);
+    EVT_HIP(token_scores_launch(m->dtype, ap, sc, s), "token scores");
+  }
+  {
+    ProfScope ps(m, EVT_PROF_HEAD, s);
+    prof_work(m, 0.0, 4.0 * B * (T + K + 1));
+    EVT_HIP(token_select_launch(sc, B, T, K, kept, s), "token select");
+  }
+  {
+    ProfScope ps(m, EVT_PROF_HEAD, s);
+    prof_work(m, 0.0, 2.0 * B * (K + 1) * (D * es + slots * 8.0) + 4.0 * B * (K + 1));
+    EVT_HIP(token_gather_launch(m->dtype, m->ws.x, m->ws.xm, m->ws.sx, m->ws.sm, slots, kept, B, T,
+                                K + 1, D, s),
+            "token gather");
+  }
+  std::swap(m->ws.x, m->ws.xm);
+  std::swap(m->ws.sx, m->ws.sm);
+  return EVT_OK;
+}
+
 // Encoder layers (transformer_encoder.py:13-18 / :26-34) on the token stream m->ws.x (+ stats sx).
+// T tokens per image: sh.T until a block of the handle's token schedule, 1 + K_l after it.
 int run_encoder(evt_model* m, ForwardCall& call) {
-  const int B = call.B, D = m->D, T = m->sh.T, rows = B * T;
+  const int B = call.B, D = m->D;
+  int T = m->sh.T, rows = B * T;
   hipStream_t s = call.s;
   const float log2e = 1.4426950408889634f;
   m->hm_layers = 0;
   m->tail_mode = 0;
+  call.tprune_next = 0;
   int block = 0;
   for (const Layer& L : m->layers) {
     const float scale_log2 = log2e / std::sqrt((float)L.hd);  // h_k^-0.5 (attention.py:13)
@@ -227,8 +273,16 @@ int run_encoder(evt_model* m, ForwardCall& call) {
       if (full) EVT_RC(dense(m, L.fc2, c2, s));
       if (last) EVT_RC(dense(m, L.fc2, tail(c2), s));
     }
-    EVT_RC(feat_tap(m, call, block++, D, rows, D));
+    EVT_RC(feat_tap(m, call, block, D, rows, D));
+    if (call.tprune_next < (int)m->tp_blocks.size() && m->tp_blocks[call.tprune_next] == block) {
+      const int K = m->tp_keep[call.tprune_next];
+      EVT_RC(token_prune(m, call, ap, K, call.tprune_next++));
+      T = K + 1;
+      rows = B * T;
+    }
+    ++block;
   }
+  call.T = T;
   return EVT_OK;
 }
 
@@ -274,7 +328,7 @@ int run_encoder_mx8(evt_model* m, ForwardCall& call) {
 // stream the last encoder block left in ws.x
 int encoder_features(evt_model* m, const ForwardCall& call) {
   const evt_features_args* a = call.feat;
-  const int B = call.B, D = m->D, T = m->sh.T;
+  const int B = call.B, D = m->D, T = call.T ? call.T : m->sh.T;
   hipStream_t s = call.s;
   const bool norm = m->norm_g != nullptr;  // REFERENCE ViT: no final LayerNorm (vit.py:54)
   if (a->tokens) EVT_RC(feat_export(m, m->ws.x, D, 1, a->tokens, norm, B * T, D, s));

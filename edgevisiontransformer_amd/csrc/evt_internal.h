@@ -162,6 +162,20 @@ inline size_t rollout_buf_bytes(int B, int N) {
   return (((size_t)B * N * N * sizeof(float)) + 255) & ~(size_t)255;
 }
 
+// Token pruning (token_pruning.hip; include/evt_token_pruning.h), the three launches after a
+// scheduled block. token_scores_launch: out[b][j] = sum_h p[b][h][0][j] of the probabilities
+// attn_probs_launch exports (bitwise their head-ordered fp32 sum), fp32 contiguous [B][N]; p as
+// attn_probs_launch, out 4-byte aligned. token_select_launch: kept[b] = (0, the K entries j >= 1
+// of scores[b] (rows N floats apart) that come first in np.argsort(-s, kind="stable"), ascending),
+// int32 [B][K + 1]; 2 <= N <= 4096, 1 <= K <= N - 1. token_gather_launch: dst row b K1 + t = src
+// row b T + kept[b][t] (D elements of dtype, D % 8 == 0) and, with ssrc / sdst, the rows' `slots`
+// (sum, sumsq) pairs (slots even); 16-byte aligned, dst must not overlap src (the caller's check).
+hipError_t token_scores_launch(int dtype, const AttnParams& p, float* out, hipStream_t s);
+hipError_t token_select_launch(const float* scores, int B, int N, int K, int* kept, hipStream_t s);
+hipError_t token_gather_launch(int dtype, const void* src, void* dst, const float* ssrc,
+                               float* sdst, int slots, const int* kept, int B, int T, int K1,
+                               int D, hipStream_t s);
+
 // FFN neuron statistics (ffn_stats.hip; include/evt_ffn_stats.h): out[b][j][0..3] = (mean, mean_abs,
 // mean_sq, max_abs) over the T rows of image b of column j < F of the row-major matrix h (B T rows,
 // pitch ld elements, dtype bf16 or f32), fp32 contiguous [B][F][4]. One launch, no scratch; h and

@@ -315,6 +315,20 @@ int window_attn_map(evt_model* m, ForwardCall& call, int block, int w, const Swi
   return EVT_OK;
 }
 
+// T_l of block `block` under m's token schedule: the tokens per image the block runs on
+int tokens_at(const ModelCore& m, int block) {
+  int T = m.sh.T;
+  for (size_t i = 0; i < m.tp_blocks.size() && m.tp_blocks[i] < block; ++i) T = m.tp_keep[i] + 1;
+  return T;
+}
+
+int no_token_schedule(const evt_model* m, const char* what) {
+  if (m->tp_blocks.empty()) return EVT_OK;
+  return fail(EVT_EINVAL, std::string(what) + " is not available while a token schedule is set: "
+                          "the stream drops tokens between blocks (clear it with "
+                          "evt_model_set_token_schedule(m, 0, ...))");
+}
+
 int finish_create(evt_model* m, int rc, evt_model** out) {
   if (rc) {
     std::string keep = g_err;
@@ -631,6 +645,8 @@ static int validate_features(const evt_model* m, const evt_features_args* a, int
   if (!a->logits && !a->pooled && !a->tokens && a->n_taps == 0)
     return fail(EVT_EINVAL, "no output requested: logits, pooled and tokens are NULL, n_taps is 0");
   EVT_RC(check_batch(m, B));  // (here, ahead of forward's own: the order the checks fire in)
+  if (a->tokens) EVT_RC(no_token_schedule(m, "the final token map (tokens)"));
+  if (a->n_taps > 0) EVT_RC(no_token_schedule(m, "a block tap"));
   if (a->tap_norm != 0 && a->tap_norm != 1) return fail(EVT_EINVAL, "tap_norm must be 0 or 1");
   if (a->tap_norm && (m->family == FAM_SWIN || !m->norm_g))
     return fail(EVT_EINVAL, m->family == FAM_SWIN
@@ -784,6 +800,7 @@ int evt_forward_attention(evt_model* m, const evt_image_args* in, int B,
   if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and attn must be non-null");
   EVT_RC(validate_image(m, in, &aff));
   EVT_RC(attn_family(m));
+  EVT_RC(no_token_schedule(m, "evt_forward_attention"));
   EVT_RC(validate_attn(m, B, feat, a, (int)m->layers.size(), true));
   ForwardCall call = image_call(in, aff, B, feat ? feat->logits : nullptr, stream);
   call.feat = feat;
@@ -818,6 +835,7 @@ int evt_forward_head_stats(evt_model* m, const evt_image_args* in, int B,
   if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and hs must be non-null");
   EVT_RC(validate_image(m, in, &aff));
   EVT_RC(attn_family(m));
+  EVT_RC(no_token_schedule(m, "evt_forward_head_stats"));
   if (a->n_blocks < 0 || a->n_blocks > 64) return fail(EVT_EINVAL, "n_blocks must be in [0, 64]");
   if (a->n_blocks == 0 && !feat)
     return fail(EVT_EINVAL, "no output requested: n_blocks is 0 and feat is NULL");
@@ -878,6 +896,7 @@ int evt_forward_ffn_stats(evt_model* m, const evt_image_args* in, int B,
   if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and fs must be non-null");
   EVT_RC(validate_image(m, in, &aff));
   EVT_RC(ffn_stats_family(m));
+  EVT_RC(no_token_schedule(m, "evt_forward_ffn_stats"));
   if (a->n_blocks < 0 || a->n_blocks > 64) return fail(EVT_EINVAL, "n_blocks must be in [0, 64]");
   if (a->n_blocks == 0 && !feat)
     return fail(EVT_EINVAL, "no output requested: n_blocks is 0 and feat is NULL");
@@ -939,6 +958,7 @@ int evt_forward_rollout(evt_model* m, const evt_image_args* in, int B,
   if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and ro must be non-null");
   EVT_RC(validate_image(m, in, &aff));
   EVT_RC(rollout_family(m));
+  EVT_RC(no_token_schedule(m, "evt_forward_rollout"));
   if (feat) EVT_RC(validate_features(m, feat, B));
   else EVT_RC(check_batch(m, B));
   const int depth = (int)m->layers.size();
@@ -956,6 +976,101 @@ int evt_forward_rollout(evt_model* m, const evt_image_args* in, int B,
   ForwardCall call = image_call(in, aff, B, feat ? feat->logits : nullptr, stream);
   call.feat = feat;
   call.rollout = a;
+  // one lane, on this handle's own workspace, whatever its lane count (as evt_forward_attention)
+  return forward(m, call, false);
+}
+
+// ---- token pruning (include/evt_token_pruning.h) ---------------------------------------------
+
+static int token_pruning_family(const evt_model* m) {
+  if (m->family == FAM_SWIN)
+    return fail(EVT_EINVAL, "token pruning: Swin's windows need the whole token grid");
+  if (m->family == FAM_T2T)
+    return fail(EVT_EINVAL, "token pruning: T2T-ViT is not supported yet (ViT handles only)");
+  if (m->mx8)
+    return fail(EVT_EINVAL, "token pruning is not available on an EVT_DTYPE_MX8 model");
+  return EVT_OK;
+}
+
+int evt_model_set_token_schedule(evt_model* m, int n, const int32_t* blocks, const int32_t* keep,
+                                 void*) {
+  if (!m) return fail(EVT_EINVAL, "model is NULL");
+  if (m->is_lane) return fail(EVT_EINVAL, "the model is a lane of another model");
+  EVT_RC(token_pruning_family(m));
+  if (m->graph) return fail(EVT_EINVAL, "set the schedule before evt_graph_capture");
+  if (n < 0 || n > EVT_TOKEN_SCHEDULE_MAX)
+    return fail(EVT_EINVAL, "token schedule: n must be in [0, " +
+                                std::to_string(EVT_TOKEN_SCHEDULE_MAX) + "]");
+  if (n > 0 && (!blocks || !keep))
+    return fail(EVT_EINVAL, "token schedule: n > 0 needs the blocks and keep arrays");
+  const int depth = (int)m->layers.size();
+  int T = m->sh.T;
+  for (int i = 0; i < n; ++i) {
+    if (i > 0 && blocks[i] <= blocks[i - 1])
+      return fail(EVT_EINVAL, "token schedule: blocks must be strictly ascending");
+    if (blocks[i] < 0 || blocks[i] >= depth - 1)
+      return fail(EVT_EINVAL, "token schedule: block " + std::to_string(blocks[i]) +
+                                  " is outside [0, depth - 1 = " + std::to_string(depth - 1) +
+                                  "): the last block's output is the CLS token's alone");
+    if (keep[i] < 1 || keep[i] > T - 1)
+      return fail(EVT_EINVAL, "token schedule: keep " + std::to_string(keep[i]) + " after block " +
+                                  std::to_string(blocks[i]) + " is outside [1, " +
+                                  std::to_string(T - 1) + "], the block's patch tokens");
+    T = keep[i] + 1;
+  }
+  m->tp_blocks.assign(blocks, blocks + n);
+  m->tp_keep.assign(keep, keep + n);
+  for (evt_model* c : m->lanes) {  // lanes set later copy the core, the schedule with it
+    c->tp_blocks = m->tp_blocks;
+    c->tp_keep = m->tp_keep;
+  }
+  return EVT_OK;
+}
+
+int evt_model_token_schedule(const evt_model* m, int* n, int32_t* blocks, int32_t* keep, int cap) {
+  if (!m || !n || cap < 0) return fail(EVT_EINVAL, "token schedule: a NULL model or n, or cap < 0");
+  *n = (int)m->tp_blocks.size();
+  for (int i = 0; i < *n && i < cap; ++i) {
+    if (blocks) blocks[i] = m->tp_blocks[i];
+    if (keep) keep[i] = m->tp_keep[i];
+  }
+  return EVT_OK;
+}
+
+int evt_model_tokens_at(const evt_model* m, int block, int* tokens) {
+  if (!m || !tokens) return fail(EVT_EINVAL, "null argument");
+  if (m->family != FAM_VIT)
+    return fail(EVT_EINVAL, "tokens_at: token schedules are a ViT handle's");
+  if (block < 0 || block >= (int)m->layers.size())
+    return fail(EVT_EINVAL, "block must be in [0, " + std::to_string(m->layers.size()) + ")");
+  *tokens = tokens_at(*m, block);
+  return EVT_OK;
+}
+
+int evt_forward_token_pruning(evt_model* m, const evt_image_args* in, int B,
+                              const evt_features_args* feat, const evt_token_pruning_args* tp,
+                              void* stream) {
+  ImgAffine aff{};
+  if (!m || !in || !feat)
+    return fail(EVT_EINVAL, "model, image descriptor and feat must be non-null");
+  EVT_RC(validate_image(m, in, &aff));
+  EVT_RC(token_pruning_family(m));
+  if (m->tp_blocks.empty())
+    return fail(EVT_EINVAL, "forward_token_pruning: the model has no token schedule "
+                            "(evt_model_set_token_schedule first)");
+  EVT_RC(validate_features(m, feat, B));  // tokens and taps: refused under a schedule
+  if (tp) {
+    const int n = (int)m->tp_blocks.size();
+    if (tp->n_blocks != n)
+      return fail(EVT_EINVAL, "forward_token_pruning: n_blocks must be the schedule's length " +
+                                  std::to_string(n));
+    for (int i = 0; i < n; ++i)
+      if (((tp->scores ? (uintptr_t)tp->scores[i] : 0) | (tp->kept ? (uintptr_t)tp->kept[i] : 0)) & 3)
+        return fail(EVT_EINVAL, "forward_token_pruning: scores and kept must be 4-byte aligned");
+  }
+  ForwardCall call = image_call(in, aff, B, feat->logits, stream);
+  call.feat = feat;
+  call.tprune = tp;
   // one lane, on this handle's own workspace, whatever its lane count (as evt_forward_attention)
   return forward(m, call, false);
 }

@@ -138,6 +138,10 @@ struct ModelCore {
   // norm_g / norm_b: the final LayerNorm; STANDARD ViT and T2T-ViT keep it too (their heads have
   // it folded into the weights) for the feature outputs; null for a REFERENCE ViT (it has none)
   float *pnorm_g = nullptr, *pnorm_b = nullptr, *norm_g = nullptr, *norm_b = nullptr;
+  // evt_model_set_token_schedule (ViT): after block tp_blocks[i] the stream keeps the CLS token and
+  // tp_keep[i] patch tokens. The one part of a core that changes after create; lane children get
+  // the parent's copy (set_lanes copies the core, set_token_schedule writes every lane)
+  std::vector<int32_t> tp_blocks, tp_keep;
   // desc's per-layer arrays live in this core's own vectors (after every copy of a core)
   void bind_desc() {
     desc.heads = heads.data();
@@ -232,6 +236,9 @@ struct ForwardCall {
   const evt_ffn_stats_args* fstats = nullptr;  // evt_forward_ffn_stats blocks (null: none)
   int fstats_next = 0;            // the next entry of fstats' block list
   const evt_rollout_args* rollout = nullptr;  // evt_forward_rollout (null: none)
+  const evt_token_pruning_args* tprune = nullptr;  // evt_forward_token_pruning exports (null: none)
+  int tprune_next = 0;            // the next entry of the handle's token schedule
+  int T = 0;                      // tokens per image of the stream run_encoder left (0: sh.T)
   hipStream_t s = nullptr;
   // images [b0, b1) of a logits-only call, on stream `lane`: the input advances by whole images
   // (4 bytes per element of an fp32 batch, 1 of a uint8 one), the logits by rows
@@ -372,6 +379,10 @@ int head_stats(evt_model* m, ForwardCall& call, int block, const AttnParams& ap)
 int ffn_stats(evt_model* m, ForwardCall& call, int block, const Layer& L, int rows);
 // evt_forward_rollout: block's head mean and rollout step, from the call's start block on
 int rollout_step(evt_model* m, ForwardCall& call, int block, const AttnParams& ap);
+// Token pruning (include/evt_token_pruning.h). tokens_at: T_l of block `block` under m's schedule.
+// no_token_schedule: EVT_EINVAL naming the schedule if m has one (`what` reads all T tokens).
+int tokens_at(const ModelCore& m, int block);
+int no_token_schedule(const evt_model* m, const char* what);
 // evt_forward_window_attention (Swin): whether the call asks for block's map next, and the export
 bool window_attn_wanted(const ForwardCall& call, int block);
 int window_attn_map(evt_model* m, ForwardCall& call, int block, int w, const SwinAttnParams& ap);

@@ -108,11 +108,19 @@ WsLayout vit_ws(const Shape& sh, int dtype, bool mx8, int B) {
 int vit_run(evt_model* m, ForwardCall& call) {
   const evt_vit_desc& d = m->desc;
   const Shape& sh = m->sh;
-  const int B = call.B, D = d.dim, T = sh.T, dt = m->dtype;
+  const int B = call.B, D = d.dim, dt = m->dtype;
   const float* img = call.img;
   float* logits = call.logits;
   hipStream_t s = call.s;
   prof_reset(m);
+  // a token schedule swaps the roles of x / xm and sx / sm at every scheduled block (encoder.cpp
+  // token_prune): the handle gets its own pointers back once the call is enqueued, however it ends
+  struct StreamRoles {
+    Workspace& ws;
+    void *x, *xm;
+    float *sx, *sm;
+    ~StreamRoles() { ws.x = x; ws.xm = xm; ws.sx = sx; ws.sm = sm; }
+  } roles{m->ws, m->ws.x, m->ws.xm, m->ws.sx, m->ws.sm};
   // patch embedding (vit.py:45-51): rearrange -> Dense(D) + pos, CLS row = cls + pos[0]
   {
     ProfScope ps(m, EVT_PROF_PATCHIFY, s);
@@ -142,7 +150,9 @@ int vit_run(evt_model* m, ForwardCall& call) {
     c.resid = m->pos_h; c.ldr = m->pos_h ? D : 0;  // bf16 table for the persistent kernel
     EVT_RC(dense(m, m->patch, c, s));
   }
+  call.T = sh.T;
   EVT_RC(m->mx8 ? run_encoder_mx8(m, call) : run_encoder(m, call));
+  const int T = call.T;  // tokens per image of the stream the last block left (token schedule)
   if (call.feat) EVT_RC(encoder_features(m, call));
   if (!logits) return EVT_OK;
   ProfScope ps_head(m, EVT_PROF_HEAD, s);

@@ -499,6 +499,76 @@ int evt_attention_rollout_step(int dtype, const void* qkv, int64_t ldq, int64_t 
   return EVT_OK;
 }
 
+// include/evt_token_pruning.h: evt_attention_probs' checks of (qkv, layout, shape, scale)
+int evt_token_scores(int dtype, const void* qkv, int64_t ldq, int64_t sb, int64_t sh, int ko,
+                     int B, int N, int H, int head_dim, float scale, float* scores, void* stream) {
+  if (dtype != EVT_DTYPE_F32 && dtype != EVT_DTYPE_BF16)
+    return fail(EVT_EINVAL, "token_scores: dtype must be EVT_DTYPE_F32 or EVT_DTYPE_BF16");
+  if (!qkv || !scores || B < 0 || N <= 0 || N > EVT_ATTN_MAX_TOKENS || H <= 0 || head_dim <= 0 ||
+      head_dim > 128)
+    return fail(EVT_EINVAL, "token_scores: bad shape (N <= 4096, head size in [1, 128])");
+  if (!(scale > 0.f && scale < INFINITY))
+    return fail(EVT_EINVAL, "token_scores: the scale must be positive and finite");
+  if ((uintptr_t)scores & 3) return fail(EVT_EINVAL, "token_scores: scores must be 4-byte aligned");
+  const int64_t vec = dtype == DT_BF16 ? 8 : 4;
+  if (sb || sh || ko) {
+    if (dtype != DT_BF16 || head_dim != 64 || sb < 0 || sh < 0 || ko < 0 || sb % 8 || sh % 8 ||
+        ko % 8 || ldq % 8 || ldq < 64 || ((uintptr_t)qkv & 15))
+      return fail(EVT_EINVAL, "token_scores: a slice layout needs bf16, head size 64 and "
+                              "non-negative strides that are multiples of 8");
+  } else {
+    if (ldq < 3 * (int64_t)H * head_dim)
+      return fail(EVT_EINVAL, "token_scores: ldq must be at least 3*H*head_dim");
+    if (head_dim % vec == 0 && (ldq % vec || ((uintptr_t)qkv & 15)))
+      return fail(EVT_EINVAL, "token_scores: qkv rows must be 16-B aligned for this head size");
+  }
+  AttnParams p{qkv, ldq, nullptr, 0, N, H, B, scale * 1.4426950408889634f};
+  p.hd = head_dim;
+  p.sb = sb; p.sh = sh; p.ko = ko;
+  EVT_HIP(token_scores_launch(dtype, p, scores, (hipStream_t)stream), "token_scores");
+  return EVT_OK;
+}
+
+int evt_token_select(const float* scores, int B, int N, int K, int32_t* kept, void* stream) {
+  if (!scores || !kept || B < 0)
+    return fail(EVT_EINVAL, "token_select: scores and kept must be non-null, B >= 0");
+  if (N < 2 || N > EVT_ATTN_MAX_TOKENS || K < 1 || K > N - 1)
+    return fail(EVT_EINVAL, "token_select: needs 2 <= N <= 4096 and 1 <= K <= N - 1");
+  if (((uintptr_t)scores | (uintptr_t)kept) & 3)
+    return fail(EVT_EINVAL, "token_select: scores and kept must be 4-byte aligned");
+  EVT_HIP(token_select_launch(scores, B, N, K, kept, (hipStream_t)stream), "token_select");
+  return EVT_OK;
+}
+
+int evt_token_gather(int dtype, const void* src, void* dst, const float* stats_src,
+                     float* stats_dst, int slots, const int32_t* kept, int B, int T, int K1, int D,
+                     void* stream) {
+  if (dtype != EVT_DTYPE_F32 && dtype != EVT_DTYPE_BF16)
+    return fail(EVT_EINVAL, "token_gather: dtype must be EVT_DTYPE_F32 or EVT_DTYPE_BF16");
+  if (!src || !dst || !kept || B < 0 || T < 1 || K1 < 1 || K1 > T || D < 8 || D % 8)
+    return fail(EVT_EINVAL, "token_gather: needs src, dst, kept, 1 <= K1 <= T and D a positive "
+                            "multiple of 8");
+  if ((!stats_src) != (!stats_dst) || (stats_src && (slots < 2 || slots % 2)))
+    return fail(EVT_EINVAL, "token_gather: stats_src and stats_dst go together, slots even");
+  if ((((uintptr_t)src | (uintptr_t)dst | (uintptr_t)stats_src | (uintptr_t)stats_dst) & 15) ||
+      ((uintptr_t)kept & 3))
+    return fail(EVT_EINVAL, "token_gather: rows and statistics must be 16-byte aligned, kept "
+                            "4-byte aligned");
+  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+  };
+  const size_t es = dtype == DT_BF16 ? 2 : 4;
+  if (overlap(src, (size_t)B * T * D * es, dst, (size_t)B * K1 * D * es) ||
+      (stats_src && overlap(stats_src, (size_t)B * T * slots * 8, stats_dst,
+                            (size_t)B * K1 * slots * 8)))
+    return fail(EVT_EINVAL, "token_gather: dst must not overlap src (a gather cannot run in place)");
+  EVT_HIP(token_gather_launch(dtype, src, dst, stats_src, stats_dst, slots, kept, B, T, K1, D,
+                              (hipStream_t)stream),
+          "token_gather");
+  return EVT_OK;
+}
+
 int evt_window_attention_probs(int dtype, const void* qkv, int64_t ldq, const float* rpb, int B,
                                int R, int window, int C, int H, int shift, float* out,
                                void* stream) {

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from ... import _lib
-from .classify import Classification
+from .token_pruning import TokenPruning
 from ...weights import (ViTConfig, make_std_vit_params, make_vit_params, std_vit_param_shapes,
                         vit_config, vit_param_shapes)
 
@@ -54,15 +54,17 @@ def decode_prune_encoding(prune_encoding: str):
     return prune_setting, num_heads_list, ffn_threshold_list
 
 
-class ViT(Classification):
+class ViT(TokenPruning):
     """Vision Transformer forward on MI355X (reference `ViT`, vit.py:9-55).
 
     `image_size` / `patch_size`: any pair with (image_size / patch_size)^2 + 1 <= 4096 tokens per
     image (224 px: 197; 384 px as `get_torch_deit`, utils.py:52-62: 577; patch 14: 257 at 224 px,
     1370 at 518 px; "mx8": <= 256 tokens); the factories (`get_deit_*`, `build_named`) pass
-    `image_size=` through. `dim`: a multiple of 8 up to 1536 ("mx8": of 64, up to 1024)."""
+    `image_size=` through. `dim`: a multiple of 8 up to 1536 ("mx8": of 64, up to 1024).
+    `token_keep`: a token schedule `{block: keep}` (token_pruning.py `set_token_pruning`)."""
 
     SEMANTICS = _lib.VIT_REFERENCE
+    _TOKEN_PRUNING_OK = True
     _param_shapes = staticmethod(vit_param_shapes)
     _make_params = staticmethod(make_vit_params)
     layer_norm_eps = 0.0  # 0: the library default 1e-5 (reference norm.py:6)
@@ -70,7 +72,8 @@ class ViT(Classification):
     def __init__(self, *, image_size=224, patch_size=16, num_classes=1000, dim=768, depth=12,
                  heads=12, mlp_dim=3072, dtype: str = "bf16", seed: int = 0,
                  weights: Optional[Dict[str, np.ndarray]] = None, device=None, max_batch: int = 0,
-                 lanes: Optional[int] = None, _cfg: Optional[ViTConfig] = None):
+                 lanes: Optional[int] = None, token_keep=None,
+                 _cfg: Optional[ViTConfig] = None):
         assert image_size % patch_size == 0, "image dimensions must be divisible by the patch size"
         if _cfg is None:
             if dim % heads != 0:  # reference Attention raises ValueError (attention.py:8-9)
@@ -81,6 +84,7 @@ class ViT(Classification):
         self.image_size, self.patch_size = image_size, patch_size
         self.num_classes, self.dim, self.depth, self.mlp_dim = num_classes, dim, depth, mlp_dim
         self._open_device(dtype, device)
+        self.set_token_pruning(token_keep)  # {block: keep} (token_pruning.py); applied by _build
         params = weights if weights is not None else self._make_params(self.cfg, seed=seed)
         for name, shape in self._param_shapes(self.cfg):
             a = np.asarray(params[name], dtype=np.float32)

@@ -181,6 +181,10 @@ def _server_flags(parser: argparse.ArgumentParser) -> None:
                         help=f"model name: {', '.join(list(VIT_NAMED) + list(STD_VIT_NAMED) + list(T2T_NAMED))}")
     parser.add_argument("--prune_encoding", default=None, type=str,
                         help="ViT_Pruned encoding (all_head{N}_ffn{F} / layerwise_h{N}-d{F}_...)")
+    parser.add_argument("--token_keep", default=None, type=str,
+                        help="token schedule block:keep,... (ViT models): keep that many patch "
+                             "tokens, or with a '.' that rate of them, after the block, e.g. "
+                             "3:0.7,6:0.7,9:0.7")
     parser.add_argument("--use_gpu", action="store_true", help="accepted; always the GPU")
     parser.add_argument("--num_runs", type=int, default=50)
     parser.add_argument("--warmup_runs", type=int, default=50)
@@ -225,12 +229,16 @@ def gpu_benchmark(argv: Optional[List[str]] = None) -> str:
     shape = _input_shape(args.model, args.input_shape)  # the family's fp32 layout either way
     model = build_model(args.model, args.compute_dtype, args.prune_encoding, max_batch=shape[0],
                         image_size=_image_size(args.model, shape))
+    if args.token_keep:
+        from .modeling.models.token_pruning import parse_token_keep
+        model.set_token_pruning(parse_token_keep(args.token_keep))
     u8 = args.dtype == "uint8"
     lat = latency_samples(model, uint8_shape(args.model, shape) if u8 else shape, args.num_runs,
                           args.warmup_runs, args.io_binding, graph=args.graph, uint8=u8,
                           raw_shape=args.raw_shape)
     avg, std = summarize(lat, args.top)
     name = args.model + (f"_{args.prune_encoding}" if args.prune_encoding else "")
+    name += f"_tokens{args.token_keep}" if args.token_keep else ""
     line = format_line(name, avg, std, args.precision)
     print(line, flush=True)
     return line
