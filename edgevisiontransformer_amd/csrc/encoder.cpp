@@ -197,16 +197,10 @@ int run_encoder(evt_model* m, ForwardCall& call) {
     // out-proj, FC1 and FC2 run on the B CLS rows (the CLS tail, below) and its attention on query
     // tile 0. A call that exports the last block's token map (tokens, or a tap on it) runs the
     // full-row block as well; the CLS rows it exports, and the head reads, are still the tail's.
+    // The last block's FFN statistics are those of the full-row FC1 launch (evt_ffn_stats.h).
     const bool last = block + 1 == (int)m->layers.size();
-    bool full = !last;
-    if (last && call.feat) {
-      const evt_features_args* a = call.feat;
-      full = a->tokens || (a->n_taps > 0 && a->tap_blocks[a->n_taps - 1] == block);
-    }
-    // the last block's FFN statistics are those of the full-row FC1 launch (evt_ffn_stats.h)
-    if (last && call.fstats && call.fstats->n_blocks > 0 &&
-        call.fstats->blocks[call.fstats->n_blocks - 1] == block)
-      full = true;
+    const bool full = !last || (call.feat && call.feat->tokens) || call.taps.last_is(block) ||
+                      call.fstats.last_is(block);
     if (last) m->tail_mode = full ? 3 : 1;
     {
       ProfScope ps(m, EVT_PROF_ATTENTION, s);

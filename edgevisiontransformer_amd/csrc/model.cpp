@@ -212,24 +212,23 @@ int feat_export(evt_model* m, const void* x, int64_t ldx, int64_t row_step, floa
 
 // After block `block` of a features forward, its output in ws.x: the tap, if one was asked for
 int feat_tap(evt_model* m, ForwardCall& call, int block, int64_t ldx, int rows, int D) {
-  const evt_features_args* a = call.feat;
-  if (!a || call.feat_next >= a->n_taps || a->tap_blocks[call.feat_next] != block) return EVT_OK;
-  return feat_export(m, m->ws.x, ldx, 1, a->taps[call.feat_next++], a->tap_norm != 0, rows, D,
-                     call.s);
+  float* out = call.taps.take(block);
+  if (!out) return EVT_OK;
+  return feat_export(m, m->ws.x, ldx, 1, out, call.feat->tap_norm != 0, rows, D, call.s);
 }
 
 // Right after block `block`'s attention kernel of an evt_forward_attention call, while ws.qkv still
 // holds the block's q and k in the layout `ap` describes: the block's map, if one was asked for
 // (attn_maps.hip; counted under EVT_PROF_HEAD like the feature exports)
 int attn_map(evt_model* m, ForwardCall& call, int block, const AttnParams& ap) {
-  const evt_attn_args* a = call.attn;
-  if (!a || call.attn_next >= a->n_maps || a->blocks[call.attn_next] != block) return EVT_OK;
-  const int nq = a->queries == EVT_ATTN_ALL ? ap.N : 1;
+  float* out = call.maps.take(block);
+  if (!out) return EVT_OK;
+  const int nq = call.map_queries == EVT_ATTN_ALL ? ap.N : 1;
   ProfScope ps(m, EVT_PROF_HEAD, call.s);
   const double bh = (double)ap.B * ap.H;
   prof_work(m, 4.0 * bh * nq * (double)ap.N * ap.hd,  // the scores, twice
             bh * ((double)(nq + ap.N) * ap.hd * elem_size(m->dtype) + (double)nq * ap.N * 4.0));
-  EVT_HIP(attn_probs_launch(m->dtype, ap, nq, a->maps[call.attn_next++], call.s), "attention map");
+  EVT_HIP(attn_probs_launch(m->dtype, ap, nq, out, call.s), "attention map");
   return EVT_OK;
 }
 
@@ -242,14 +241,13 @@ static int patch_grid_w(const ModelCore& m) {
 // At the same point of an evt_forward_head_stats call: the block's four statistics per head, if they
 // were asked for (attn_maps.hip; counted under EVT_PROF_HEAD)
 int head_stats(evt_model* m, ForwardCall& call, int block, const AttnParams& ap) {
-  const evt_head_stats_args* a = call.hstats;
-  if (!a || call.hstats_next >= a->n_blocks || a->blocks[call.hstats_next] != block) return EVT_OK;
+  float* out = call.hstats.take(block);
+  if (!out) return EVT_OK;
   ProfScope ps(m, EVT_PROF_HEAD, call.s);
   const double bh = (double)ap.B * ap.H;
   prof_work(m, 4.0 * bh * ap.N * (double)ap.N * ap.hd,  // the scores, twice
             bh * (2.0 * ap.N * ap.hd * elem_size(m->dtype) + 4.0 * EVT_HEAD_STATS));
-  EVT_HIP(head_stats_launch(m->dtype, ap, 1, patch_grid_w(*m), a->stats[call.hstats_next++], call.s),
-          "head statistics");
+  EVT_HIP(head_stats_launch(m->dtype, ap, 1, patch_grid_w(*m), out, call.s), "head statistics");
   return EVT_OK;
 }
 
@@ -257,13 +255,13 @@ int head_stats(evt_model* m, ForwardCall& call, int block, const AttnParams& ap)
 // `block`'s hidden rows: the block's four statistics per neuron, if they were asked for
 // (ffn_stats.hip; counted under EVT_PROF_HEAD)
 int ffn_stats(evt_model* m, ForwardCall& call, int block, const Layer& L, int rows) {
-  const evt_ffn_stats_args* a = call.fstats;
-  if (!a || call.fstats_next >= a->n_blocks || a->blocks[call.fstats_next] != block) return EVT_OK;
+  float* out = call.fstats.take(block);
+  if (!out) return EVT_OK;
   ProfScope ps(m, EVT_PROF_HEAD, call.s);
   prof_work(m, 5.0 * rows * (double)L.ffn,  // |a|, three adds (one fused with a^2) and a max
             (double)rows * L.ffn * elem_size(m->dtype) + 4.0 * call.B * L.ffn * EVT_FFN_STATS);
-  EVT_HIP(ffn_stats_launch(m->dtype, m->ws.hbuf, L.ffn_st, call.B, rows / call.B, L.ffn,
-                           a->stats[call.fstats_next++], call.s),
+  EVT_HIP(ffn_stats_launch(m->dtype, m->ws.hbuf, L.ffn_st, call.B, rows / call.B, L.ffn, out,
+                           call.s),
           "ffn statistics");
   return EVT_OK;
 }
@@ -299,19 +297,14 @@ int rollout_step(evt_model* m, ForwardCall& call, int block, const AttnParams& a
 
 // The Swin counterpart (evt_forward_window_attention): while ws.qkv holds block `block`'s LN1-folded
 // QKV rows that `ap` describes, the block's window map, if it is the next one asked for
-bool window_attn_wanted(const ForwardCall& call, int block) {
-  const evt_attn_args* a = call.attn;
-  return a && call.attn_next < a->n_maps && a->blocks[call.attn_next] == block;
-}
-
 int window_attn_map(evt_model* m, ForwardCall& call, int block, int w, const SwinAttnParams& ap) {
-  if (!window_attn_wanted(call, block)) return EVT_OK;
+  float* out = call.maps.take(block);
+  if (!out) return EVT_OK;
   ProfScope ps(m, EVT_PROF_HEAD, call.s);
   const double n = (double)w * w, wh = (double)ap.B * ap.nwx * ap.nwx * ap.H;
   prof_work(m, 2.0 * wh * n * n * 32,  // the scores
             wh * (2.0 * n * 32 * elem_size(m->dtype) + n * n * 4.0));
-  EVT_HIP(window_probs_launch(m->dtype, w, ap, call.attn->maps[call.attn_next++], call.s),
-          "window attention map");
+  EVT_HIP(window_probs_launch(m->dtype, w, ap, out, call.s), "window attention map");
   return EVT_OK;
 }
 
@@ -639,9 +632,54 @@ int evt_tap_shape(const evt_model* m, int block, int* tokens, int* width) {
   return EVT_OK;
 }
 
+// One per-block output list of a public args struct with the nouns of its messages: the count
+// field, the two arrays, a block, the block list, a pointer, and what must be aligned
+struct BlockList {
+  int n;
+  const int32_t* blocks;
+  float* const* out;
+  const char *count, *arrays, *block, *list, *pointer, *aligned;
+  BlockCursor cursor() const { return BlockCursor{blocks, out, n}; }
+};
+
+static int check_count(const BlockList& l) {
+  if (l.n < 0 || l.n > 64) return fail(EVT_EINVAL, std::string(l.count) + " must be in [0, 64]");
+  return EVT_OK;
+}
+
+// The entries of a list whose count is in range, on a model of nb blocks: the arrays, `refused`
+// (why this model takes no such list, or null), then entry by entry the block in [0, nb) and above
+// the one before, the pointer non-null and 16-byte aligned. With `bits` the pointers are or-ed
+// into it instead, for the caller's one alignment check after the list (the feature outputs).
+static int check_blocks(const BlockList& l, int nb, const char* refused, uintptr_t* bits) {
+  if (l.n == 0) return EVT_OK;
+  if (!l.blocks || !l.out)
+    return fail(EVT_EINVAL, std::string(l.count) + " > 0 needs the " + l.arrays + " arrays");
+  if (refused) return fail(EVT_EINVAL, refused);
+  for (int i = 0; i < l.n; ++i) {
+    if (l.blocks[i] < 0 || l.blocks[i] >= nb)
+      return fail(EVT_EINVAL, std::string(l.block) + " " + std::to_string(l.blocks[i]) +
+                                  " is outside [0, " + std::to_string(nb) + ")");
+    if (i > 0 && l.blocks[i] <= l.blocks[i - 1])
+      return fail(EVT_EINVAL, std::string(l.list) + " must be strictly increasing");
+    if (!l.out[i])
+      return fail(EVT_EINVAL, std::string(l.pointer) + " " + std::to_string(i) + " is NULL");
+    if (bits) *bits |= (uintptr_t)l.out[i];
+    else if ((uintptr_t)l.out[i] & 15)
+      return fail(EVT_EINVAL, std::string(l.aligned) + " must be 16-byte aligned");
+  }
+  return EVT_OK;
+}
+
+static BlockList tap_list(const evt_features_args* a) {
+  return {a->n_taps, a->tap_blocks, a->taps, "n_taps", "tap_blocks and taps", "tap block",
+          "tap_blocks", "tap pointer", "feature outputs"};
+}
+
 // What evt_forward_features checks of (model, outputs, batch); evt_forward_image shares it
 static int validate_features(const evt_model* m, const evt_features_args* a, int B) {
-  if (a->n_taps < 0 || a->n_taps > 64) return fail(EVT_EINVAL, "n_taps must be in [0, 64]");
+  const BlockList taps = tap_list(a);
+  EVT_RC(check_count(taps));
   if (!a->logits && !a->pooled && !a->tokens && a->n_taps == 0)
     return fail(EVT_EINVAL, "no output requested: logits, pooled and tokens are NULL, n_taps is 0");
   EVT_RC(check_batch(m, B));  // (here, ahead of forward's own: the order the checks fire in)
@@ -652,23 +690,11 @@ static int validate_features(const evt_model* m, const evt_features_args* a, int
     return fail(EVT_EINVAL, m->family == FAM_SWIN
                                 ? "tap_norm: Swin stage widths differ from the final LayerNorm's"
                                 : "tap_norm: a REFERENCE ViT has no final LayerNorm");
-  uintptr_t align = (uintptr_t)a->pooled | (uintptr_t)a->tokens;  // 16-B stores (features.hip)
-  if (a->n_taps > 0) {
-    if (!a->tap_blocks || !a->taps)
-      return fail(EVT_EINVAL, "n_taps > 0 needs the tap_blocks and taps arrays");
-    if (m->mx8) return fail(EVT_EINVAL, "taps are not available on an EVT_DTYPE_MX8 model");
-    const int nb = model_blocks(m);
-    for (int i = 0; i < a->n_taps; ++i) {
-      if (a->tap_blocks[i] < 0 || a->tap_blocks[i] >= nb)
-        return fail(EVT_EINVAL, "tap block " + std::to_string(a->tap_blocks[i]) +
-                                    " is outside [0, " + std::to_string(nb) + ")");
-      if (i > 0 && a->tap_blocks[i] <= a->tap_blocks[i - 1])
-        return fail(EVT_EINVAL, "tap_blocks must be strictly increasing");
-      if (!a->taps[i]) return fail(EVT_EINVAL, "tap pointer " + std::to_string(i) + " is NULL");
-      align |= (uintptr_t)a->taps[i];
-    }
-  }
-  if (align & 15) return fail(EVT_EINVAL, "feature outputs must be 16-byte aligned");
+  // one alignment check of every output, after the tap list (16-B stores, features.hip)
+  uintptr_t align = (uintptr_t)a->pooled | (uintptr_t)a->tokens;
+  EVT_RC(check_blocks(taps, model_blocks(m),
+                      m->mx8 ? "taps are not available on an EVT_DTYPE_MX8 model" : nullptr, &align));
+  if (align & 15) return fail(EVT_EINVAL, std::string(taps.aligned) + " must be 16-byte aligned");
   return EVT_OK;
 }
 
@@ -677,7 +703,8 @@ int evt_forward_features(evt_model* m, const float* img, int B, const evt_featur
   if (!m || !img || !a) return fail(EVT_EINVAL, "model, img and args must be non-null");
   EVT_RC(validate_features(m, a, B));
   ForwardCall call;
-  call.img = img; call.B = B; call.logits = a->logits; call.feat = a; call.s = (hipStream_t)stream;
+  call.img = img; call.B = B; call.logits = a->logits; call.s = (hipStream_t)stream;
+  call.set_feat(a);
   // one lane, on this handle's own workspace, whatever its lane count (as a profiled forward)
   return forward(m, call, false);
 }
@@ -722,17 +749,50 @@ static ForwardCall image_call(const evt_image_args* in, const ImgAffine& aff, in
   return call;
 }
 
+// The forward of evt_forward_image and evt_forward_classify from validated arguments. Logits alone:
+// over the handle's lanes, like evt_*_forward; anything more: a features forward, as one lane
+static int image_forward(evt_model* m, const evt_image_args* in, const ImgAffine& aff, int B,
+                         const evt_features_args* a, void* stream) {
+  const bool logits_only = a->logits && !a->pooled && !a->tokens && a->n_taps == 0;
+  ForwardCall call = image_call(in, aff, B, a->logits, stream);
+  if (!logits_only) call.set_feat(a);
+  return forward(m, call, logits_only);
+}
+
 int evt_forward_image(evt_model* m, const evt_image_args* in, int B, const evt_features_args* a,
                       void* stream) {
   ImgAffine aff{};
   if (!a) return fail(EVT_EINVAL, "image descriptor, outputs and model must be non-null");
   EVT_RC(validate_image(m, in, &aff));
   EVT_RC(validate_features(m, a, B));
-  // logits alone: over the handle's lanes, like evt_*_forward; anything more: a features forward
-  const bool logits_only = a->logits && !a->pooled && !a->tokens && a->n_taps == 0;
-  ForwardCall call = image_call(in, aff, B, a->logits, stream);
-  if (!logits_only) call.feat = a;
-  return forward(m, call, logits_only);
+  return image_forward(m, in, aff, B, a, stream);
+}
+
+// What the analysis forwards below open with, after their own null check: the image descriptor,
+// the family (`family` fails with the reason it is refused), the token schedule (refused under the
+// name `no_schedule` unless that is null), `list`'s count and "no output" (list: the call's own
+// block list, or null), then feat's outputs or, without feat, the batch. On EVT_OK *call is the
+// call, feat set; it runs as one lane on the handle's own workspace, whatever its lane count (as
+// a features forward).
+static int analysis_call(evt_model* m, const evt_image_args* in, int B,
+                         const evt_features_args* feat, void* stream,
+                         int (*family)(const evt_model*), const char* no_schedule,
+                         const BlockList* list, ForwardCall* call) {
+  ImgAffine aff{};
+  EVT_RC(validate_image(m, in, &aff));
+  EVT_RC(family(m));
+  if (no_schedule) EVT_RC(no_token_schedule(m, no_schedule));
+  if (list) {
+    EVT_RC(check_count(*list));
+    if (list->n == 0 && !feat)
+      return fail(EVT_EINVAL, std::string("no output requested: ") + list->count +
+                                  " is 0 and feat is NULL");
+  }
+  if (feat) EVT_RC(validate_features(m, feat, B));
+  else EVT_RC(check_batch(m, B));
+  *call = image_call(in, aff, B, feat ? feat->logits : nullptr, stream);
+  call->set_feat(feat);
+  return EVT_OK;
 }
 
 int evt_graph_capture_image(evt_model* m, const evt_image_args* in, int B, float* logits,
@@ -766,50 +826,39 @@ int evt_attn_map_shape(const evt_model* m, int block, int* heads, int* tokens) {
   return EVT_OK;
 }
 
-// The map list of an attention call on a model of nb blocks (after the image and family checks);
-// cls_ok: EVT_ATTN_CLS is a mode of the call (evt_forward_attention) or not (the window maps)
-static int validate_attn(const evt_model* m, int B, const evt_features_args* feat,
-                         const evt_attn_args* a, int nb, bool cls_ok) {
-  if (a->n_maps < 0 || a->n_maps > 64) return fail(EVT_EINVAL, "n_maps must be in [0, 64]");
-  if (a->n_maps == 0 && !feat)
-    return fail(EVT_EINVAL, "no output requested: n_maps is 0 and feat is NULL");
-  if (feat) EVT_RC(validate_features(m, feat, B));
-  else EVT_RC(check_batch(m, B));
+// An attention call (evt_forward_attention, or the window maps) on a model of nb blocks, from the
+// null check on. cls_ok: EVT_ATTN_CLS is a mode of the call (evt_forward_attention) or not.
+static int attention_forward(evt_model* m, const evt_image_args* in, int B,
+                             const evt_features_args* feat, const evt_attn_args* a, void* stream,
+                             int (*family)(const evt_model*), const char* no_schedule, bool cls_ok) {
+  const BlockList maps = {a->n_maps, a->blocks, a->maps, "n_maps", "blocks and maps", "map block",
+                          "map blocks", "map pointer", "attention maps"};
+  ForwardCall call;
+  EVT_RC(analysis_call(m, in, B, feat, stream, family, no_schedule, &maps, &call));
   if (!cls_ok && a->queries != EVT_ATTN_ALL)
     return fail(EVT_EINVAL, "window attention maps: queries must be EVT_ATTN_ALL");
   if (a->queries != EVT_ATTN_CLS && a->queries != EVT_ATTN_ALL)
     return fail(EVT_EINVAL, "queries must be EVT_ATTN_CLS or EVT_ATTN_ALL");
-  if (a->n_maps > 0) {
-    if (!a->blocks || !a->maps) return fail(EVT_EINVAL, "n_maps > 0 needs the blocks and maps arrays");
-    for (int i = 0; i < a->n_maps; ++i) {
-      if (a->blocks[i] < 0 || a->blocks[i] >= nb)
-        return fail(EVT_EINVAL, "map block " + std::to_string(a->blocks[i]) + " is outside [0, " +
-                                    std::to_string(nb) + ")");
-      if (i > 0 && a->blocks[i] <= a->blocks[i - 1])
-        return fail(EVT_EINVAL, "map blocks must be strictly increasing");
-      if (!a->maps[i]) return fail(EVT_EINVAL, "map pointer " + std::to_string(i) + " is NULL");
-      if ((uintptr_t)a->maps[i] & 15) return fail(EVT_EINVAL, "attention maps must be 16-byte aligned");
-    }
-  }
-  return EVT_OK;
+  EVT_RC(check_blocks(maps, model_blocks(m), nullptr, nullptr));
+  call.maps = maps.cursor();
+  call.map_queries = a->queries;
+  return forward(m, call, false);
 }
 
 int evt_forward_attention(evt_model* m, const evt_image_args* in, int B,
                           const evt_features_args* feat, const evt_attn_args* a, void* stream) {
-  ImgAffine aff{};
   if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and attn must be non-null");
-  EVT_RC(validate_image(m, in, &aff));
-  EVT_RC(attn_family(m));
-  EVT_RC(no_token_schedule(m, "evt_forward_attention"));
-  EVT_RC(validate_attn(m, B, feat, a, (int)m->layers.size(), true));
-  ForwardCall call = image_call(in, aff, B, feat ? feat->logits : nullptr, stream);
-  call.feat = feat;
-  call.attn = a;
-  // one lane, on this handle's own workspace, whatever its lane count (as a features forward)
-  return forward(m, call, false);
+  return attention_forward(m, in, B, feat, a, stream, attn_family, "evt_forward_attention", true);
 }
 
 // ---- head statistics (include/evt_head_stats.h) ---------------------------------------------
+
+// Why m has no head statistics (its patch tokens are not rows of patch_grid_w columns), or null
+static const char* no_patch_grid(const evt_model* m) {
+  const int gw = patch_grid_w(*m);
+  if (gw >= 1 && (m->sh.T - 1) % gw == 0) return nullptr;
+  return "head statistics: the tokens after the CLS token are not a grid of image_size / patch rows";
+}
 
 int evt_head_stats_shape(const evt_model* m, int block, int* heads, int* tokens, int* prefix,
                          int* grid_w) {
@@ -817,10 +866,8 @@ int evt_head_stats_shape(const evt_model* m, int block, int* heads, int* tokens,
   EVT_RC(attn_family(m));
   if (block < 0 || block >= (int)m->layers.size())
     return fail(EVT_EINVAL, "block must be in [0, " + std::to_string(m->layers.size()) + ")");
+  if (const char* why = no_patch_grid(m)) return fail(EVT_EINVAL, why);
   const int gw = patch_grid_w(*m);
-  if (gw < 1 || (m->sh.T - 1) % gw)
-    return fail(EVT_EINVAL, "head statistics: the tokens after the CLS token are not a grid of "
-                            "image_size / patch rows");
   *heads = m->layers[block].heads;
   *tokens = m->sh.T;
   *prefix = 1;
@@ -831,38 +878,15 @@ int evt_head_stats_shape(const evt_model* m, int block, int* heads, int* tokens,
 int evt_forward_head_stats(evt_model* m, const evt_image_args* in, int B,
                            const evt_features_args* feat, const evt_head_stats_args* a,
                            void* stream) {
-  ImgAffine aff{};
   if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and hs must be non-null");
-  EVT_RC(validate_image(m, in, &aff));
-  EVT_RC(attn_family(m));
-  EVT_RC(no_token_schedule(m, "evt_forward_head_stats"));
-  if (a->n_blocks < 0 || a->n_blocks > 64) return fail(EVT_EINVAL, "n_blocks must be in [0, 64]");
-  if (a->n_blocks == 0 && !feat)
-    return fail(EVT_EINVAL, "no output requested: n_blocks is 0 and feat is NULL");
-  if (feat) EVT_RC(validate_features(m, feat, B));
-  else EVT_RC(check_batch(m, B));
-  if (a->n_blocks > 0) {
-    if (!a->blocks || !a->stats)
-      return fail(EVT_EINVAL, "n_blocks > 0 needs the blocks and stats arrays");
-    const int nb = (int)m->layers.size(), gw = patch_grid_w(*m);
-    if (gw < 1 || (m->sh.T - 1) % gw)
-      return fail(EVT_EINVAL, "head statistics: the tokens after the CLS token are not a grid of "
-                              "image_size / patch rows");
-    for (int i = 0; i < a->n_blocks; ++i) {
-      if (a->blocks[i] < 0 || a->blocks[i] >= nb)
-        return fail(EVT_EINVAL, "head statistics block " + std::to_string(a->blocks[i]) +
-                                    " is outside [0, " + std::to_string(nb) + ")");
-      if (i > 0 && a->blocks[i] <= a->blocks[i - 1])
-        return fail(EVT_EINVAL, "head statistics blocks must be strictly increasing");
-      if (!a->stats[i]) return fail(EVT_EINVAL, "stats pointer " + std::to_string(i) + " is NULL");
-      if ((uintptr_t)a->stats[i] & 15)
-        return fail(EVT_EINVAL, "head statistics must be 16-byte aligned");
-    }
-  }
-  ForwardCall call = image_call(in, aff, B, feat ? feat->logits : nullptr, stream);
-  call.feat = feat;
-  call.hstats = a;
-  // one lane, on this handle's own workspace, whatever its lane count (as evt_forward_attention)
+  const BlockList stats = {a->n_blocks, a->blocks, a->stats, "n_blocks", "blocks and stats",
+                           "head statistics block", "head statistics blocks", "stats pointer",
+                           "head statistics"};
+  ForwardCall call;
+  EVT_RC(analysis_call(m, in, B, feat, stream, attn_family, "evt_forward_head_stats", &stats,
+                       &call));
+  EVT_RC(check_blocks(stats, model_blocks(m), no_patch_grid(m), nullptr));
+  call.hstats = stats.cursor();
   return forward(m, call, false);
 }
 
@@ -892,35 +916,15 @@ int evt_ffn_stats_shape(const evt_model* m, int block, int* neurons, int* tokens
 int evt_forward_ffn_stats(evt_model* m, const evt_image_args* in, int B,
                           const evt_features_args* feat, const evt_ffn_stats_args* a,
                           void* stream) {
-  ImgAffine aff{};
   if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and fs must be non-null");
-  EVT_RC(validate_image(m, in, &aff));
-  EVT_RC(ffn_stats_family(m));
-  EVT_RC(no_token_schedule(m, "evt_forward_ffn_stats"));
-  if (a->n_blocks < 0 || a->n_blocks > 64) return fail(EVT_EINVAL, "n_blocks must be in [0, 64]");
-  if (a->n_blocks == 0 && !feat)
-    return fail(EVT_EINVAL, "no output requested: n_blocks is 0 and feat is NULL");
-  if (feat) EVT_RC(validate_features(m, feat, B));
-  else EVT_RC(check_batch(m, B));
-  if (a->n_blocks > 0) {
-    if (!a->blocks || !a->stats)
-      return fail(EVT_EINVAL, "n_blocks > 0 needs the blocks and stats arrays");
-    const int nb = (int)m->layers.size();
-    for (int i = 0; i < a->n_blocks; ++i) {
-      if (a->blocks[i] < 0 || a->blocks[i] >= nb)
-        return fail(EVT_EINVAL, "FFN statistics block " + std::to_string(a->blocks[i]) +
-                                    " is outside [0, " + std::to_string(nb) + ")");
-      if (i > 0 && a->blocks[i] <= a->blocks[i - 1])
-        return fail(EVT_EINVAL, "FFN statistics blocks must be strictly increasing");
-      if (!a->stats[i]) return fail(EVT_EINVAL, "stats pointer " + std::to_string(i) + " is NULL");
-      if ((uintptr_t)a->stats[i] & 15)
-        return fail(EVT_EINVAL, "FFN statistics must be 16-byte aligned");
-    }
-  }
-  ForwardCall call = image_call(in, aff, B, feat ? feat->logits : nullptr, stream);
-  call.feat = feat;
-  call.fstats = a;
-  // one lane, on this handle's own workspace, whatever its lane count (as evt_forward_attention)
+  const BlockList stats = {a->n_blocks, a->blocks, a->stats, "n_blocks", "blocks and stats",
+                           "FFN statistics block", "FFN statistics blocks", "stats pointer",
+                           "FFN statistics"};
+  ForwardCall call;
+  EVT_RC(analysis_call(m, in, B, feat, stream, ffn_stats_family, "evt_forward_ffn_stats", &stats,
+                       &call));
+  EVT_RC(check_blocks(stats, model_blocks(m), nullptr, nullptr));
+  call.fstats = stats.cursor();
   return forward(m, call, false);
 }
 
@@ -954,13 +958,10 @@ int evt_rollout_scratch_bytes(const evt_model* m, int B, int mode, size_t* bytes
 
 int evt_forward_rollout(evt_model* m, const evt_image_args* in, int B,
                         const evt_features_args* feat, const evt_rollout_args* a, void* stream) {
-  ImgAffine aff{};
   if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and ro must be non-null");
-  EVT_RC(validate_image(m, in, &aff));
-  EVT_RC(rollout_family(m));
-  EVT_RC(no_token_schedule(m, "evt_forward_rollout"));
-  if (feat) EVT_RC(validate_features(m, feat, B));
-  else EVT_RC(check_batch(m, B));
+  ForwardCall call;
+  EVT_RC(analysis_call(m, in, B, feat, stream, rollout_family, "evt_forward_rollout", nullptr,
+                       &call));
   const int depth = (int)m->layers.size();
   if (a->start < 0 || a->start >= depth)
     return fail(EVT_EINVAL, "rollout start must be in [0, " + std::to_string(depth) + ")");
@@ -973,10 +974,7 @@ int evt_forward_rollout(evt_model* m, const evt_image_args* in, int B,
   if (a->scratch_bytes < need)
     return fail(EVT_EINVAL, "rollout scratch_bytes is " + std::to_string(a->scratch_bytes) +
                                 ", this call needs " + std::to_string(need));
-  ForwardCall call = image_call(in, aff, B, feat ? feat->logits : nullptr, stream);
-  call.feat = feat;
   call.rollout = a;
-  // one lane, on this handle's own workspace, whatever its lane count (as evt_forward_attention)
   return forward(m, call, false);
 }
 
@@ -1047,18 +1045,23 @@ int evt_model_tokens_at(const evt_model* m, int block, int* tokens) {
   return EVT_OK;
 }
 
-int evt_forward_token_pruning(evt_model* m, const evt_image_args* in, int B,
-                              const evt_features_args* feat, const evt_token_pruning_args* tp,
-                              void* stream) {
-  ImgAffine aff{};
-  if (!m || !in || !feat)
-    return fail(EVT_EINVAL, "model, image descriptor and feat must be non-null");
-  EVT_RC(validate_image(m, in, &aff));
+// evt_forward_token_pruning: a family that has token schedules, and a schedule set
+static int scheduled_family(const evt_model* m) {
   EVT_RC(token_pruning_family(m));
   if (m->tp_blocks.empty())
     return fail(EVT_EINVAL, "forward_token_pruning: the model has no token schedule "
                             "(evt_model_set_token_schedule first)");
-  EVT_RC(validate_features(m, feat, B));  // tokens and taps: refused under a schedule
+  return EVT_OK;
+}
+
+int evt_forward_token_pruning(evt_model* m, const evt_image_args* in, int B,
+                              const evt_features_args* feat, const evt_token_pruning_args* tp,
+                              void* stream) {
+  if (!m || !in || !feat)
+    return fail(EVT_EINVAL, "model, image descriptor and feat must be non-null");
+  ForwardCall call;
+  // (feat's tokens and taps are refused under a schedule: validate_features)
+  EVT_RC(analysis_call(m, in, B, feat, stream, scheduled_family, nullptr, nullptr, &call));
   if (tp) {
     const int n = (int)m->tp_blocks.size();
     if (tp->n_blocks != n)
@@ -1068,10 +1071,7 @@ int evt_forward_token_pruning(evt_model* m, const evt_image_args* in, int B,
       if (((tp->scores ? (uintptr_t)tp->scores[i] : 0) | (tp->kept ? (uintptr_t)tp->kept[i] : 0)) & 3)
         return fail(EVT_EINVAL, "forward_token_pruning: scores and kept must be 4-byte aligned");
   }
-  ForwardCall call = image_call(in, aff, B, feat->logits, stream);
-  call.feat = feat;
   call.tprune = tp;
-  // one lane, on this handle's own workspace, whatever its lane count (as evt_forward_attention)
   return forward(m, call, false);
 }
 
@@ -1104,16 +1104,8 @@ int evt_window_attn_map_shape(const evt_model* m, int block, int* windows, int* 
 int evt_forward_window_attention(evt_model* m, const evt_image_args* in, int B,
                                  const evt_features_args* feat, const evt_attn_args* a,
                                  void* stream) {
-  ImgAffine aff{};
   if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and attn must be non-null");
-  EVT_RC(validate_image(m, in, &aff));
-  EVT_RC(window_attn_family(m));
-  EVT_RC(validate_attn(m, B, feat, a, model_blocks(m), false));
-  ForwardCall call = image_call(in, aff, B, feat ? feat->logits : nullptr, stream);
-  call.feat = feat;
-  call.attn = a;
-  // one lane, on this handle's own workspace, whatever its lane count (as evt_forward_attention)
-  return forward(m, call, false);
+  return attention_forward(m, in, B, feat, a, stream, window_attn_family, nullptr, false);
 }
 
 int evt_forward_classify(evt_model* m, const evt_image_args* in, int B,
@@ -1131,15 +1123,12 @@ int evt_forward_classify(evt_model* m, const evt_image_args* in, int B,
   EVT_RC(validate_features(m, feat, B));
   ClassifyParams p;
   EVT_RC(validate_classify(cls, B, m->num_classes, m->num_classes, &p));
-  // the forward of evt_forward_image: logits alone over the lanes, anything more as one lane
-  const bool logits_only = !feat->pooled && !feat->tokens && feat->n_taps == 0;
-  ForwardCall call = image_call(in, aff, B, feat->logits, stream);
-  if (!logits_only) call.feat = feat;
-  EVT_RC(forward(m, call, logits_only));
+  EVT_RC(image_forward(m, in, aff, B, feat, stream));
   // the lanes have joined `stream` (lanes_forward): the logits of every image are ordered before
-  ProfScope ps(m, EVT_PROF_HEAD, call.s);
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(m, EVT_PROF_HEAD, s);
   prof_work(m, 0.0, (double)B * m->num_classes * 4.0 * (p.k + 1 + (p.labels ? 1 : 0)));
-  EVT_HIP(classify_launch(feat->logits, m->num_classes, B, m->num_classes, p, call.s), "classify");
+  EVT_HIP(classify_launch(feat->logits, m->num_classes, B, m->num_classes, p, s), "classify");
   return EVT_OK;
 }
 

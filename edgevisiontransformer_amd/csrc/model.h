@@ -218,6 +218,19 @@ struct evt_model : evt::ModelCore {  // a handle: the core, its own workspace, i
 
 namespace evt {
 
+// One per-block output list of a call (taps, maps, head or FFN statistics: validated, strictly
+// increasing) and where the forward stands in it. The run functions visit the blocks in order, so
+// the block a hook is called for either is the list's next entry or is not in the list.
+struct BlockCursor {
+  const int32_t* blocks = nullptr;
+  float* const* out = nullptr;
+  int n = 0, next = 0;
+  bool wants(int block) const { return next < n && blocks[next] == block; }
+  // block's output pointer, moving on to the next entry, if block is the next entry; else null
+  float* take(int block) { return wants(block) ? out[next++] : nullptr; }
+  bool last_is(int block) const { return n > 0 && blocks[n - 1] == block; }
+};
+
 // The arguments of one forward. The entry points build one and the run functions read it; nothing
 // of a call is kept on the handle (hm_layers and tail_mode, which evt_model_qkv_layout and
 // evt_model_tail_mode read later, aside).
@@ -227,14 +240,18 @@ struct ForwardCall {
   ImgAffine aff{};                // its per-channel affine
   int B = 0;
   float* logits = nullptr;        // may be null in a features forward (no head then)
-  const evt_features_args* feat = nullptr;  // evt_forward_features outputs (null: plain forward)
-  int feat_next = 0;              // the next entry of feat's tap list
-  const evt_attn_args* attn = nullptr;  // evt_forward_attention maps (null: none)
-  int attn_next = 0;              // the next entry of attn's block list
-  const evt_head_stats_args* hstats = nullptr;  // evt_forward_head_stats blocks (null: none)
-  int hstats_next = 0;            // the next entry of hstats' block list
-  const evt_ffn_stats_args* fstats = nullptr;  // evt_forward_ffn_stats blocks (null: none)
-  int fstats_next = 0;            // the next entry of fstats' block list
+  // evt_forward_features outputs (null: plain forward): tokens, pooled and tap_norm are read here,
+  // the tap list through `taps` (set_feat)
+  const evt_features_args* feat = nullptr;
+  BlockCursor taps;               // feat's block taps
+  BlockCursor maps;               // evt_forward_attention / _window_attention maps, of
+  int map_queries = 0;            // EVT_ATTN_CLS or EVT_ATTN_ALL rows
+  BlockCursor hstats;             // evt_forward_head_stats blocks
+  BlockCursor fstats;             // evt_forward_ffn_stats blocks
+  void set_feat(const evt_features_args* a) {
+    feat = a;
+    if (a) taps = BlockCursor{a->tap_blocks, a->taps, a->n_taps};
+  }
   const evt_rollout_args* rollout = nullptr;  // evt_forward_rollout (null: none)
   const evt_token_pruning_args* tprune = nullptr;  // evt_forward_token_pruning exports (null: none)
   int tprune_next = 0;            // the next entry of the handle's token schedule
@@ -383,8 +400,7 @@ int rollout_step(evt_model* m, ForwardCall& call, int block, const AttnParams& a
 // no_token_schedule: EVT_EINVAL naming the schedule if m has one (`what` reads all T tokens).
 int tokens_at(const ModelCore& m, int block);
 int no_token_schedule(const evt_model* m, const char* what);
-// evt_forward_window_attention (Swin): whether the call asks for block's map next, and the export
-bool window_attn_wanted(const ForwardCall& call, int block);
+// evt_forward_window_attention (Swin): block's window map, if the call asks for it next
 int window_attn_map(evt_model* m, ForwardCall& call, int block, int w, const SwinAttnParams& ap);
 int finish_create(evt_model* m, int rc, evt_model** out);
 int check_batch(const evt_model* m, int B);

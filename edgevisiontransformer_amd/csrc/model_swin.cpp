@@ -244,7 +244,7 @@ int swin_run(evt_model* m, ForwardCall& call) {
       qc.stats_in = m->ws.sx; qc.ln_width = C;
       const SwinAttnParams ap{m->ws.qkv, 3 * C, m->ws.o, Cst, bl.bias, B, st.R, st.R / st.w, C, st.H,
                               bl.shift, scale_log2};
-      if (fuse96 && window_attn_wanted(call, block)) {
+      if (fuse96 && call.maps.wants(block)) {
         // The fused sublayer keeps q and k on chip: for a requested block only, the general
         // path's QKV GEMM into ws.qkv (ws.x / ws.sx stay as the sublayer reads them) and the map
         // of its q / k; the sublayer below runs unchanged (evt_window_attention.h)

@@ -137,10 +137,20 @@ class ModelHandle:
             self._build(b)
         return b
 
+    @staticmethod
+    def _image_args(img) -> _lib.evt_image_args:
+        """The evt_image_args (include/evt_image.h) of a device-resident batch: a `Uint8Images`'
+        own, or the fp32 tensor's data pointer."""
+        if isinstance(img, Uint8Images):
+            return img.image_args()
+        args = _lib.evt_image_args()
+        args.data, args.format = img.data_ptr(), 0  # EVT_IMG_F32
+        return args
+
     def _forward_image(self, img: Uint8Images, out) -> None:
         """evt_forward_image of a device-resident Uint8Images with the outputs `out`
         (evt_features_args); logits alone run over the handle's lanes like the fp32 forward."""
-        b, args = self._fit(img), img.image_args()
+        b, args = self._fit(img), self._image_args(img)
         _lib.check(_lib.load_library().evt_forward_image(
             self._ptr(), ctypes.byref(args), b, ctypes.byref(out), self._stream()))
 

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from ... import _lib
-from ...images import Uint8Images
+from .features import outputs_to_numpy
 from .ffn_stats import FFNStats
 
 VALUES = {"prob": _lib.CLASSIFY_PROB, "logit": _lib.CLASSIFY_LOGIT}
@@ -127,19 +127,10 @@ class Classification(FFNStats):
         b = img.shape[0]
         if logits is None:
             raise ValueError("logits is required: the caller owns the buffer the kernel reads")
-        feat = _lib.evt_features_args()
-        feat.logits = self._feature_tensor("logits", logits, (b, self.cfg.num_classes))
+        feat = self._feat_args(b, logits=logits)
         a = self._classify_args(b, self.cfg.num_classes, topk, values, indices, values_out, lse,
                                 labels, rank, counters)
-        if isinstance(img, Uint8Images):
-            args = img.image_args()
-        else:
-            args = _lib.evt_image_args()
-            args.data, args.format = img.data_ptr(), 0  # EVT_IMG_F32
-        self._fit(img)
-        _lib.check(_lib.load_library().evt_forward_classify(
-            self._ptr(), ctypes.byref(args), b, ctypes.byref(feat), ctypes.byref(a),
-            self._stream()))
+        self._analysis_forward("evt_forward_classify", img, feat, a)
 
     def classify_logits(self, logits: torch.Tensor, *, indices: torch.Tensor = None,
                         values_out: torch.Tensor = None, lse: torch.Tensor = None,
@@ -183,6 +174,4 @@ class Classification(FFNStats):
                                lse=out["lse"], labels=y, rank=out.get("rank"), topk=k, values=v)
         if logits:
             out["logits"] = lg
-        if was_numpy:  # .cpu() waits for the stream, as __call__ does
-            out = {name: t.cpu().numpy() for name, t in out.items()}
-        return out
+        return outputs_to_numpy(out) if was_numpy else out

@@ -57,6 +57,13 @@ def resolve_taps(taps: Sequence[int], num_blocks: int, *, tap_norm: bool = False
     return out
 
 
+def outputs_to_numpy(out: Dict[str, object]) -> Dict[str, object]:
+    """The host copy of a dict of device tensors and lists of them (.cpu() waits for the stream,
+    as `__call__` does)."""
+    return {k: [t.cpu().numpy() for t in v] if isinstance(v, list) else v.cpu().numpy()
+            for k, v in out.items()}
+
+
 class FeatureOutputs(ModelHandle):
     """What ViT, T2T_ViT and SwinTransformer derive from: the feature outputs on top of the handle
     plumbing (_handle.py). The model class provides `_feature_geometry()` -> (F, T, [(tokens,
@@ -87,6 +94,58 @@ class FeatureOutputs(ModelHandle):
                              f"on {self.device}")
         return t.data_ptr()
 
+    # -- what the per-block outputs share (the analysis forwards of the classes on top of this one) --
+    def _feat_shapes(self, b: int) -> Dict[str, Tuple[int, ...]]:
+        f, t, _ = self._feature_geometry()
+        return {"logits": (b, self.cfg.num_classes), "pooled": (b, f), "tokens": (b, t, f)}
+
+    def _feat_args(self, b: int, **tensors):
+        """(the evt_features_args of the fp32 device tensors `logits` [b, num_classes] / `pooled`
+        [b, F] / `tokens` [b, T, F] given, None: not asked for, checked in the order given; whether
+        any of them is set)."""
+        a, shapes = _lib.evt_features_args(), self._feat_shapes(b)
+        for name, t in tensors.items():
+            setattr(a, name, self._feature_tensor(name, t, shapes[name]))
+        return a, bool(a.logits or a.pooled or a.tokens)
+
+    def _block_list(self, blocks: Sequence[int], tensors: Sequence[torch.Tensor], shape, name: str,
+                    per: str):
+        """The block and pointer arrays of a per-block output list for the C ABI, which wants the
+        blocks rising: `tensors[i]` (of `shape(blocks[i])`, named `name[i]` in an error) is the
+        output of block `blocks[i]`, in the caller's order; ValueError(f"{name} needs one tensor per
+        {per}") on another count. The caller keeps the arrays alive until after the call."""
+        if len(tensors) != len(blocks):
+            raise ValueError(f"{name} needs one tensor per {per}")
+        order = sorted(range(len(blocks)), key=blocks.__getitem__)
+        ptrs = [self._feature_tensor(f"{name}[{i}]", tensors[i], shape(blocks[i])) for i in order]
+        n = max(1, len(blocks))  # (ctypes: no zero-length arrays to point at)
+        return (ctypes.c_int32 * n)(*[blocks[i] for i in order]), (ctypes.c_void_p * n)(*ptrs)
+
+    def _analysis_forward(self, fn: str, img, feat, args) -> None:
+        """The analysis forward `fn` (evt_forward_attention, ...) of a device-resident batch (fp32 in
+        the model's layout, or a `Uint8Images`) with the outputs `feat` = `_feat_args(...)` and the
+        entry point's own `args`."""
+        image = self._image_args(img)
+        b = self._fit(img)
+        _lib.check(getattr(_lib.load_library(), fn)(
+            self._ptr(), ctypes.byref(image), b, ctypes.byref(feat[0]) if feat[1] else None,
+            ctypes.byref(args), self._stream()))
+
+    def _block_outputs(self, img, key: str, blocks: Sequence[int], shape, into,
+                       **want: bool) -> Dict[str, object]:
+        """What the allocating wrappers share: {key: [one fp32 tensor of `shape(b, block)` per block
+        of `blocks`]} plus the "logits" / "pooled" / "tokens" asked for in `want`, filled by
+        `into(x, tensors, logits=..., ...)` on the model's device. numpy in, numpy out."""
+        x, was_numpy = self._checked_image(img)
+        b = x.shape[0]
+        new = lambda shape: torch.empty(shape, dtype=torch.float32, device=self.device)  # noqa: E731
+        out: Dict[str, object] = {key: [new(shape(b, i)) for i in blocks]}
+        shapes = self._feat_shapes(b)
+        out.update({k: new(shapes[k]) for k, wanted in want.items() if wanted})
+        with torch.cuda.device(self.device):
+            into(x, out[key], **{k: out.get(k) for k in want})
+        return outputs_to_numpy(out) if was_numpy else out
+
     def features_into(self, img: torch.Tensor, *, pooled: torch.Tensor = None,
                       tokens: torch.Tensor = None, logits: torch.Tensor = None,
                       taps: Sequence[int] = (), tap_tensors: Sequence[torch.Tensor] = (),
@@ -96,24 +155,14 @@ class FeatureOutputs(ModelHandle):
         after block `taps[i]`); no allocation, no synchronisation (evt_forward_features)."""
         blocks = resolve_taps(taps, self.num_blocks, tap_norm=tap_norm,
                               tap_norm_ok=self._TAP_NORM_OK)
-        if len(tap_tensors) != len(blocks):
-            raise ValueError("tap_tensors needs one tensor per tap")
-        b = img.shape[0]
-        f, t, geo = self._feature_geometry()
-        a = _lib.evt_features_args()
-        a.pooled = self._feature_tensor("pooled", pooled, (b, f))
-        a.tokens = self._feature_tensor("tokens", tokens, (b, t, f))
-        a.logits = self._feature_tensor("logits", logits, (b, self.num_classes))
-        order = sorted(range(len(blocks)), key=blocks.__getitem__)  # the C ABI wants them rising
-        ptrs = [self._feature_tensor(f"tap_tensors[{i}]", tap_tensors[i], (b, *geo[blocks[i]]))
-                for i in order]
-        if not (a.pooled or a.tokens or a.logits or blocks):
+        b, geo = img.shape[0], self._feature_geometry()[2]
+        keep = self._block_list(blocks, tap_tensors, lambda i: (b, *geo[i]), "tap_tensors", "tap")
+        a, any_set = self._feat_args(b, pooled=pooled, tokens=tokens, logits=logits)
+        if not (any_set or blocks):
             raise ValueError("no output requested")
-        idx = (ctypes.c_int32 * max(1, len(blocks)))(*[blocks[i] for i in order])
-        arr = (ctypes.c_void_p * max(1, len(blocks)))(*ptrs)
         a.n_taps, a.tap_norm = len(blocks), int(bool(tap_norm))
         if blocks:
-            a.tap_blocks, a.taps = idx, arr
+            a.tap_blocks, a.taps = keep
         if isinstance(img, Uint8Images):  # device-resident uint8 NHWC (include/evt_image.h)
             return self._forward_image(img, a)
         self._fit(img)
@@ -126,24 +175,15 @@ class FeatureOutputs(ModelHandle):
         the order given). numpy in, numpy out; a device tensor gives device tensors."""
         blocks = resolve_taps(taps, self.num_blocks, tap_norm=tap_norm,
                               tap_norm_ok=self._TAP_NORM_OK)
-        x, was_numpy = self._checked_image(img)
-        b = x.shape[0]
-        f, t, geo = self._feature_geometry()
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)  # noqa: E731
-        out: Dict[str, object] = {"pooled": new(b, f)}
-        if tokens:
-            out["tokens"] = new(b, t, f)
-        if logits:
-            out["logits"] = new(b, self.num_classes)
+        geo = self._feature_geometry()[2]
+        out = self._block_outputs(
+            img, "taps", blocks, lambda b, i: (b, *geo[i]),
+            lambda x, t, **kw: self.features_into(x, taps=blocks, tap_tensors=t, tap_norm=tap_norm,
+                                                  **kw),
+            pooled=True, tokens=tokens, logits=logits)
+        tapped = out.pop("taps")  # last, and only when asked for
         if blocks:
-            out["taps"] = [new(b, *geo[i]) for i in blocks]
-        with torch.cuda.device(self.device):
-            self.features_into(x, pooled=out["pooled"], tokens=out.get("tokens"),
-                               logits=out.get("logits"), taps=blocks,
-                               tap_tensors=out.get("taps", ()), tap_norm=tap_norm)
-        if was_numpy:  # .cpu() waits for the stream, as __call__ does
-            out = {k: [v.cpu().numpy() for v in val] if isinstance(val, list) else val.cpu().numpy()
-                   for k, val in out.items()}
+            out["taps"] = tapped
         return out
 
     def forward_features(self, img):

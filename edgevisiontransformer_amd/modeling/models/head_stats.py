@@ -25,14 +25,12 @@ raise ValueError, as for `attention_maps`.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from ... import _lib
-from ...images import Uint8Images
 from .features import resolve_taps
 from .window_attention_maps import WindowAttentionMaps
 
@@ -101,33 +99,17 @@ class HeadStats(WindowAttentionMaps):
         allocation, no synchronisation (evt_forward_head_stats)."""
         geo = self._attn_blocks()
         idx = resolve_taps(blocks, len(geo))
-        if len(stat_tensors) != len(idx):
-            raise ValueError("stat_tensors needs one tensor per block")
         b = img.shape[0]
-        order = sorted(range(len(idx)), key=idx.__getitem__)  # the C ABI wants them rising
-        ptrs = [self._feature_tensor(f"stat_tensors[{i}]", stat_tensors[i],
-                                     (b, geo[idx[i]][0], _lib.HEAD_STATS)) for i in order]
-        feat = _lib.evt_features_args()
-        feat.logits = self._feature_tensor("logits", logits, (b, self.num_classes))
-        feat.pooled = self._feature_tensor("pooled", pooled, (b, self.feature_dim))
-        if not (idx or feat.logits or feat.pooled):
+        keep = self._block_list(idx, stat_tensors, lambda i: (b, geo[i][0], _lib.HEAD_STATS),
+                                "stat_tensors", "block")
+        feat = self._feat_args(b, logits=logits, pooled=pooled)
+        if not (idx or feat[1]):
             raise ValueError("no output requested")
         a = _lib.evt_head_stats_args()
         a.n_blocks = len(idx)
-        keep = ((ctypes.c_int32 * max(1, len(idx)))(*[idx[i] for i in order]),
-                (ctypes.c_void_p * max(1, len(idx)))(*ptrs))
         if idx:
             a.blocks, a.stats = keep
-        if isinstance(img, Uint8Images):
-            args = img.image_args()
-        else:
-            args = _lib.evt_image_args()
-            args.data, args.format = img.data_ptr(), 0  # EVT_IMG_F32
-        self._fit(img)
-        _lib.check(_lib.load_library().evt_forward_head_stats(
-            self._ptr(), ctypes.byref(args), b,
-            ctypes.byref(feat) if (feat.logits or feat.pooled) else None, ctypes.byref(a),
-            self._stream()))
+        self._analysis_forward("evt_forward_head_stats", img, feat, a)
 
     def head_stats(self, img, blocks: Optional[Sequence[int]] = None, logits: bool = False,
                    pooled: bool = False) -> Dict[str, object]:
@@ -136,18 +118,7 @@ class HeadStats(WindowAttentionMaps):
         `Uint8Images`) gives device tensors."""
         geo = self._attn_blocks()
         idx = resolve_taps(range(len(geo)) if blocks is None else blocks, len(geo))
-        x, was_numpy = self._checked_image(img)
-        b = x.shape[0]
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)  # noqa: E731
-        out: Dict[str, object] = {"stats": [new(b, geo[i][0], _lib.HEAD_STATS) for i in idx]}
-        if logits:
-            out["logits"] = new(b, self.num_classes)
-        if pooled:
-            out["pooled"] = new(b, self.feature_dim)
-        with torch.cuda.device(self.device):
-            self.head_stats_into(x, blocks=idx, stat_tensors=out["stats"],
-                                 logits=out.get("logits"), pooled=out.get("pooled"))
-        if was_numpy:  # .cpu() waits for the stream, as __call__ does
-            out = {k: [v.cpu().numpy() for v in val] if isinstance(val, list) else val.cpu().numpy()
-                   for k, val in out.items()}
-        return out
+        return self._block_outputs(
+            img, "stats", idx, lambda b, i: (b, geo[i][0], _lib.HEAD_STATS),
+            lambda x, t, **kw: self.head_stats_into(x, blocks=idx, stat_tensors=t, **kw),
+            logits=logits, pooled=pooled)

@@ -33,7 +33,6 @@ import numpy as np
 import torch
 
 from ... import _lib
-from ...images import Uint8Images
 from .features import resolve_taps
 from .head_stats import HeadStats
 
@@ -116,22 +115,12 @@ class AttentionRollout(HeadStats):
         if out is None:
             raise ValueError("out must be a tensor")
         a.out = self._feature_tensor("out", out, (b, t, t) if mode == _lib.ROLLOUT_ALL else (b, t))
-        feat = _lib.evt_features_args()
-        feat.logits = self._feature_tensor("logits", logits, (b, self.num_classes))
-        feat.pooled = self._feature_tensor("pooled", pooled, (b, self.feature_dim))
-        if isinstance(img, Uint8Images):
-            args = img.image_args()
-        else:
-            args = _lib.evt_image_args()
-            args.data, args.format = img.data_ptr(), 0  # EVT_IMG_F32
-        self._fit(img)
+        feat = self._feat_args(b, logits=logits, pooled=pooled)
+        self._fit(img)  # the handle sizes the scratch
         with torch.cuda.device(self.device):
             scratch = self._rollout_scratch(b, mode)
         a.scratch, a.scratch_bytes = scratch.data_ptr(), scratch.numel()
-        _lib.check(_lib.load_library().evt_forward_rollout(
-            self._ptr(), ctypes.byref(args), b,
-            ctypes.byref(feat) if (feat.logits or feat.pooled) else None, ctypes.byref(a),
-            self._stream()))
+        self._analysis_forward("evt_forward_rollout", img, feat, a)
 
     def attention_rollout(self, img, queries="cls", start: int = 0, logits: bool = False,
                           pooled: bool = False) -> Dict[str, object]:
@@ -140,17 +129,10 @@ class AttentionRollout(HeadStats):
         t, depth = self.rollout_shape()
         mode = resolve_mode(queries)
         start = resolve_taps((start,), depth)[0]
-        x, was_numpy = self._checked_image(img)
-        b = x.shape[0]
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)  # noqa: E731
-        out: Dict[str, object] = {"rollout": new(b, t, t) if mode == _lib.ROLLOUT_ALL else new(b, t)}
-        if logits:
-            out["logits"] = new(b, self.num_classes)
-        if pooled:
-            out["pooled"] = new(b, self.feature_dim)
-        with torch.cuda.device(self.device):
-            self.attention_rollout_into(x, out=out["rollout"], queries=mode, start=start,
-                                        logits=out.get("logits"), pooled=out.get("pooled"))
-        if was_numpy:  # .cpu() waits for the stream, as __call__ does
-            out = {k: v.cpu().numpy() for k, v in out.items()}
+        out = self._block_outputs(  # a list of one: the rollout
+            img, "rollout", (0,), lambda b, _: (b, t, t) if mode == _lib.ROLLOUT_ALL else (b, t),
+            lambda x, r, **kw: self.attention_rollout_into(x, out=r[0], queries=mode, start=start,
+                                                           **kw),
+            logits=logits, pooled=pooled)
+        out["rollout"] = out["rollout"][0]
         return out

@@ -29,8 +29,8 @@ import numpy as np
 import torch
 
 from ... import _lib
-from ...images import Uint8Images
 from .classify import Classification
+from .features import outputs_to_numpy
 
 Keep = Union[int, float]
 
@@ -239,20 +239,10 @@ class TokenPruning(Classification):
         kp = (ctypes.c_void_p * n)(*[self._int32_tensor(f"kept[{i}]", t, (b, sched[i][3]))
                                      for i, t in enumerate(kept)] or [None] * n)
         a.scores, a.kept = sp, kp
-        feat = _lib.evt_features_args()
-        feat.logits = self._feature_tensor("logits", logits, (b, self.num_classes))
-        feat.pooled = self._feature_tensor("pooled", pooled, (b, self.feature_dim))
-        if not (feat.logits or feat.pooled):
+        feat = self._feat_args(b, logits=logits, pooled=pooled)
+        if not feat[1]:
             raise ValueError("no output requested: logits and pooled are None")
-        if isinstance(img, Uint8Images):
-            args = img.image_args()
-        else:
-            args = _lib.evt_image_args()
-            args.data, args.format = img.data_ptr(), 0  # EVT_IMG_F32
-        self._fit(img)
-        _lib.check(_lib.load_library().evt_forward_token_pruning(
-            self._ptr(), ctypes.byref(args), b, ctypes.byref(feat), ctypes.byref(a),
-            self._stream()))
+        self._analysis_forward("evt_forward_token_pruning", img, feat, a)
 
     def token_pruning_outputs(self, img, logits: bool = True, pooled: bool = False) -> Dict[str, object]:
         """{"scores": [fp32 [B, T_in] per scheduled block], "kept": [int32 [B, 1 + K] per block],
@@ -282,7 +272,4 @@ class TokenPruning(Classification):
             for k in out["kept"]:
                 index = torch.gather(index, 1, k.long())
             out["token_index"] = index.contiguous()
-        if was_numpy:  # .cpu() waits for the stream, as __call__ does
-            out = {k: [v.cpu().numpy() for v in val] if isinstance(val, list) else val.cpu().numpy()
-                   for k, val in out.items()}
-        return out
+        return outputs_to_numpy(out) if was_numpy else out

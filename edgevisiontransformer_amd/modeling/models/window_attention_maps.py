@@ -18,14 +18,12 @@ are `attention_maps`.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from ... import _lib
-from ...images import Uint8Images
 from .attention_maps import AttentionMaps
 from .features import resolve_taps
 
@@ -80,55 +78,26 @@ class WindowAttentionMaps(AttentionMaps):
         fills `map_tensors[i]` with the window map of block `blocks[i]` and the given `logits`
         [B, num_classes] / `pooled` [B, F] tensors; no allocation, no synchronisation
         (evt_forward_window_attention)."""
-        geo = self._window_geometry()
-        idx = resolve_taps(blocks, len(geo))
-        if len(map_tensors) != len(idx):
-            raise ValueError("map_tensors needs one tensor per block")
+        idx = resolve_taps(blocks, len(self._window_geometry()))
         b = img.shape[0]
-        order = sorted(range(len(idx)), key=idx.__getitem__)  # the C ABI wants them rising
-        ptrs = [self._feature_tensor(f"map_tensors[{i}]", map_tensors[i],
-                                     self._window_map_shape(b, idx[i])) for i in order]
-        feat = _lib.evt_features_args()
-        feat.logits = self._feature_tensor("logits", logits, (b, self.num_classes))
-        feat.pooled = self._feature_tensor("pooled", pooled, (b, self.feature_dim))
-        if not (idx or feat.logits or feat.pooled):
+        keep = self._block_list(idx, map_tensors, lambda i: self._window_map_shape(b, i),
+                                "map_tensors", "block")
+        feat = self._feat_args(b, logits=logits, pooled=pooled)
+        if not (idx or feat[1]):
             raise ValueError("no output requested")
         a = _lib.evt_attn_args()
         a.n_maps, a.queries = len(idx), _lib.ATTN_ALL
-        keep = ((ctypes.c_int32 * max(1, len(idx)))(*[idx[i] for i in order]),
-                (ctypes.c_void_p * max(1, len(idx)))(*ptrs))
         if idx:
             a.blocks, a.maps = keep
-        if isinstance(img, Uint8Images):
-            args = img.image_args()
-        else:
-            args = _lib.evt_image_args()
-            args.data, args.format = img.data_ptr(), 0  # EVT_IMG_F32
-        self._fit(img)
-        _lib.check(_lib.load_library().evt_forward_window_attention(
-            self._ptr(), ctypes.byref(args), b,
-            ctypes.byref(feat) if (feat.logits or feat.pooled) else None, ctypes.byref(a),
-            self._stream()))
+        self._analysis_forward("evt_forward_window_attention", img, feat, a)
 
     def window_attention_maps(self, img, *, blocks: Sequence[int] = (-1,), logits: bool = False,
                               pooled: bool = False) -> Dict[str, object]:
         """{"maps": [one [B, nW, H, N, N] per block, in the order given]} plus the requested
         "logits" / "pooled". numpy in, numpy out; a device tensor (or a device `Uint8Images`)
         gives device tensors."""
-        geo = self._window_geometry()
-        idx = resolve_taps(blocks, len(geo))
-        x, was_numpy = self._checked_image(img)
-        b = x.shape[0]
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)  # noqa: E731
-        out: Dict[str, object] = {"maps": [new(*self._window_map_shape(b, i)) for i in idx]}
-        if logits:
-            out["logits"] = new(b, self.num_classes)
-        if pooled:
-            out["pooled"] = new(b, self.feature_dim)
-        with torch.cuda.device(self.device):
-            self.window_attention_maps_into(x, blocks=idx, map_tensors=out["maps"],
-                                            logits=out.get("logits"), pooled=out.get("pooled"))
-        if was_numpy:  # .cpu() waits for the stream, as __call__ does
-            out = {k: [v.cpu().numpy() for v in val] if isinstance(val, list) else val.cpu().numpy()
-                   for k, val in out.items()}
-        return out
+        idx = resolve_taps(blocks, len(self._window_geometry()))
+        return self._block_outputs(
+            img, "maps", idx, self._window_map_shape,
+            lambda x, t, **kw: self.window_attention_maps_into(x, blocks=idx, map_tensors=t, **kw),
+            logits=logits, pooled=pooled)
