@@ -292,6 +292,17 @@ TOKEN_PRUNING_SIGNATURES = {
     "evt_token_gather": (_I, [_I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
 }
 
+# the entry points of include/evt_gates.h (evt.h includes it; bound like SIGNATURES)
+_PF = ctypes.POINTER(ctypes.c_float)
+GATES_SIGNATURES = {
+    "evt_model_set_head_gates": (_I, [_P, _I, _PF, _I, _P]),
+    "evt_model_set_ffn_gates": (_I, [_P, _I, _PF, _I, _P]),
+    "evt_model_clear_gates": (_I, [_P, _P]),
+    "evt_model_get_head_gates": (_I, [_P, _I, _PF, _I, _PI]),
+    "evt_model_get_ffn_gates": (_I, [_P, _I, _PF, _I, _PI]),
+    "evt_gate_weights": (_I, [_I, _P, _P, _P, _I, _I, _P]),
+}
+
 # the entry points of include/evt_window_attention.h (evt.h includes it; bound like SIGNATURES)
 WINDOW_ATTENTION_SIGNATURES = {
     "evt_window_attn_map_shape": (_I, [_P, _I, _PI, _PI, _PI]),
@@ -362,7 +373,8 @@ def load_library() -> ctypes.CDLL:
                                       **TAIL_SIGNATURES, **HEAD_STATS_SIGNATURES,
                                       **ROLLOUT_SIGNATURES, **FFN_STATS_SIGNATURES,
                                       **CLASSIFY_SIGNATURES, **WORKSPACE_SIGNATURES,
-                                      **PERFORMER_SIGNATURES, **TOKEN_PRUNING_SIGNATURES}.items():
+                                      **PERFORMER_SIGNATURES, **TOKEN_PRUNING_SIGNATURES,
+                                      **GATES_SIGNATURES}.items():
                 if lenient and not hasattr(lib, name):
                     continue
                 fn = getattr(lib, name)

@@ -176,6 +176,13 @@ hipError_t token_gather_launch(int dtype, const void* src, void* dst, const floa
                                float* sdst, int slots, const int* kept, int B, int T, int K1,
                                int D, hipStream_t s);
 
+// Structured gates (gates.hip; include/evt_gates.h): w[n][k] = round_dtype(g[k] * w0[n][k]) for
+// n < rows, k < kpad of a packed weight [rows][kpad] (dtype bf16 or f32), g fp32 [kpad]; the
+// multiply in fp32, the rounding pack_weight's. kpad a positive multiple of PAD_K, w0, w and g
+// 16-byte aligned, w must not overlap w0 or g (the caller's check).
+hipError_t gate_weights_launch(int dtype, const void* w0, void* w, const float* g, int rows,
+                               int kpad, hipStream_t s);
+
 // FFN neuron statistics (ffn_stats.hip; include/evt_ffn_stats.h): out[b][j][0..3] = (mean, mean_abs,
 // mean_sq, max_abs) over the T rows of image b of column j < F of the row-major matrix h (B T rows,
 // pitch ld elements, dtype bf16 or f32), fp32 contiguous [B][F][4]. One launch, no scratch; h and

@@ -1075,6 +1075,143 @@ int evt_forward_token_pruning(evt_model* m, const evt_image_args* in, int B,
   return forward(m, call, false);
 }
 
+// ---- structured gates (include/evt_gates.h) --------------------------------------------------
+
+static int gates_family(const evt_model* m) {
+  if (m->is_lane) return fail(EVT_EINVAL, "structured gates: the model is a lane of another model");
+  if (m->family == FAM_SWIN)
+    return fail(EVT_EINVAL, "structured gates: Swin is not supported (ViT handles only)");
+  if (m->family == FAM_T2T)
+    return fail(EVT_EINVAL, "structured gates: T2T-ViT is not supported (ViT handles only)");
+  if (m->mx8)
+    return fail(EVT_EINVAL, "structured gates are not available on an EVT_DTYPE_MX8 model: its "
+                            "block-scaled weights would need requantising");
+  return EVT_OK;
+}
+
+// block (negative: from the last) -> its index, or EVT_EINVAL
+static int gate_block(const evt_model* m, int block, int* index) {
+  const int depth = (int)m->layers.size();
+  const int i = block < 0 ? block + depth : block;
+  if (i < 0 || i >= depth)
+    return fail(EVT_EINVAL, "structured gates: block " + std::to_string(block) +
+                                " is outside the model's " + std::to_string(depth) + " blocks");
+  *index = i;
+  return EVT_OK;
+}
+
+// The calls that enqueue on s refuse a capturing stream: they allocate at a role's first gate, and
+// a graph has no use for a gate set inside it (its replays read the weights the set wrote)
+static int not_capturing(hipStream_t s, const char* what) {
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  EVT_HIP(hipStreamIsCapturing(s, &st), "stream capture status");
+  if (st != hipStreamCaptureStatusNone)
+    return fail(EVT_EINVAL, std::string(what) + ": the stream is capturing (set the gates outside "
+                            "the capture; a captured graph needs no recapture)");
+  return EVT_OK;
+}
+
+// The n gates of one role of block `block`: out-projection (per head, each over its hd K columns)
+// or FC2 (per neuron). Everything is checked before anything is allocated, enqueued or recorded.
+static int set_gates(evt_model* m, int block, bool ffn, const float* gates, int n, void* stream) {
+  const char* what = ffn ? "set_ffn_gates" : "set_head_gates";
+  if (!m || !gates) return fail(EVT_EINVAL, std::string(what) + ": model and gates must be non-null");
+  EVT_RC(gates_family(m));
+  int i = 0;
+  EVT_RC(gate_block(m, block, &i));
+  const Layer& L = m->layers[i];
+  const DenseW& dw = ffn ? L.fc2 : L.out;
+  const int count = ffn ? L.ffn : L.heads, per = ffn ? 1 : L.hd;
+  if (n != count)
+    return fail(EVT_EINVAL, std::string(what) + ": n is " + std::to_string(n) + ", block " +
+                                std::to_string(i) + " has " + std::to_string(count) +
+                                (ffn ? " FFN neurons" : " heads"));
+  bool identity = true;
+  for (int j = 0; j < n; ++j) {
+    if (!std::isfinite(gates[j]))
+      return fail(EVT_EINVAL, std::string(what) + ": gate " + std::to_string(j) +
+                                  " is not finite (NaN or infinite)");
+    identity = identity && gates[j] == 1.0f;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  EVT_RC(not_capturing(s, what));
+  if (m->gates.empty()) m->gates.resize(m->layers.size());
+  GateRole& r = ffn ? m->gates[i].ffn : m->gates[i].head;
+  if (identity && !r.w0) {  // the packed weight is still the pristine one
+    r.rec.assign(gates, gates + n);
+    return EVT_OK;
+  }
+  if (!r.w0) {
+    const size_t bytes = (size_t)dw.npad * dw.kpad * elem_size(m->dtype);
+    void* w0 = nullptr;
+    float* g = nullptr;
+    EVT_RC(dev_alloc(m, &w0, bytes));
+    EVT_RC(dev_alloc(m, (void**)&g, (size_t)dw.kpad * sizeof(float)));
+    EVT_HIP(hipMemcpyAsync(w0, dw.w, bytes, hipMemcpyDeviceToDevice, s), "pristine weight copy");
+    r.w0 = w0;
+    r.g = g;
+  }
+  std::vector<float> k((size_t)dw.kpad, 1.0f);  // 1 in the K padding: its zero columns stay +0
+  for (int j = 0; j < n; ++j) std::fill_n(k.begin() + (size_t)j * per, per, gates[j]);
+  // pageable source: staged before the call returns, so k (and the caller's array) may go
+  EVT_HIP(hipMemcpyAsync(r.g, k.data(), k.size() * sizeof(float), hipMemcpyHostToDevice, s),
+          "gate upload");
+  // the layer's N rows: the padding rows [N, npad) keep the +0 make_dense gave them
+  EVT_HIP(gate_weights_launch(m->dtype, r.w0, dw.w, r.g, dw.N, dw.kpad, s), "gate_weights");
+  r.rec.assign(gates, gates + n);
+  return EVT_OK;
+}
+
+static int get_gates(const evt_model* m, int block, bool ffn, float* gates, int cap, int* n) {
+  if (!m || !n || cap < 0)
+    return fail(EVT_EINVAL, "get gates: a NULL model or n, or cap < 0");
+  EVT_RC(gates_family(m));
+  int i = 0;
+  EVT_RC(gate_block(m, block, &i));
+  *n = ffn ? m->layers[i].ffn : m->layers[i].heads;
+  const GateRole* r = m->gates.empty() ? nullptr : ffn ? &m->gates[i].ffn : &m->gates[i].head;
+  for (int j = 0; gates && j < *n && j < cap; ++j)
+    gates[j] = r && !r->rec.empty() ? r->rec[j] : 1.0f;
+  return EVT_OK;
+}
+
+int evt_model_set_head_gates(evt_model* m, int block, const float* gates, int n, void* stream) {
+  return set_gates(m, block, false, gates, n, stream);
+}
+
+int evt_model_set_ffn_gates(evt_model* m, int block, const float* gates, int n, void* stream) {
+  return set_gates(m, block, true, gates, n, stream);
+}
+
+int evt_model_clear_gates(evt_model* m, void* stream) {
+  if (!m) return fail(EVT_EINVAL, "clear_gates: model is NULL");
+  EVT_RC(gates_family(m));
+  hipStream_t s = (hipStream_t)stream;
+  EVT_RC(not_capturing(s, "clear_gates"));
+  for (size_t i = 0; i < m->gates.size(); ++i) {
+    const Layer& L = m->layers[i];
+    for (int ffn = 0; ffn < 2; ++ffn) {
+      GateRole& r = ffn ? m->gates[i].ffn : m->gates[i].head;
+      const DenseW& dw = ffn ? L.fc2 : L.out;
+      // a role without a pristine copy was never written; all-ones gates wrote the pristine bits
+      if (r.w0 && std::any_of(r.rec.begin(), r.rec.end(), [](float g) { return g != 1.0f; }))
+        EVT_HIP(hipMemcpyAsync(dw.w, r.w0, (size_t)dw.npad * dw.kpad * elem_size(m->dtype),
+                               hipMemcpyDeviceToDevice, s),
+                "restore pristine weight");
+      r.rec.clear();
+    }
+  }
+  return EVT_OK;
+}
+
+int evt_model_get_head_gates(const evt_model* m, int block, float* gates, int cap, int* n) {
+  return get_gates(m, block, false, gates, cap, n);
+}
+
+int evt_model_get_ffn_gates(const evt_model* m, int block, float* gates, int cap, int* n) {
+  return get_gates(m, block, true, gates, cap, n);
+}
+
 // ---- Swin window attention maps (include/evt_window_attention.h) ----------------------------
 
 static int window_attn_family(const evt_model* m) {

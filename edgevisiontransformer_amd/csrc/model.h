@@ -185,6 +185,18 @@ struct Workspace {
 };
 static_assert(std::is_trivially_copyable<Workspace>::value, "raw pointers and integers only");
 
+// Structured gates (include/evt_gates.h) of one packed weight, a block's out-projection (head
+// gates) or FC2 (FFN gates): the host-side record and, from the first non-identity gate on, the
+// pristine copy of the weight and the device gate vector (both owned through evt_model::allocs)
+struct GateRole {
+  std::vector<float> rec;  // one gate per head / neuron; empty: never set, all 1
+  void* w0 = nullptr;      // [npad][kpad] model dtype: DenseW::w as make_dense packed it
+  float* g = nullptr;      // [kpad] fp32: rec expanded over the K columns, 1 in the padding
+};
+struct LayerGates {
+  GateRole head, ffn;
+};
+
 }  // namespace evt
 
 struct evt_model : evt::ModelCore {  // a handle: the core, its own workspace, its own runtime state
@@ -214,6 +226,9 @@ struct evt_model : evt::ModelCore {  // a handle: the core, its own workspace, i
   // lane fills the CUs a balanced grid leaves idle; measured +2.9 % on T2T-ViT-14 bs256, while
   // Swin lanes measured -1.3 % without the balancing: DESIGN.md, batch lanes)
   int no_balance = 0;
+  // evt_model_set_head_gates / _ffn_gates: per encoder block, sized at the first set. The parent
+  // handle's alone: the lanes read the parent's weight allocations, which the gate kernel rewrites
+  std::vector<evt::LayerGates> gates;
 };
 
 namespace evt {

@@ -569,6 +569,29 @@ int evt_token_gather(int dtype, const void* src, void* dst, const float* stats_s
   return EVT_OK;
 }
 
+// include/evt_gates.h: the gate kernel on caller buffers
+int evt_gate_weights(int dtype, const void* w0, void* w, const float* gates, int npad, int kpad,
+                     void* stream) {
+  if (dtype != EVT_DTYPE_F32 && dtype != EVT_DTYPE_BF16)
+    return fail(EVT_EINVAL, "gate_weights: dtype must be EVT_DTYPE_F32 or EVT_DTYPE_BF16");
+  if (!w0 || !w || !gates) return fail(EVT_EINVAL, "gate_weights: w0, w and gates must be non-null");
+  if (npad < 1 || kpad < PAD_K || kpad % PAD_K)
+    return fail(EVT_EINVAL, "gate_weights: needs npad >= 1 and kpad a positive multiple of 64");
+  if (((uintptr_t)w0 | (uintptr_t)w | (uintptr_t)gates) & 15)
+    return fail(EVT_EINVAL, "gate_weights: w0, w and gates must be 16-byte aligned");
+  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+  };
+  const size_t bytes = (size_t)npad * kpad * (dtype == DT_BF16 ? 2 : 4);
+  if (overlap(w, bytes, w0, bytes) || overlap(w, bytes, gates, (size_t)kpad * sizeof(float)))
+    return fail(EVT_EINVAL, "gate_weights: w must not overlap w0 or gates (the kernel always "
+                            "reads the pristine copy)");
+  EVT_HIP(gate_weights_launch(dtype, w0, w, gates, npad, kpad, (hipStream_t)stream),
+          "gate_weights");
+  return EVT_OK;
+}
+
 int evt_window_attention_probs(int dtype, const void* qkv, int64_t ldq, const float* rpb, int B,
                                int R, int window, int C, int H, int shift, float* out,
                                void* stream) {

@@ -82,6 +82,47 @@ def _ratio(a: int, b: int) -> float:
     return a / b if b else 0.0
 
 
+def head_ablation(model, loader: Iterable, topk: int = 5, transform=None, blocks=None,
+                  log: Optional[Callable[[str], None]] = None) -> Dict[str, object]:
+    """The head-ablation sweep of the reference's `are_16_heads/heads_ablation.sh` (`--attention_
+    mask_heads layer:head` over every head) on the loaded model: {"base": `evaluate`'s result with
+    the model's current gates, "acc1": [[top-1 accuracy with head h of block l masked] per head]
+    per block, "acck": the same for top-`topk`, "blocks": the block indices of the rows}.
+    `blocks=None` sweeps every block (negative indices and any order as `head_stats`); a pruned
+    model's rows have its per-block head counts.
+
+    One head at a time is gated to 0 on top of the gates the model already has (`mask_heads`
+    semantics on that one head: modeling/models/gates.py), and the whole loader is counted by
+    `evaluate` on the device. `loader` is re-iterated once per mask and once for the base: give a
+    list (or anything that can be iterated again), not a one-shot generator; nothing is
+    materialised here. The model's gates are back as they were at the end, also on an exception.
+    `log` gets one line per mask."""
+    from .modeling.models.features import resolve_taps
+    nb = model.num_blocks
+    idx = resolve_taps(range(nb) if blocks is None else blocks, nb)
+    res: Dict[str, object] = {"base": evaluate(model, loader, topk=topk, transform=transform),
+                              "acc1": [], "acck": [], "blocks": list(idx)}
+    for l in idx:
+        mine = model.head_gates()[l]
+        row1, rowk = [], []
+        for h in range(mine.shape[0]):
+            g = mine.copy()
+            g[h] = 0.0
+            with model.gated(heads={l: g}):
+                r = evaluate(model, loader, topk=topk, transform=transform)
+            if r["seen"] != res["base"]["seen"]:
+                raise ValueError("head_ablation: the loader gave a different number of images on a "
+                                 "later pass (it must be re-iterable)")
+            row1.append(r["acc1"])
+            rowk.append(r["acck"])
+            if log is not None:
+                log(f"head_ablation block {l} head {h}: acc1 {r['acc1'] * 100:.2f}% "
+                    f"(base {res['base']['acc1'] * 100:.2f}%)")
+        res["acc1"].append(row1)
+        res["acck"].append(rowk)
+    return res
+
+
 def collect_head_stats(model, loader: Iterable, transform=None, blocks=None):
     """Dataset means of the per-head attention statistics (modeling/models/head_stats.py): one
     fp64 [H_i, 4] array per block (`blocks=None`: every block; negative indices and any order as

@@ -99,6 +99,41 @@ def importance_from_head_stats(stats: Sequence[np.ndarray], kind: str = "confide
     return np.stack(rows)
 
 
+def importance_from_head_ablation(result: Dict[str, object]) -> np.ndarray:
+    """The [layers, heads] importance table `heads_from_importance` takes, from `head_ablation`'s
+    result (evaluate.py): base top-1 accuracy minus the top-1 accuracy with that head masked, so
+    the head whose removal costs most is the most important (a head whose removal helps is
+    negative). ValueError: no rows, or rows whose head counts differ (a pruned model, or a sweep
+    of some blocks of one: a table has one width)."""
+    rows = [np.asarray(r, dtype=np.float64) for r in result["acc1"]]
+    if not rows or any(r.ndim != 1 or r.size < 1 for r in rows):
+        raise ValueError("the ablation result has no rows")
+    if len({r.size for r in rows}) != 1:
+        raise ValueError(f"head counts differ between blocks ({[r.size for r in rows]}): an "
+                         "importance table needs the same number of heads in every layer")
+    return float(result["base"]["acc1"]) - np.stack(rows)
+
+
+def gates_from_kept(kept: Sequence[Sequence[int]], n) -> Dict[int, np.ndarray]:
+    """Binary gates `{layer: float32 [n_l]}` of per-layer keep-lists (`heads_from_importance`,
+    `ffn_keep_from_importance`): 1 for the kept indices, 0 for the rest; `n` is the layers' head /
+    neuron count, one int for all or one per layer. What `set_head_gates` / `set_ffn_gates` take:
+    masking with them checks a keep-list on the loaded model before `build_pruned_vit` cuts it.
+    ValueError: an index outside [0, n_l), a count list of another length."""
+    counts = [int(n)] * len(kept) if isinstance(n, (int, np.integer)) else [int(v) for v in n]
+    if len(counts) != len(kept):
+        raise ValueError("one count per layer")
+    out = {}
+    for l, (k, c) in enumerate(zip(kept, counts)):
+        idx = np.asarray(list(k), dtype=np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= c):
+            raise ValueError(f"layer {l}: kept indices {list(k)} out of range 0..{c - 1}")
+        g = np.zeros(c, dtype=np.float32)
+        g[idx] = 1.0
+        out[l] = g
+    return out
+
+
 def heads_from_importance(importance: np.ndarray, keep_per_layer: Optional[Sequence[int]] = None,
                           keep_total: Optional[int] = None) -> List[List[int]]:
     """Kept heads per layer, most important first kept: either a per-layer count, or a global

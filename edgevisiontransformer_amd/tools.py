@@ -4,6 +4,7 @@
     python -m edgevisiontransformer_amd.tools gpu_benchmark --model deit_base --input_shape 64,3,384,384
     python -m edgevisiontransformer_amd.tools gpu_benchmark --model vit_huge_patch14_224 --input_shape 64,3,224,224
     python -m edgevisiontransformer_amd.tools gpu_benchmark --model deit_tiny --prune_encoding all_head2_ffn0.7
+    python -m edgevisiontransformer_amd.tools gpu_benchmark --model deit_base --mask_heads 3:1,3:5
     python -m edgevisiontransformer_amd.tools test_keras_latency --model t2t_vit_14 --input_shape 1,224,224,3
     python -m edgevisiontransformer_amd.tools prune_benchmark --types tiny --num_runs 20
     python -m edgevisiontransformer_amd.tools fetch_latency_std -f bench.log
@@ -185,6 +186,9 @@ def _server_flags(parser: argparse.ArgumentParser) -> None:
                         help="token schedule block:keep,... (ViT models): keep that many patch "
                              "tokens, or with a '.' that rate of them, after the block, e.g. "
                              "3:0.7,6:0.7,9:0.7")
+    parser.add_argument("--mask_heads", default=None, type=str,
+                        help="heads to mask block:head,... (ViT models; the reference's "
+                             "--attention_mask_heads layer:head, 0-based), e.g. 3:1,3:5")
     parser.add_argument("--use_gpu", action="store_true", help="accepted; always the GPU")
     parser.add_argument("--num_runs", type=int, default=50)
     parser.add_argument("--warmup_runs", type=int, default=50)
@@ -214,6 +218,9 @@ def parse_server_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     args = parser.parse_args(argv)
     if args.dtype not in INPUT_DTYPES:
         raise ValueError(f"input dtype must be one of {INPUT_DTYPES}")
+    if args.mask_heads is not None:
+        from .modeling.models.gates import parse_mask_heads
+        args.mask_heads = parse_mask_heads(args.mask_heads)  # {block: [heads]}
     if args.raw_shape is not None:
         if args.dtype != "uint8":
             raise ValueError("--raw_shape needs --dtype uint8")
@@ -232,6 +239,8 @@ def gpu_benchmark(argv: Optional[List[str]] = None) -> str:
     if args.token_keep:
         from .modeling.models.token_pruning import parse_token_keep
         model.set_token_pruning(parse_token_keep(args.token_keep))
+    if args.mask_heads:
+        model.mask_heads(args.mask_heads)
     u8 = args.dtype == "uint8"
     lat = latency_samples(model, uint8_shape(args.model, shape) if u8 else shape, args.num_runs,
                           args.warmup_runs, args.io_binding, graph=args.graph, uint8=u8,
@@ -239,6 +248,8 @@ def gpu_benchmark(argv: Optional[List[str]] = None) -> str:
     avg, std = summarize(lat, args.top)
     name = args.model + (f"_{args.prune_encoding}" if args.prune_encoding else "")
     name += f"_tokens{args.token_keep}" if args.token_keep else ""
+    if args.mask_heads:
+        name += "_mask" + ",".join(f"{b}:{h}" for b, hs in args.mask_heads.items() for h in hs)
     line = format_line(name, avg, std, args.precision)
     print(line, flush=True)
     return line
