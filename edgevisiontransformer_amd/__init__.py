@@ -13,4 +13,4 @@ __version__ = "0.4.0"
 from .images import (IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD, EvalTransform,  # noqa: E402,F401
                      Uint8Images)
 from .evaluate import (collect_ffn_stats, collect_head_stats, evaluate,  # noqa: E402,F401
-                       head_ablation)
+                       head_ablation, sublayer_ablation)

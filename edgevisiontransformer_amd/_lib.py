@@ -303,6 +303,29 @@ GATES_SIGNATURES = {
     "evt_gate_weights": (_I, [_I, _P, _P, _P, _I, _I, _P]),
 }
 
+class evt_block_stats_args(ctypes.Structure):
+    _fields_ = [("n_blocks", ctypes.c_int32), ("blocks", ctypes.POINTER(ctypes.c_int32)),
+                ("stats", ctypes.POINTER(ctypes.c_void_p))]
+
+
+# include/evt_depth.h constants: EVT_DEPTH_STATS and the index of each statistic, the sublayer
+# index of a block's statistics, and the bits of a skip mask
+DEPTH_STATS = 4
+DEPTH_COSINE, DEPTH_REL_UPDATE, DEPTH_NORM_RATIO, DEPTH_CLS_COSINE = 0, 1, 2, 3
+DEPTH_ATTN, DEPTH_FFN = 0, 1
+SKIP_ATTN, SKIP_FFN = 1, 2
+_PU8 = ctypes.POINTER(ctypes.c_uint8)
+# the entry points of include/evt_depth.h (evt.h includes it; bound like SIGNATURES)
+DEPTH_SIGNATURES = {
+    "evt_block_stats_shape": (_I, [_P, _I, _PI, _PI, _PI]),
+    "evt_forward_block_stats": (_I, [_P, ctypes.POINTER(evt_image_args), _I,
+                                     ctypes.POINTER(evt_features_args),
+                                     ctypes.POINTER(evt_block_stats_args), _P]),
+    "evt_stream_delta_stats": (_I, [_I, _P, _I64, _P, _I64, _I, _I, _I, _P, _P]),
+    "evt_model_set_skips": (_I, [_P, _PU8, _I, _P]),
+    "evt_model_get_skips": (_I, [_P, _PU8, _I, _PI]),
+}
+
 # the entry points of include/evt_window_attention.h (evt.h includes it; bound like SIGNATURES)
 WINDOW_ATTENTION_SIGNATURES = {
     "evt_window_attn_map_shape": (_I, [_P, _I, _PI, _PI, _PI]),
@@ -374,7 +397,7 @@ def load_library() -> ctypes.CDLL:
                                       **ROLLOUT_SIGNATURES, **FFN_STATS_SIGNATURES,
                                       **CLASSIFY_SIGNATURES, **WORKSPACE_SIGNATURES,
                                       **PERFORMER_SIGNATURES, **TOKEN_PRUNING_SIGNATURES,
-                                      **GATES_SIGNATURES}.items():
+                                      **GATES_SIGNATURES, **DEPTH_SIGNATURES}.items():
                 if lenient and not hasattr(lib, name):
                     continue
                 fn = getattr(lib, name)

@@ -150,6 +150,11 @@ static int token_prune(evt_model* m, ForwardCall& call, const AttnParams& ap, in
 
 // Encoder layers (transformer_encoder.py:13-18 / :26-34) on the token stream m->ws.x (+ stats sx).
 // T tokens per image: sh.T until a block of the handle's token schedule, 1 + K_l after it.
+//
+// A skipped sublayer (evt_model_set_skips, include/evt_depth.h) launches nothing: the stream and
+// its row statistics stay where they are and the x / xm and sx / sm roles swap for the rest of the
+// call, as token_prune swaps them (vit_run puts the handle's pointers back), so the next consumer
+// finds them under the name it reads. Whatever is skipped, a block leaves the stream in ws.x.
 int run_encoder(evt_model* m, ForwardCall& call) {
   const int B = call.B, D = m->D;
   int T = m->sh.T, rows = B * T;
@@ -158,80 +163,25 @@ int run_encoder(evt_model* m, ForwardCall& call) {
   m->hm_layers = 0;
   m->tail_mode = 0;
   call.tprune_next = 0;
+  // the block of the CLS tail: the last one that runs a sublayer (the last block, without skips)
+  const int last_block = m->last_running();
   int block = 0;
   for (const Layer& L : m->layers) {
-    const float scale_log2 = log2e / std::sqrt((float)L.hd);  // h_k^-0.5 (attention.py:13)
-    // qkv head-major ([B][heads][q | k | v][T][64], EPI_HM) where the QKV GEMM takes the
-    // persistent kernel (h_k = 64, bf16): an (image, head)'s q, k and v are three contiguous 25 KB
-    // runs instead of T 128-B pieces at a 3 D-element stride each; token-major otherwise
-    bool hm = false;
-    {  // LN1-folded QKV (attention.py:24)
-      ProfScope ps(m, EVT_PROF_QKV, s);
-      DenseCall c;
-      c.flags = EPI_LNIN | EPI_BIAS;
-      c.A = m->ws.x; c.lda = D; c.C = m->ws.qkv; c.ldc = 3 * L.inner; c.M = rows; c.N = 3 * L.inner;
-      c.stats_in = m->ws.sx;
-      if (L.hd == 64 && m->headmajor) {
-        DenseCall h = c;
-        h.flags |= EPI_HM;
-        h.ldc = 64;
-        h.P = T;
-        if (gemm_headmajor_ok(m->dtype, h.flags, dense_params(m, L.qkv, h))) {
-          c = h;
-          hm = true;
-          ++m->hm_layers;
-        }
-      }
-      EVT_RC(dense(m, L.qkv, c, s));
-    }
-    AttnParams ap{m->ws.qkv, 3 * L.inner, m->ws.o, L.inner, T, L.heads, B, scale_log2};
-    ap.hd = L.hd;
-    if (hm) {
-      ap.ldq = 64;
-      ap.sb = (int64_t)L.heads * 3 * T * 64;
-      ap.sh = (int64_t)3 * T * 64;
-      ap.ko = T * 64;
-      ap.vo = 2 * T * 64;
-    }
+    const uint8_t skip = m->skip_of(block);
+    const bool run_attn = !(skip & EVT_SKIP_ATTN), run_ffn = !(skip & EVT_SKIP_FFN);
     // The classifier and `pooled` read token 0 of the last block and nothing else, so its
     // out-proj, FC1 and FC2 run on the B CLS rows (the CLS tail, below) and its attention on query
-    // tile 0. A call that exports the last block's token map (tokens, or a tap on it) runs the
-    // full-row block as well; the CLS rows it exports, and the head reads, are still the tail's.
-    // The last block's FFN statistics are those of the full-row FC1 launch (evt_ffn_stats.h).
-    const bool last = block + 1 == (int)m->layers.size();
-    const bool full = !last || (call.feat && call.feat->tokens) || call.taps.last_is(block) ||
-                      call.fstats.last_is(block);
+    // tile 0. A call that exports the last block's token map (tokens, or a tap on it or on a
+    // skipped block after it) runs the full-row block as well; the CLS rows it exports, and the
+    // head reads, are still the tail's. The last block's FFN and stream statistics are those of the
+    // full-row launches (evt_ffn_stats.h, evt_depth.h).
+    const bool last = block == last_block;
+    // the call asks for this block's stream statistics (read here: the cursor moves on at the
+    // block's FFN sublayer)
+    const bool bs = call.bstats.wants(block);
+    const bool full = !last || (call.feat && call.feat->tokens) || call.taps.reaches(block) ||
+                      call.fstats.last_is(block) || bs;
     if (last) m->tail_mode = full ? 3 : 1;
-    {
-      ProfScope ps(m, EVT_PROF_ATTENTION, s);
-      prof_work(m, 4.0 * B * L.heads * (double)T * T * L.hd,
-                (double)rows * 4 * L.inner * elem_size(m->dtype));  // qkv read + O written
-      // (the model's work also where only query tile 0 runs: evt_model_profile_work)
-      AttnParams aq = ap;
-      aq.cls_only = !full && attention_cls_ok(m->dtype, ap);
-      EVT_HIP(attention_launch(m->dtype, aq, s), "attention");
-    }
-    EVT_RC(attn_map(m, call, block, ap));
-    EVT_RC(head_stats(m, call, block, ap));
-    EVT_RC(rollout_step(m, call, block, ap));
-    // out-proj + bias + LN1(x) residual -> xm (+ stats); STANDARD: + x
-    DenseCall co;
-    co.flags = m->standard ? (EPI_BIAS | EPI_RESID | EPI_STATS)
-                           : (EPI_BIAS | EPI_RESID | EPI_RESLN | EPI_STATS);
-    co.A = m->ws.o; co.lda = L.inner; co.C = m->ws.xm; co.ldc = D; co.M = rows; co.N = D;
-    co.resid = m->ws.x; co.ldr = D; co.rstats = m->ws.sx; co.rgamma = L.ln1_g; co.rbeta = L.ln1_b;
-    co.stats_out = m->ws.sm;
-    // LN2-folded FC1 + GELU (ffn.py:8; STANDARD: exact erf GELU)
-    DenseCall c1;
-    c1.flags = EPI_LNIN | EPI_BIAS | (m->standard ? EPI_GELU_ERF : EPI_GELU);
-    c1.A = m->ws.xm; c1.lda = D; c1.C = m->ws.hbuf; c1.ldc = L.ffn_st; c1.M = rows; c1.N = L.ffn_st;
-    c1.stats_in = m->ws.sm;
-    // FC2 + bias + LN2(xm) residual -> x (+ stats); STANDARD: + xm
-    DenseCall c2;
-    c2.flags = co.flags;
-    c2.A = m->ws.hbuf; c2.lda = L.ffn_st; c2.C = m->ws.x; c2.ldc = D; c2.M = rows; c2.N = D;
-    c2.resid = m->ws.xm; c2.ldr = D; c2.rstats = m->ws.sm; c2.rgamma = L.ln2_g; c2.rbeta = L.ln2_b;
-    c2.stats_out = m->ws.sx;
     // The CLS tail's form of a launch: row b is row b T of the stream and statistics buffers, in
     // place (the head, and `pooled`, read them where they always did), the FFN hidden rows compact
     // in ws.hc, and the 128x128 kernel whatever B is (one image alone = the image in a batch). It
@@ -248,24 +198,118 @@ int run_encoder(evt_model* m, ForwardCall& call) {
       c.work_M = full ? -1 : rows;
       return c;
     };
-    // Each full-row launch comes before its role's tail launch: the tail's out-proj still finds
-    // the block's input rows in x / sx, and what it, FC1 and FC2 leave in rows b T of xm / sm,
-    // hc and x / sx is what the next tail launch, the exports and the head read.
-    {
-      ProfScope ps(m, EVT_PROF_OUT_PROJ, s);
-      if (full) EVT_RC(dense(m, L.out, co, s));
-      if (last) EVT_RC(dense(m, L.out, tail(co), s));
+    // out-proj / FC2 epilogue: + bias + LN(x) residual (+ stats); STANDARD: + x
+    const int resid_flags = m->standard ? (EPI_BIAS | EPI_RESID | EPI_STATS)
+                                        : (EPI_BIAS | EPI_RESID | EPI_RESLN | EPI_STATS);
+    AttnParams ap{};
+    if (run_attn) {
+      const float scale_log2 = log2e / std::sqrt((float)L.hd);  // h_k^-0.5 (attention.py:13)
+      // qkv head-major ([B][heads][q | k | v][T][64], EPI_HM) where the QKV GEMM takes the
+      // persistent kernel (h_k = 64, bf16): an (image, head)'s q, k and v are three contiguous 25 KB
+      // runs instead of T 128-B pieces at a 3 D-element stride each; token-major otherwise
+      bool hm = false;
+      {  // LN1-folded QKV (attention.py:24)
+        ProfScope ps(m, EVT_PROF_QKV, s);
+        DenseCall c;
+        c.flags = EPI_LNIN | EPI_BIAS;
+        c.A = m->ws.x; c.lda = D; c.C = m->ws.qkv; c.ldc = 3 * L.inner; c.M = rows; c.N = 3 * L.inner;
+        c.stats_in = m->ws.sx;
+        if (L.hd == 64 && m->headmajor) {
+          DenseCall h = c;
+          h.flags |= EPI_HM;
+          h.ldc = 64;
+          h.P = T;
+          if (gemm_headmajor_ok(m->dtype, h.flags, dense_params(m, L.qkv, h))) {
+            c = h;
+            hm = true;
+            ++m->hm_layers;
+          }
+        }
+        EVT_RC(dense(m, L.qkv, c, s));
+      }
+      ap = AttnParams{m->ws.qkv, 3 * L.inner, m->ws.o, L.inner, T, L.heads, B, scale_log2};
+      ap.hd = L.hd;
+      if (hm) {
+        ap.ldq = 64;
+        ap.sb = (int64_t)L.heads * 3 * T * 64;
+        ap.sh = (int64_t)3 * T * 64;
+        ap.ko = T * 64;
+        ap.vo = 2 * T * 64;
+      }
+      {
+        ProfScope ps(m, EVT_PROF_ATTENTION, s);
+        prof_work(m, 4.0 * B * L.heads * (double)T * T * L.hd,
+                  (double)rows * 4 * L.inner * elem_size(m->dtype));  // qkv read + O written
+        // (the model's work also where only query tile 0 runs: evt_model_profile_work)
+        AttnParams aq = ap;
+        aq.cls_only = !full && attention_cls_ok(m->dtype, ap);
+        EVT_HIP(attention_launch(m->dtype, aq, s), "attention");
+      }
+      EVT_RC(attn_map(m, call, block, ap));
+      EVT_RC(head_stats(m, call, block, ap));
+      EVT_RC(rollout_step(m, call, block, ap));
+      // out-proj + bias + LN1(x) residual -> xm (+ stats); STANDARD: + x
+      DenseCall co;
+      co.flags = resid_flags;
+      co.A = m->ws.o; co.lda = L.inner; co.C = m->ws.xm; co.ldc = D; co.M = rows; co.N = D;
+      co.resid = m->ws.x; co.ldr = D; co.rstats = m->ws.sx; co.rgamma = L.ln1_g; co.rbeta = L.ln1_b;
+      co.stats_out = m->ws.sm;
+      // Each full-row launch comes before its role's tail launch: the tail's out-proj still finds
+      // the block's input rows in x / sx, and what it, FC1 and FC2 leave in rows b T of xm / sm,
+      // hc and x / sx is what the next tail launch, the exports and the head read.
+      // The stream statistics of a block the call asks for (then `full`) read the full-row
+      // launch's rows, so they run between the two.
+      {
+        ProfScope ps(m, EVT_PROF_OUT_PROJ, s);
+        if (full) EVT_RC(dense(m, L.out, co, s));
+        if (last && !bs) EVT_RC(dense(m, L.out, tail(co), s));
+      }
+      if (bs) {
+        EVT_RC(block_stats(m, call, block, 0, m->ws.x, m->ws.xm, T));
+        if (last) {
+          ProfScope ps(m, EVT_PROF_OUT_PROJ, s);
+          EVT_RC(dense(m, L.out, tail(co), s));
+        }
+      }
+    } else {
+      std::swap(m->ws.x, m->ws.xm);
+      std::swap(m->ws.sx, m->ws.sm);
+      EVT_RC(block_stats(m, call, block, 0, nullptr, nullptr, T));
     }
-    {
-      ProfScope ps(m, EVT_PROF_FC1, s);
-      if (full) EVT_RC(dense(m, L.fc1, c1, s));
-      if (last) EVT_RC(dense(m, L.fc1, tail(c1), s));
-    }
-    if (full) EVT_RC(ffn_stats(m, call, block, L, rows));
-    {
-      ProfScope ps(m, EVT_PROF_FC2, s);
-      if (full) EVT_RC(dense(m, L.fc2, c2, s));
-      if (last) EVT_RC(dense(m, L.fc2, tail(c2), s));
+    if (run_ffn) {
+      // LN2-folded FC1 + GELU (ffn.py:8; STANDARD: exact erf GELU)
+      DenseCall c1;
+      c1.flags = EPI_LNIN | EPI_BIAS | (m->standard ? EPI_GELU_ERF : EPI_GELU);
+      c1.A = m->ws.xm; c1.lda = D; c1.C = m->ws.hbuf; c1.ldc = L.ffn_st; c1.M = rows; c1.N = L.ffn_st;
+      c1.stats_in = m->ws.sm;
+      // FC2 + bias + LN2(xm) residual -> x (+ stats); STANDARD: + xm
+      DenseCall c2;
+      c2.flags = resid_flags;
+      c2.A = m->ws.hbuf; c2.lda = L.ffn_st; c2.C = m->ws.x; c2.ldc = D; c2.M = rows; c2.N = D;
+      c2.resid = m->ws.xm; c2.ldr = D; c2.rstats = m->ws.sm; c2.rgamma = L.ln2_g; c2.rbeta = L.ln2_b;
+      c2.stats_out = m->ws.sx;
+      {
+        ProfScope ps(m, EVT_PROF_FC1, s);
+        if (full) EVT_RC(dense(m, L.fc1, c1, s));
+        if (last) EVT_RC(dense(m, L.fc1, tail(c1), s));
+      }
+      if (full) EVT_RC(ffn_stats(m, call, block, L, rows));
+      {
+        ProfScope ps(m, EVT_PROF_FC2, s);
+        if (full) EVT_RC(dense(m, L.fc2, c2, s));
+        if (last && !bs) EVT_RC(dense(m, L.fc2, tail(c2), s));
+      }
+      if (bs) {
+        EVT_RC(block_stats(m, call, block, 1, m->ws.xm, m->ws.x, T));
+        if (last) {
+          ProfScope ps(m, EVT_PROF_FC2, s);
+          EVT_RC(dense(m, L.fc2, tail(c2), s));
+        }
+      }
+    } else {
+      std::swap(m->ws.x, m->ws.xm);
+      std::swap(m->ws.sx, m->ws.sm);
+      EVT_RC(block_stats(m, call, block, 1, nullptr, nullptr, T));
     }
     EVT_RC(feat_tap(m, call, block, D, rows, D));
     if (call.tprune_next < (int)m->tp_blocks.size() && m->tp_blocks[call.tprune_next] == block) {

@@ -192,6 +192,22 @@ constexpr int FFN_STATS_MAX_TOKENS = 4096;  // EVT_FFN_STATS_MAX_TOKENS of the h
 hipError_t ffn_stats_launch(int dtype, const void* h, int64_t ld, int B, int T, int F, float* out,
                             hipStream_t s);
 
+// Stream-delta statistics (depth_stats.hip; include/evt_depth.h): out[b ldo + 0..3] = (cosine,
+// rel_update, norm_ratio, cls_cosine) of the rows b T .. b T + T - 1 of a against those of b (B T
+// rows of D elements, pitches lda / ldb, dtype bf16 or f32). One launch for T <= STREAM_DELTA_CHUNK;
+// above it two, with the per-chunk partials in `part` (stream_delta_part_bytes(B, T), 16-byte
+// aligned). D a multiple of 8, pitches >= D and a multiple of 16 bytes, ldo a multiple of 4, a, b
+// and out 16-byte aligned, 1 <= T <= 4096, B >= 1 (hipErrorInvalidValue otherwise).
+constexpr int STREAM_DELTA_MAX_TOKENS = 4096;  // EVT_DEPTH_MAX_TOKENS of the header
+constexpr int STREAM_DELTA_CHUNK = 16;         // tokens of an image one workgroup owns
+inline size_t stream_delta_part_bytes(int B, int T) {
+  const size_t chunks = ((size_t)T + STREAM_DELTA_CHUNK - 1) / STREAM_DELTA_CHUNK;
+  return chunks > 1 ? (size_t)B * chunks * 4 * sizeof(float) : 0;
+}
+hipError_t stream_delta_launch(int dtype, const void* a, int64_t lda, const void* b, int64_t ldb,
+                               int B, int T, int D, float* out, int64_t ldo, float* part,
+                               hipStream_t s);
+
 
 // LayerNorm over rows of D (fp32 in) -> activation dtype out (eps 1e-5).
 hipError_t layernorm_launch(int dtype, const float* x, int64_t ldx, void* y, int64_t ldy,

@@ -266,6 +266,39 @@ int ffn_stats(evt_model* m, ForwardCall& call, int block, const Layer& L, int ro
   return EVT_OK;
 }
 
+// At both sublayer ends of an evt_forward_block_stats call, while the sublayer's input rows `a`
+// and output rows `b` are both resident (run_encoder): its four stream statistics, if the block
+// is the next one asked for (depth_stats.hip; counted under EVT_PROF_HEAD). The per-chunk partials
+// live in the FFN hidden buffer, idle at both points. A skipped sublayer (a == nullptr) gets the
+// identity values by a strided copy from the handle's constant rows: no kernel.
+int block_stats(evt_model* m, ForwardCall& call, int block, int sub, const void* a, const void* b,
+                int T) {
+  if (!call.bstats.wants(block)) return EVT_OK;
+  float* out = call.bstats.out[call.bstats.next] + sub * EVT_DEPTH_STATS;
+  if (sub == 1) ++call.bstats.next;
+  const size_t row = EVT_DEPTH_STATS * sizeof(float);
+  if (!a) {
+    // the rows are the parent handle's (evt_model_set_skips): an analysis forward runs as one lane
+    // on the handle's own workspace, never on a lane child, which has none
+    if (!m->skip_ident)
+      return fail(EVT_EINVAL, "block statistics: a lane child has no identity rows");
+    EVT_HIP(hipMemcpy2DAsync(out, 2 * row, m->skip_ident, row, row, call.B,
+                             hipMemcpyDeviceToDevice, call.s),
+            "block statistics of a skipped sublayer");
+    return EVT_OK;
+  }
+  if (stream_delta_part_bytes(call.B, T) > m->ws.hbuf_bytes)
+    return fail(EVT_EINVAL, "block statistics: the FFN hidden buffer is too small for the partials");
+  ProfScope ps(m, EVT_PROF_HEAD, call.s);
+  const double rows = (double)call.B * T;
+  prof_work(m, 8.0 * rows * m->D,  // four fused multiply-adds per element pair
+            2.0 * rows * m->D * elem_size(m->dtype) + 4.0 * call.B * EVT_DEPTH_STATS);
+  EVT_HIP(stream_delta_launch(m->dtype, a, m->D, b, m->D, call.B, T, m->D, out,
+                              2 * EVT_DEPTH_STATS, (float*)m->ws.hbuf, call.s),
+          "block statistics");
+  return EVT_OK;
+}
+
 // Scratch layout of a rollout call (include/evt_rollout.h): the head mean, then up to two rollout
 // buffers that alternate (a step cannot run in place); the last step writes the caller's output
 static int rollout_bufs(int depth) { return 1 + std::min(depth - 1, 2); }
@@ -671,6 +704,17 @@ static int check_blocks(const BlockList& l, int nb, const char* refused, uintptr
   return EVT_OK;
 }
 
+// The entries of a validated list on a handle with skips (include/evt_depth.h): EVT_EINVAL naming
+// the skip if one of them is a block whose sublayer `bit` (EVT_SKIP_ATTN / _FFN) is skipped
+static int no_skipped(const evt_model* m, const BlockList& l, int bit) {
+  for (int i = 0; i < l.n; ++i)
+    if (m->skip_of(l.blocks[i]) & bit)
+      return fail(EVT_EINVAL, std::string(l.block) + " " + std::to_string(l.blocks[i]) + ": the " +
+                                  "block's " + (bit == EVT_SKIP_ATTN ? "attention" : "FFN") +
+                                  " sublayer is skipped (evt_model_set_skips), it computes nothing");
+  return EVT_OK;
+}
+
 static BlockList tap_list(const evt_features_args* a) {
   return {a->n_taps, a->tap_blocks, a->taps, "n_taps", "tap_blocks and taps", "tap block",
           "tap_blocks", "tap pointer", "feature outputs"};
@@ -840,6 +884,7 @@ static int attention_forward(evt_model* m, const evt_image_args* in, int B,
   if (a->queries != EVT_ATTN_CLS && a->queries != EVT_ATTN_ALL)
     return fail(EVT_EINVAL, "queries must be EVT_ATTN_CLS or EVT_ATTN_ALL");
   EVT_RC(check_blocks(maps, model_blocks(m), nullptr, nullptr));
+  EVT_RC(no_skipped(m, maps, EVT_SKIP_ATTN));
   call.maps = maps.cursor();
   call.map_queries = a->queries;
   return forward(m, call, false);
@@ -886,6 +931,7 @@ int evt_forward_head_stats(evt_model* m, const evt_image_args* in, int B,
   EVT_RC(analysis_call(m, in, B, feat, stream, attn_family, "evt_forward_head_stats", &stats,
                        &call));
   EVT_RC(check_blocks(stats, model_blocks(m), no_patch_grid(m), nullptr));
+  EVT_RC(no_skipped(m, stats, EVT_SKIP_ATTN));
   call.hstats = stats.cursor();
   return forward(m, call, false);
 }
@@ -924,6 +970,7 @@ int evt_forward_ffn_stats(evt_model* m, const evt_image_args* in, int B,
   EVT_RC(analysis_call(m, in, B, feat, stream, ffn_stats_family, "evt_forward_ffn_stats", &stats,
                        &call));
   EVT_RC(check_blocks(stats, model_blocks(m), nullptr, nullptr));
+  EVT_RC(no_skipped(m, stats, EVT_SKIP_FFN));
   call.fstats = stats.cursor();
   return forward(m, call, false);
 }
@@ -974,6 +1021,10 @@ int evt_forward_rollout(evt_model* m, const evt_image_args* in, int B,
   if (a->scratch_bytes < need)
     return fail(EVT_EINVAL, "rollout scratch_bytes is " + std::to_string(a->scratch_bytes) +
                                 ", this call needs " + std::to_string(need));
+  for (int i = a->start; i < depth; ++i)
+    if (m->skip_of(i) & EVT_SKIP_ATTN)
+      return fail(EVT_EINVAL, "rollout: the attention sublayer of block " + std::to_string(i) +
+                                  " is skipped (evt_model_set_skips), it has no attention map");
   call.rollout = a;
   return forward(m, call, false);
 }
@@ -987,6 +1038,26 @@ static int token_pruning_family(const evt_model* m) {
     return fail(EVT_EINVAL, "token pruning: T2T-ViT is not supported yet (ViT handles only)");
   if (m->mx8)
     return fail(EVT_EINVAL, "token pruning is not available on an EVT_DTYPE_MX8 model");
+  return EVT_OK;
+}
+
+// A skip mask and a token schedule on one handle (include/evt_depth.h): a scheduled block scores
+// its tokens by the attention it ran, and has a block that runs after it
+static int skips_fit_schedule(const evt_model* m, const std::vector<uint8_t>& mask,
+                              const int32_t* blocks, int n) {
+  if (mask.empty()) return EVT_OK;
+  int last = (int)mask.size() - 1;
+  while (last >= 0 && mask[last] == (EVT_SKIP_ATTN | EVT_SKIP_FFN)) --last;
+  for (int i = 0; i < n; ++i) {
+    if (mask[blocks[i]] & EVT_SKIP_ATTN)
+      return fail(EVT_EINVAL, "token schedule: the attention sublayer of block " +
+                                  std::to_string(blocks[i]) + " is skipped (evt_model_set_skips): "
+                                  "it has no CLS attention to score tokens by");
+    if (blocks[i] >= last)
+      return fail(EVT_EINVAL, "token schedule: block " + std::to_string(blocks[i]) + " is the last "
+                                  "block that runs under the skip mask (evt_model_set_skips), or "
+                                  "comes after it: its output is the CLS token's alone");
+  }
   return EVT_OK;
 }
 
@@ -1016,6 +1087,7 @@ int evt_model_set_token_schedule(evt_model* m, int n, const int32_t* blocks, con
                                   std::to_string(T - 1) + "], the block's patch tokens");
     T = keep[i] + 1;
   }
+  EVT_RC(skips_fit_schedule(m, m->skips, blocks, n));
   m->tp_blocks.assign(blocks, blocks + n);
   m->tp_keep.assign(keep, keep + n);
   for (evt_model* c : m->lanes) {  // lanes set later copy the core, the schedule with it
@@ -1210,6 +1282,103 @@ int evt_model_get_head_gates(const evt_model* m, int block, float* gates, int ca
 
 int evt_model_get_ffn_gates(const evt_model* m, int block, float* gates, int cap, int* n) {
   return get_gates(m, block, true, gates, cap, n);
+}
+
+// ---- depth: stream statistics and sublayer skips (include/evt_depth.h) ------------------------
+
+static int depth_family(const evt_model* m, const char* what) {
+  if (m->family == FAM_SWIN)
+    return fail(EVT_EINVAL, std::string(what) + ": Swin is not supported (ViT handles only)");
+  if (m->family == FAM_T2T)
+    return fail(EVT_EINVAL, std::string(what) + ": T2T-ViT is not supported yet (ViT handles only)");
+  if (m->mx8)
+    return fail(EVT_EINVAL, std::string(what) + " is not available on an EVT_DTYPE_MX8 model");
+  return EVT_OK;
+}
+static int block_stats_family(const evt_model* m) { return depth_family(m, "block statistics"); }
+
+int evt_block_stats_shape(const evt_model* m, int block, int* sublayers, int* stats, int* tokens) {
+  if (!m || !sublayers || !stats || !tokens) return fail(EVT_EINVAL, "null argument");
+  EVT_RC(block_stats_family(m));
+  if (block < 0 || block >= (int)m->layers.size())
+    return fail(EVT_EINVAL, "block must be in [0, " + std::to_string(m->layers.size()) + ")");
+  *sublayers = 2;
+  *stats = EVT_DEPTH_STATS;
+  *tokens = m->sh.T;
+  return EVT_OK;
+}
+
+int evt_forward_block_stats(evt_model* m, const evt_image_args* in, int B,
+                            const evt_features_args* feat, const evt_block_stats_args* a,
+                            void* stream) {
+  if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and bs must be non-null");
+  const BlockList stats = {a->n_blocks, a->blocks, a->stats, "n_blocks", "blocks and stats",
+                           "block statistics block", "block statistics blocks", "stats pointer",
+                           "block statistics"};
+  ForwardCall call;
+  EVT_RC(analysis_call(m, in, B, feat, stream, block_stats_family, "evt_forward_block_stats",
+                       &stats, &call));
+  EVT_RC(check_blocks(stats, model_blocks(m), nullptr, nullptr));
+  call.bstats = stats.cursor();
+  return forward(m, call, false);
+}
+
+int evt_model_set_skips(evt_model* m, const uint8_t* mask, int depth, void* stream) {
+  if (!m) return fail(EVT_EINVAL, "set_skips: model is NULL");
+  if (m->is_lane) return fail(EVT_EINVAL, "set_skips: the model is a lane of another model");
+  EVT_RC(depth_family(m, "sublayer skipping"));
+  if (m->graph) return fail(EVT_EINVAL, "set the skips before evt_graph_capture");
+  hipStream_t s = (hipStream_t)stream;
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  EVT_HIP(hipStreamIsCapturing(s, &st), "stream capture status");
+  if (st != hipStreamCaptureStatusNone)
+    return fail(EVT_EINVAL, "set_skips: the stream is capturing (a graph records the launches of "
+                            "the mask it was captured under: set the skips before the capture)");
+  std::vector<uint8_t> skips;
+  if (mask) {
+    const int nb = (int)m->layers.size();
+    if (depth != nb)
+      return fail(EVT_EINVAL, "set_skips: depth is " + std::to_string(depth) + ", the model has " +
+                                  std::to_string(nb) + " blocks");
+    bool any = false;
+    for (int i = 0; i < nb; ++i) {
+      if (mask[i] & ~(EVT_SKIP_ATTN | EVT_SKIP_FFN))
+        return fail(EVT_EINVAL, "set_skips: mask of block " + std::to_string(i) + " has bits "
+                                    "beyond EVT_SKIP_ATTN | EVT_SKIP_FFN");
+      any = any || mask[i];
+    }
+    if (any) skips.assign(mask, mask + nb);
+    if (any && std::all_of(skips.begin(), skips.end(),
+                           [](uint8_t v) { return v == (EVT_SKIP_ATTN | EVT_SKIP_FFN); }))
+      return fail(EVT_EINVAL, "set_skips: the mask skips every block, no sublayer of the encoder "
+                              "would run (create the model with depth 0 instead)");
+  }
+  EVT_RC(skips_fit_schedule(m, skips, m->tp_blocks.data(), (int)m->tp_blocks.size()));
+  if (!skips.empty() && !m->skip_ident) {
+    std::vector<float> rows((size_t)m->max_batch * EVT_DEPTH_STATS);
+    for (size_t i = 0; i < rows.size(); i += EVT_DEPTH_STATS) {
+      rows[i + EVT_DEPTH_COSINE] = rows[i + EVT_DEPTH_NORM_RATIO] = rows[i + EVT_DEPTH_CLS_COSINE] = 1.f;
+      rows[i + EVT_DEPTH_REL_UPDATE] = 0.f;
+    }
+    float* d = nullptr;
+    EVT_RC(dev_alloc(m, (void**)&d, rows.size() * sizeof(float)));
+    // once per handle, 16 bytes per image: a synchronous copy, so the rows are on the device
+    // before any forward, on whatever stream, can be enqueued behind this call
+    EVT_HIP(hipMemcpy(d, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice),
+            "skip identity rows");
+    m->skip_ident = d;
+  }
+  m->skips = skips;
+  for (evt_model* c : m->lanes) c->skips = skips;  // lanes set later copy the core, the mask with it
+  return EVT_OK;
+}
+
+int evt_model_get_skips(const evt_model* m, uint8_t* mask, int cap, int* depth) {
+  if (!m || !depth || cap < 0) return fail(EVT_EINVAL, "get_skips: a NULL model or depth, or cap < 0");
+  EVT_RC(depth_family(m, "sublayer skipping"));
+  *depth = (int)m->layers.size();
+  for (int i = 0; mask && i < *depth && i < cap; ++i) mask[i] = m->skip_of(i);
+  return EVT_OK;
 }
 
 // ---- Swin window attention maps (include/evt_window_attention.h) ----------------------------

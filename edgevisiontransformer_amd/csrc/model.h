@@ -142,6 +142,18 @@ struct ModelCore {
   // tp_keep[i] patch tokens. The one part of a core that changes after create; lane children get
   // the parent's copy (set_lanes copies the core, set_token_schedule writes every lane)
   std::vector<int32_t> tp_blocks, tp_keep;
+  // evt_model_set_skips (ViT; include/evt_depth.h): per block bit 0 = the attention sublayer, bit 1
+  // = the FFN sublayer is left out of the forward; empty: none. Changes after create like the
+  // schedule, and reaches the lanes the same way
+  std::vector<uint8_t> skips;
+  uint8_t skip_of(int block) const { return skips.empty() ? 0 : skips[block]; }
+  // the last block that runs a sublayer: the CLS tail's block (evt_model_set_skips refuses a mask
+  // that skips every block; -1 only for a model of depth 0)
+  int last_running() const {
+    int i = (int)layers.size() - 1;
+    while (i >= 0 && skip_of(i) == 3) --i;
+    return i;
+  }
   // desc's per-layer arrays live in this core's own vectors (after every copy of a core)
   void bind_desc() {
     desc.heads = heads.data();
@@ -229,6 +241,9 @@ struct evt_model : evt::ModelCore {  // a handle: the core, its own workspace, i
   // evt_model_set_head_gates / _ffn_gates: per encoder block, sized at the first set. The parent
   // handle's alone: the lanes read the parent's weight allocations, which the gate kernel rewrites
   std::vector<evt::LayerGates> gates;
+  // [max_batch][4] fp32 (1, 0, 1, 1): what evt_forward_block_stats copies out for a skipped
+  // sublayer; allocated by the first evt_model_set_skips that skips something
+  float* skip_ident = nullptr;
 };
 
 namespace evt {
@@ -244,6 +259,7 @@ struct BlockCursor {
   // block's output pointer, moving on to the next entry, if block is the next entry; else null
   float* take(int block) { return wants(block) ? out[next++] : nullptr; }
   bool last_is(int block) const { return n > 0 && blocks[n - 1] == block; }
+  bool reaches(int block) const { return n > 0 && blocks[n - 1] >= block; }  // an entry >= block
 };
 
 // The arguments of one forward. The entry points build one and the run functions read it; nothing
@@ -263,6 +279,7 @@ struct ForwardCall {
   int map_queries = 0;            // EVT_ATTN_CLS or EVT_ATTN_ALL rows
   BlockCursor hstats;             // evt_forward_head_stats blocks
   BlockCursor fstats;             // evt_forward_ffn_stats blocks
+  BlockCursor bstats;             // evt_forward_block_stats blocks
   void set_feat(const evt_features_args* a) {
     feat = a;
     if (a) taps = BlockCursor{a->tap_blocks, a->taps, a->n_taps};
@@ -409,6 +426,11 @@ int head_stats(evt_model* m, ForwardCall& call, int block, const AttnParams& ap)
 // evt_forward_ffn_stats: block's neuron statistics of the `rows` hidden rows the full-row FC1 left in
 // ws.hbuf, if the call asks for them next (between FC1 and FC2)
 int ffn_stats(evt_model* m, ForwardCall& call, int block, const Layer& L, int rows);
+// evt_forward_block_stats: sublayer `sub` (0 attention, 1 FFN) of block `block`, if the call asks
+// for the block next: the statistics of the stream rows b against a (T tokens per image), or with
+// a == nullptr the identity values of a skipped sublayer. sub == 1 moves the cursor on.
+int block_stats(evt_model* m, ForwardCall& call, int block, int sub, const void* a, const void* b,
+                int T);
 // evt_forward_rollout: block's head mean and rollout step, from the call's start block on
 int rollout_step(evt_model* m, ForwardCall& call, int block, const AttnParams& ap);
 // Token pruning (include/evt_token_pruning.h). tokens_at: T_l of block `block` under m's schedule.

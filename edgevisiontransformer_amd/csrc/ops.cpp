@@ -453,6 +453,35 @@ int evt_ffn_neuron_stats(int dtype, const void* h, int64_t ld, int B, int T, int
   return EVT_OK;
 }
 
+// include/evt_depth.h: the stream-delta kernel on caller buffers; the per-chunk partials of an
+// image of more than 16 tokens come from, and go back to, the stream's memory pool
+int evt_stream_delta_stats(int dtype, const void* a, int64_t lda, const void* b, int64_t ldb,
+                           int B, int T, int D, float* out, void* stream) {
+  if (dtype != EVT_DTYPE_F32 && dtype != EVT_DTYPE_BF16)
+    return fail(EVT_EINVAL, "stream_delta_stats: dtype must be EVT_DTYPE_F32 or EVT_DTYPE_BF16");
+  static_assert(EVT_DEPTH_MAX_TOKENS == STREAM_DELTA_MAX_TOKENS, "header and kernel agree");
+  if (B < 1) return fail(EVT_EINVAL, "stream_delta_stats: B must be at least 1");
+  if (T < 1 || T > EVT_DEPTH_MAX_TOKENS)
+    return fail(EVT_EINVAL, "stream_delta_stats: T must be in [1, 4096]");
+  if (D < 8 || D % 8)
+    return fail(EVT_EINVAL, "stream_delta_stats: D must be a positive multiple of 8");
+  const int64_t vec = dtype == DT_BF16 ? 8 : 4;
+  if (lda < D || ldb < D || lda % vec || ldb % vec)
+    return fail(EVT_EINVAL, "stream_delta_stats: lda and ldb must be at least D and the row "
+                            "pitches a multiple of 16 bytes");
+  if (!a || !b || !out) return fail(EVT_EINVAL, "stream_delta_stats: a, b and out must be non-null");
+  if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15)
+    return fail(EVT_EINVAL, "stream_delta_stats: a, b and out must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  float* part = nullptr;
+  const size_t bytes = stream_delta_part_bytes(B, T);
+  if (bytes) EVT_HIP(hipMallocAsync((void**)&part, bytes, s), "malloc partials");
+  const hipError_t e = stream_delta_launch(dtype, a, lda, b, ldb, B, T, D, out, 4, part, s);
+  if (part) (void)hipFreeAsync(part, s);
+  EVT_HIP(e, "stream_delta_stats");
+  return EVT_OK;
+}
+
 // include/evt_rollout.h: evt_attention_probs' checks of (qkv, layout, shape, scale), then the
 // rollout buffers and the scratch; two launches (the head mean into the scratch, then the step)
 int evt_attention_rollout_step(int dtype, const void* qkv, int64_t ldq, int64_t sb, int64_t sh,

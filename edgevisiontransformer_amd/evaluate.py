@@ -123,6 +123,51 @@ def head_ablation(model, loader: Iterable, topk: int = 5, transform=None, blocks
     return res
 
 
+def sublayer_ablation(model, loader: Iterable, topk: int = 5, transform=None, blocks=None,
+                      log: Optional[Callable[[str], None]] = None) -> Dict[str, object]:
+    """The depth twin of `head_ablation`: {"base": `evaluate`'s result with the model's current
+    skips, "acc1": [[top-1 accuracy with the attention sublayer of block l skipped, ... with its
+    FFN sublayer skipped] per block], "acck": the same for top-`topk`, "blocks": the block indices
+    of the rows}. `blocks=None` sweeps every block (negative indices and any order as
+    `block_stats`). A sublayer the model skips already is NaN: there is nothing left to ablate.
+
+    One sublayer at a time is skipped on top of the skips the model already has
+    (modeling/models/depth.py: its kernels are not launched), and the whole loader is counted by
+    `evaluate` on the device. `loader` is re-iterated once per sublayer and once for the base: give
+    a list (or anything that can be iterated again), not a one-shot generator; nothing is
+    materialised here. The model's skips are back as they were at the end, also on an exception.
+    `log` gets one line per sublayer."""
+    from .modeling.models.depth import SKIP_BITS, SKIP_NAMES, SUBLAYERS
+    from .modeling.models.features import resolve_taps
+    model.block_stats_shape(0)  # a model without a depth axis: ValueError before any pass
+    nb = model.num_blocks
+    idx = resolve_taps(range(nb) if blocks is None else blocks, nb)
+    res: Dict[str, object] = {"base": evaluate(model, loader, topk=topk, transform=transform),
+                              "acc1": [], "acck": [], "blocks": list(idx)}
+    for l in idx:
+        row1, rowk = [], []
+        for sub in SUBLAYERS:
+            mine = model.skipped()
+            have = SKIP_BITS.get(mine.get(l, ""), 0)
+            if have & SKIP_BITS[sub]:
+                row1.append(float("nan"))
+                rowk.append(float("nan"))
+                continue
+            with model.skipping({**mine, l: SKIP_NAMES[have | SKIP_BITS[sub]]}):
+                r = evaluate(model, loader, topk=topk, transform=transform)
+            if r["seen"] != res["base"]["seen"]:
+                raise ValueError("sublayer_ablation: the loader gave a different number of images "
+                                 "on a later pass (it must be re-iterable)")
+            row1.append(r["acc1"])
+            rowk.append(r["acck"])
+            if log is not None:
+                log(f"sublayer_ablation block {l} {sub}: acc1 {r['acc1'] * 100:.2f}% "
+                    f"(base {res['base']['acc1'] * 100:.2f}%)")
+        res["acc1"].append(row1)
+        res["acck"].append(rowk)
+    return res
+
+
 def collect_head_stats(model, loader: Iterable, transform=None, blocks=None):
     """Dataset means of the per-head attention statistics (modeling/models/head_stats.py): one
     fp64 [H_i, 4] array per block (`blocks=None`: every block; negative indices and any order as

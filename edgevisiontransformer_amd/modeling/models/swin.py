@@ -32,10 +32,10 @@ import torch
 
 from ... import _lib
 from ...weights import SwinConfig, make_swin_params, swin_config, swin_param_shapes
-from .gates import StructuredGates
+from .depth import DepthAxis
 
 
-class SwinTransformer(StructuredGates):
+class SwinTransformer(DepthAxis):
     """Swin Transformer forward on MI355X (microsoft `SwinTransformer`, built by reference
     `utils.py:28-43`). Stage widths (embed_dim * 2^i) up to 1536: Swin-T / S / B / L."""
 
@@ -91,7 +91,7 @@ class SwinTransformer(StructuredGates):
         d.dtype, d.max_batch = _lib.DTYPE[self.dtype], max_batch
         return d
 
-    forward = StructuredGates.__call__  # the microsoft name
+    forward = DepthAxis.__call__  # the microsoft name
 
     # -- feature outputs (features.py): forward_features = mean over tokens of LN(x) ----------
     def _feature_geometry(self):

@@ -24,10 +24,10 @@ import torch
 
 from ... import _lib
 from ...weights import T2TConfig, make_t2t_params, t2t_config, t2t_param_shapes
-from .gates import StructuredGates
+from .depth import DepthAxis
 
 
-class T2T_ViT(StructuredGates):
+class T2T_ViT(DepthAxis):
     """Tokens-to-Token ViT forward on MI355X (reference `T2T_ViT`, t2t_vit.py:91-135).
     `image_size`: a multiple of 16 with (image_size / 16)^2 + 1 <= 4096 tokens."""
 

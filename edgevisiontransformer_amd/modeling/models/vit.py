@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from ... import _lib
-from .gates import StructuredGates
+from .depth import DepthAxis
 from ...weights import (ViTConfig, make_std_vit_params, make_vit_params, std_vit_param_shapes,
                         vit_config, vit_param_shapes)
 
@@ -54,7 +54,7 @@ def decode_prune_encoding(prune_encoding: str):
     return prune_setting, num_heads_list, ffn_threshold_list
 
 
-class ViT(StructuredGates):
+class ViT(DepthAxis):
     """Vision Transformer forward on MI355X (reference `ViT`, vit.py:9-55).
 
     `image_size` / `patch_size`: any pair with (image_size / patch_size)^2 + 1 <= 4096 tokens per
@@ -66,6 +66,7 @@ class ViT(StructuredGates):
     SEMANTICS = _lib.VIT_REFERENCE
     _TOKEN_PRUNING_OK = True
     _GATES_OK = True
+    _DEPTH_OK = True
     _param_shapes = staticmethod(vit_param_shapes)
     _make_params = staticmethod(make_vit_params)
     layer_norm_eps = 0.0  # 0: the library default 1e-5 (reference norm.py:6)

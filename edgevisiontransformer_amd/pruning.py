@@ -235,6 +235,100 @@ def ffn_keep_from_importance(importance: Sequence[np.ndarray],
             for k, v in zip(counts, layers)]
 
 
+def sublayer_importance_from_stats(means: Sequence[np.ndarray], kind: str = "cosine") -> np.ndarray:
+    """The [layers, 2] sublayer importance table (columns: attention, FFN) from the stream
+    statistics of every block: `means[l]` is a [2, 4] array (`collect_block_stats`) or a [B, 2, 4]
+    one (`block_stats`, averaged over its images here), columns in DEPTH_STATS order. `kind`:
+
+        "cosine"      1 - cosine: how far the sublayer turns the stream (0: it leaves the direction)
+        "rel_update"  the statistic itself: the size of the update relative to the stream
+
+    A higher value is a more important sublayer; a skipped sublayer scores 0 either way. ValueError:
+    an unknown `kind`, no blocks, a malformed array."""
+    if kind not in ("cosine", "rel_update"):
+        raise ValueError(f'kind must be "cosine" or "rel_update", got {kind!r}')
+    rows = []
+    for l, s in enumerate(means):
+        a = np.asarray(s, dtype=np.float64)
+        if a.ndim == 3 and a.shape[0] > 0:
+            a = a.mean(axis=0)
+        if a.shape != (2, 4):  # (attention, FFN) x DEPTH_STATS of modeling/models/depth.py
+            raise ValueError(f"means[{l}] must be [2, 4] or [B, 2, 4], got {np.shape(s)}")
+        rows.append(1.0 - a[:, 0] if kind == "cosine" else a[:, 1].copy())
+    if not rows:
+        raise ValueError("no blocks given")
+    return np.stack(rows)
+
+
+def importance_from_sublayer_ablation(result: Dict[str, object]) -> np.ndarray:
+    """The [rows, 2] sublayer importance table from `sublayer_ablation`'s result (evaluate.py): base
+    top-1 accuracy minus the top-1 accuracy with that sublayer skipped; row i is block
+    result["blocks"][i]. A sublayer that was skipped already (NaN in the result) scores 0: it can
+    be dropped at no further cost. ValueError: no rows, or rows that are not (attention, FFN)."""
+    rows = np.asarray(result["acc1"], dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[0] < 1 or rows.shape[1] != 2:
+        raise ValueError(f"the ablation result must have [blocks, 2] accuracies, got {rows.shape}")
+    return np.where(np.isnan(rows), 0.0, float(result["base"]["acc1"]) - rows)
+
+
+def sublayers_from_importance(importance, drop: int,
+                              blocks: Optional[Sequence[int]] = None) -> Dict[int, str]:
+    """The `{block: "attn" | "ffn" | "block"}` dict `skip_sublayers` takes: the `drop` least
+    important sublayers of a [layers, 2] table (ties go to the earlier block, attention before
+    FFN); a block that loses both is "block". Row i is block `blocks[i]` (default: i). ValueError: a
+    malformed table, NaN, `drop` outside [0, 2 * layers]."""
+    imp = np.asarray(importance, dtype=np.float64)
+    if imp.ndim != 2 or imp.shape[1] != 2 or imp.shape[0] < 1:
+        raise ValueError(f"importance must be [layers, 2], got {imp.shape}")
+    if np.isnan(imp).any():
+        raise ValueError("importance holds NaN")
+    if isinstance(drop, bool) or not 0 <= int(drop) <= imp.size:
+        raise ValueError(f"drop must be in [0, {imp.size}], got {drop!r}")
+    idx = list(range(imp.shape[0])) if blocks is None else [int(b) for b in blocks]
+    if len(idx) != imp.shape[0]:
+        raise ValueError("one block index per row")
+    bits: Dict[int, int] = {}
+    for flat in np.argsort(imp.reshape(-1), kind="stable")[:int(drop)]:
+        l, sub = divmod(int(flat), 2)
+        bits[idx[l]] = bits.get(idx[l], 0) | (1 << sub)
+    return {b: ("attn", "ffn", "block")[v - 1] for b, v in sorted(bits.items())}
+
+
+def drop_blocks(params: Dict[str, np.ndarray], cfg: ViTConfig,
+                blocks: Sequence[int]) -> Tuple[Dict[str, np.ndarray], ViTConfig]:
+    """(params, config) of the shallower model without the layers `blocks` (negative: from the
+    last), the remaining layers renumbered l0, l1, ... in their order: what a model with these
+    blocks skipped whole (`skip_sublayers({b: "block"})`) is cut to, bitwise. Everything that is not
+    a layer's (`l{i}.*`) is the input's own array. ValueError: a block out of range or named twice."""
+    import dataclasses
+    depth = cfg.depth
+    gone = set()
+    for b in blocks:
+        if isinstance(b, bool) or not isinstance(b, (int, np.integer)):
+            raise ValueError(f"blocks must be integers, got {b!r}")
+        i = int(b) + depth if b < 0 else int(b)
+        if not 0 <= i < depth:
+            raise ValueError(f"block {b} is outside the model's {depth} blocks")
+        if i in gone:
+            raise ValueError(f"block {i} is named twice")
+        gone.add(i)
+    kept = [i for i in range(depth) if i not in gone]
+    new_index = {old: new for new, old in enumerate(kept)}
+    out: Dict[str, np.ndarray] = {}
+    for name, value in params.items():
+        layer, dot, rest = name.partition(".")
+        if dot and layer[:1] == "l" and layer[1:].isdigit():
+            old = int(layer[1:])
+            if old in new_index:
+                out[f"l{new_index[old]}.{rest}"] = value
+        else:
+            out[name] = value
+    pick = lambda v: tuple(list(v)[i] for i in kept)  # noqa: E731
+    new_cfg = dataclasses.replace(cfg, depth=len(kept), heads=pick(cfg.heads),
+                                  head_dim=pick(cfg.head_dim), ffn=pick(cfg.ffn))
+    return out, new_cfg
+
+
 def prune_vit_params(params: Dict[str, np.ndarray], cfg: ViTConfig, kept_heads: List[List[int]],
                      kept_ffn: Optional[List[List[int]]] = None,
                      head_size: int = 64) -> Tuple[Dict[str, np.ndarray], ViTConfig]:

@@ -5,6 +5,7 @@
     python -m edgevisiontransformer_amd.tools gpu_benchmark --model vit_huge_patch14_224 --input_shape 64,3,224,224
     python -m edgevisiontransformer_amd.tools gpu_benchmark --model deit_tiny --prune_encoding all_head2_ffn0.7
     python -m edgevisiontransformer_amd.tools gpu_benchmark --model deit_base --mask_heads 3:1,3:5
+    python -m edgevisiontransformer_amd.tools gpu_benchmark --model deit_base --skip 10:attn,11:block
     python -m edgevisiontransformer_amd.tools test_keras_latency --model t2t_vit_14 --input_shape 1,224,224,3
     python -m edgevisiontransformer_amd.tools prune_benchmark --types tiny --num_runs 20
     python -m edgevisiontransformer_amd.tools fetch_latency_std -f bench.log
@@ -189,6 +190,9 @@ def _server_flags(parser: argparse.ArgumentParser) -> None:
     parser.add_argument("--mask_heads", default=None, type=str,
                         help="heads to mask block:head,... (ViT models; the reference's "
                              "--attention_mask_heads layer:head, 0-based), e.g. 3:1,3:5")
+    parser.add_argument("--skip", default=None, type=str,
+                        help="sublayers to leave out block:attn|ffn|block,... (ViT models; "
+                             "negative blocks count from the last), e.g. 5:attn,9:block")
     parser.add_argument("--use_gpu", action="store_true", help="accepted; always the GPU")
     parser.add_argument("--num_runs", type=int, default=50)
     parser.add_argument("--warmup_runs", type=int, default=50)
@@ -221,6 +225,9 @@ def parse_server_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     if args.mask_heads is not None:
         from .modeling.models.gates import parse_mask_heads
         args.mask_heads = parse_mask_heads(args.mask_heads)  # {block: [heads]}
+    if args.skip is not None:
+        from .modeling.models.depth import parse_skips
+        args.skip = parse_skips(args.skip)  # {block: "attn" | "ffn" | "block"}
     if args.raw_shape is not None:
         if args.dtype != "uint8":
             raise ValueError("--raw_shape needs --dtype uint8")
@@ -241,6 +248,8 @@ def gpu_benchmark(argv: Optional[List[str]] = None) -> str:
         model.set_token_pruning(parse_token_keep(args.token_keep))
     if args.mask_heads:
         model.mask_heads(args.mask_heads)
+    if args.skip:
+        model.skip_sublayers(args.skip)
     u8 = args.dtype == "uint8"
     lat = latency_samples(model, uint8_shape(args.model, shape) if u8 else shape, args.num_runs,
                           args.warmup_runs, args.io_binding, graph=args.graph, uint8=u8,
@@ -250,6 +259,8 @@ def gpu_benchmark(argv: Optional[List[str]] = None) -> str:
     name += f"_tokens{args.token_keep}" if args.token_keep else ""
     if args.mask_heads:
         name += "_mask" + ",".join(f"{b}:{h}" for b, hs in args.mask_heads.items() for h in hs)
+    if args.skip:
+        name += "_skip" + ",".join(f"{b}:{w}" for b, w in args.skip.items())
     line = format_line(name, avg, std, args.precision)
     print(line, flush=True)
     return line

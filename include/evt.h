@@ -522,6 +522,7 @@ int evt_model_qkv_layout(const evt_model* m, int* headmajor_layers);
 #include "evt_rollout.h"  /* evt_forward_rollout, evt_rollout_shape, evt_rollout_scratch_bytes, evt_attention_rollout_step */
 #include "evt_token_pruning.h"  /* evt_model_set_token_schedule, evt_forward_token_pruning, evt_token_scores / _select / _gather */
 #include "evt_gates.h"  /* evt_model_set_head_gates / _ffn_gates, evt_model_clear_gates, evt_model_get_*_gates, evt_gate_weights */
+#include "evt_depth.h"  /* evt_forward_block_stats, evt_block_stats_shape, evt_stream_delta_stats, evt_model_set_skips / _get_skips */
 #include "evt_window_attention.h"  /* evt_forward_window_attention, evt_window_attn_map_shape, evt_window_attention_probs */
 #include "evt_classify.h"  /* evt_classify, evt_forward_classify */
 #include "evt_tail.h"      /* evt_model_tail_mode (the encoder's CLS tail) */
