@@ -23,7 +23,7 @@ SOURCES = ["gemm.hip", "attention.hip", "norm.hip", "t2t.hip", "swin.hip", "mx8.
 GEMM_HEADERS = ["gemm_epi.h", "gemm_nt.h", "gemm_big8.h", "gemm_big.h", "gemm_pers.h",
                 "gemm_p384.h", "gemm_sk.h"]
 HEADERS = GEMM_HEADERS + [
-           "common.h", "evt_internal.h", "model.h", "attn_scores.h",
+           "common.h", "evt_internal.h", "model.h", "attn_scores.h", "window_scores.h",
            os.path.join("..", "..", "include", "evt.h"),
            os.path.join("..", "..", "include", "evt_patchify.h"),
            os.path.join("..", "..", "include", "evt_features.h"),

@@ -57,6 +57,7 @@
 #include "attn_scores.h"
 #include "common.h"
 #include "evt_internal.h"
+#include "window_scores.h"
 
 namespace evt {
 
@@ -468,7 +469,7 @@ hipError_t head_mean_launch(int dtype, const AttnParams& p_in, float* out, hipSt
 //
 // of the q and k rows the block's QKV GEMM stored in raster order: what the window kernels of
 // swin.hip form in registers, multiply by V and discard. q, k: window-local tokens of the SHIFTED
-// frame, row-major inside the window (swin.hip WinGeom::row); win: row-major over that frame's
+// frame, row-major inside the window (window_scores.h WinGeom::row); win: row-major over that frame's
 // windows; N = w * w tokens per window, head size 32. A pair in different SW-MSA regions gets a
 // -inf score, so exactly 0.0f (the reference's additive -100 leaves at most e^-100 of relative
 // weight, below fp32 resolution); a query shares a region with itself, so no row is empty and the
@@ -478,8 +479,10 @@ hipError_t head_mean_launch(int dtype, const AttnParams& p_in, float* out, hipSt
 //
 // The bias comes from the head's compact table (rpb_compact_table: entry r = table[r][h] log2 e),
 // bias(q, k) = T[(2w - 1)(qi - ki + w - 1) + (qj - kj + w - 1)], copied to LDS; the regions are
-// worked out on the VALU as in swin.hip (region bit 0: rows >= w - shift of a window of the last
-// window row, bit 1: the same for columns). There is no V, no LDS V tile and no P . V.
+// worked out on the VALU (region bit 0: rows >= w - shift of a window of the last window row,
+// bit 1: the same for columns). Geometry, constants and key tables are window_scores.h's, the
+// definitions the forward kernels of swin.hip use; the score loop, the reductions, the division
+// and the stores below are this kernel's own. There is no V, no LDS V tile and no P . V.
 //
 // bf16 (window_probs_bf16_kernel<w>): the geometry of window_attn_bf16_kernel (w = 7: four waves
 // per block, a wave per (image, window, head), four 16-token tiles of which keys 49 .. 63 never
@@ -505,17 +508,17 @@ hipError_t head_mean_launch(int dtype, const AttnParams& p_in, float* out, hipSt
 namespace {
 
 constexpr int wp_prow(int w) { return w == 7 ? 49 : 148; }  // LDS tile row (148: b128 conflict-free)
-constexpr int wp_tl(int w) { return w == 7 ? 192 : 576; }   // LDS floats of a table copy
 
 template <int W, bool WIDE>
 __global__ __launch_bounds__(W == 7 ? 256 : 192) void window_probs_bf16_kernel(
     SwinAttnParams p, const float* __restrict__ table, int trow, float* __restrict__ out) {
-  constexpr int N = W * W, NKT = (N + 15) / 16, TW = 2 * W - 1;
+  using T = WinTraits<W>;
+  constexpr int N = T::N, NKT = T::NKT;
   constexpr int PW = W == 7 ? 1 : 3;  // waves per (image, window, head)
   constexpr int PB = W == 7 ? 4 : 1;  // (image, window, head) per block
   constexpr int QTW = NKT / PW;       // query tiles per wave
-  constexpr int PROW = wp_prow(W), PT = 16 * PROW, TL = wp_tl(W);
-  static_assert(NKT % PW == 0 && TW * TW <= TL && PT % 4 == 0 && (!WIDE || N % 4 == 0), "geometry");
+  constexpr int PROW = wp_prow(W), PT = 16 * PROW, TL = T::CROW;  // TL: LDS floats of a table copy
+  static_assert(NKT % PW == 0 && PT % 4 == 0 && (!WIDE || N % 4 == 0), "geometry");
   __shared__ __attribute__((aligned(16))) float smem[PB * PW * (PT + TL)];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // uniform: scalar index math
@@ -525,67 +528,49 @@ __global__ __launch_bounds__(W == 7 ? 256 : 192) void window_probs_bf16_kernel(
   const int h = pair % p.H;
   const int bw = pair / p.H;
   const int win = bw % nw, b = bw / nw;
-  const int R = p.R, s0 = p.shift;
-  const int wy = win / p.nwx, wx = win - wy * p.nwx;
-  const int y0 = wy * W + s0, x0 = wx * W + s0;
-  const bool lr_ = s0 && wy == p.nwx - 1, lc_ = s0 && wx == p.nwx - 1;  // last window row / column
-  const int cut = W - s0;
-  // image-local raster row of window token t (with the cyclic shift)
-  auto lrow = [&](int t) {
-    const int i = t / W, j = t - W * i;
-    int y = y0 + i, x = x0 + j;
-    if (y >= R) y -= R;
-    if (x >= R) x -= R;
-    return y * R + x;
-  };
+  const int R = p.R;
+  const WinGeom<W> G(R, p.nwx, p.shift, win);
   const int ldq2 = (int)p.ldq * 2, C2 = p.C * 2;
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
       (char*)const_cast<void*>(p.qkv) + (int64_t)b * R * R * ldq2, 0, R * R * ldq2, 0x00020000);
   EVT_LDS float* Ps = (EVT_LDS float*)smem + wave * (PT + TL);  // this wave's [16 queries][PROW]
   EVT_LDS float* Ts = Ps + PT;                                  // and its copy of the head's table
-  for (int e = lane; e < TW * TW; e += 64) Ts[e] = table[(int64_t)h * trow + e];
+  for (int e = lane; e < T::TW * T::TW; e += 64) Ts[e] = table[(int64_t)h * trow + e];
   // K fragments of every tile, Q fragments of this wave's: tile i, lane (token 16 i + c16,
   // d 8 g .. 8 g + 7); tokens past N - 1 (w = 7) repeat token N - 1 and are masked below
   const int g = lane >> 4, c16 = lane & 15;
   u32x4 kf[NKT], qf[QTW];
 #pragma unroll
   for (int i = 0; i < NKT; ++i) {
-    const int vo = lrow(min(16 * i + c16, N - 1)) * ldq2 + (h * 32 + 8 * g) * 2;
+    const int vo = G.row(T::clamp(16 * i + c16)) * ldq2 + (h * 32 + 8 * g) * 2;
     kf[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, C2, 0));
   }
 #pragma unroll
   for (int n = 0; n < QTW; ++n) {
-    const int vo = lrow(min(16 * (pw * QTW + n) + c16, N - 1)) * ldq2 + (h * 32 + 8 * g) * 2;
+    const int vo = G.row(T::clamp(16 * (pw * QTW + n) + c16)) * ldq2 + (h * 32 + 8 * g) * 2;
     qf[n] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, 0, 0));
   }
   // per-lane table offsets of its keys k = 16 kt + 4 g + j and their region codes, a byte per j
   int kofs[NKT][4];
   unsigned kc[NKT];
-#pragma unroll
-  for (int kt = 0; kt < NKT; ++kt) {
-    kc[kt] = 0u;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int k = min(16 * kt + 4 * g + j, N - 1), ki = k / W, kj = k - W * ki;
-      kofs[kt][j] = TW * ki + kj;
-      kc[kt] |= (unsigned)((lr_ && ki >= cut ? 1 : 0) | (lc_ && kj >= cut ? 2 : 0)) << (8 * j);
-    }
-  }
+  key_tables<W>(G, g, kofs, kc);
   // the table copy is this wave's alone: LDS operations of a wave complete in order
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
   const int64_t obase = (int64_t)pair * N * N;  // element offset of the (image, window, head)
-  const float NEG = -INFINITY;
 #pragma unroll
   for (int n = 0; n < QTW; ++n) {
     const int qt = pw * QTW + n;
-    const int q = min(16 * qt + c16, N - 1), qi = q / W, qj = q - W * qi;
-    const EVT_LDS float* Tq = Ts + (TW * (qi + W - 1) + qj + W - 1);
-    const unsigned cq = ((lr_ && qi >= cut ? 1u : 0u) | (lc_ && qj >= cut ? 2u : 0u)) * 0x01010101u;
-    // s[kt][j] = S^T[key 16 kt + 4 g + j][query q], in the log2 domain, + bias, then the masks
+    const int q = T::clamp(16 * qt + c16), qi = T::div(q);
+    const EVT_LDS float* Tq = Ts + T::a(qi, q);
+    const unsigned cq = G.code(qi, q - W * qi) * 0x01010101u;
+    // s[kt][j] = S^T[key 16 kt + 4 g + j][query q], in the log2 domain, + bias, then the masks.
+    // Not window_scores.h's score_tile: with it this kernel measured 7 to 9 % slower at w = 7
+    // (profiles/window_core_speed.json), so the step keeps the form it was tuned in
     f32x4 s[NKT];
+    const float NEG = -INFINITY;
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
       const f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -653,7 +638,8 @@ __global__ __launch_bounds__(W == 7 ? 256 : 192) void window_probs_bf16_kernel(
 template <int W>
 __global__ __launch_bounds__(W == 7 ? 64 : 192) void window_probs_f32_kernel(
     SwinAttnParams p, const float* __restrict__ table, int trow, float* __restrict__ out) {
-  constexpr int N = W * W, NT = W == 7 ? 64 : 192, TW = 2 * W - 1;
+  using T = WinTraits<W>;
+  constexpr int N = T::N, NT = W == 7 ? 64 : 192, TW = T::TW;
   constexpr int PR = N % 2 ? N : N + 1;  // row stride of the P tile: odd, so conflict-free
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* Ks = (float*)smem;  // [N][33]
@@ -665,39 +651,28 @@ __global__ __launch_bounds__(W == 7 ? 64 : 192) void window_probs_f32_kernel(
   const int h = (int)(pair % p.H);
   const int64_t bw = pair / p.H;
   const int win = (int)(bw % nw), b = (int)(bw / nw);
-  const int R = p.R, s0 = p.shift;
-  const int wy = win / p.nwx, wx = win - wy * p.nwx;
-  const bool lr_ = s0 && wy == p.nwx - 1, lc_ = s0 && wx == p.nwx - 1;
-  const int cut = W - s0;
-  const int64_t base = (int64_t)b * R * R;
-  auto row = [&](int t) {
-    const int i = t / W, j = t - W * i;
-    int y = wy * W + s0 + i, x = wx * W + s0 + j;
-    if (y >= R) y -= R;
-    if (x >= R) x -= R;
-    return base + (y * R + x);
-  };
+  const WinGeom<W> G(p.R, p.nwx, p.shift, win);
+  const int64_t base = (int64_t)b * p.R * p.R;
   const float* qkv = (const float*)p.qkv;
   for (int e = tid; e < N * 32; e += NT) {
     const int t = e >> 5, d = e & 31;
-    Ks[t * 33 + d] = qkv[row(t) * p.ldq + p.C + h * 32 + d];
+    Ks[t * 33 + d] = qkv[(base + G.row(t)) * p.ldq + p.C + h * 32 + d];
   }
   for (int e = tid; e < TW * TW; e += NT) Ts[e] = table[(int64_t)h * trow + e];
   __syncthreads();
   if (tid < N) {
     const int t = tid, qi = t / W, qj = t - W * qi;
-    const int64_t qrow = row(t);
+    const int64_t qrow = base + G.row(t);
     float q[32];
 #pragma unroll
     for (int d = 0; d < 32; ++d) q[d] = qkv[qrow * p.ldq + h * 32 + d];
-    const int cq = (lr_ && qi >= cut ? 1 : 0) | (lc_ && qj >= cut ? 2 : 0);
-    const float* Tq = Ts + (TW * (qi + W - 1) + qj + W - 1);
+    const unsigned cq = G.code(qi, qj);
+    const float* Tq = Ts + T::a(qi, t);
     auto score = [&](int k, int ki, int kj) {
       float a = 0.f;
 #pragma unroll
       for (int d = 0; d < 32; ++d) a += q[d] * Ks[k * 33 + d];
-      const int ck = (lr_ && ki >= cut ? 1 : 0) | (lc_ && kj >= cut ? 2 : 0);
-      return ck != cq ? -INFINITY : a * p.scale_log2 + Tq[-(TW * ki + kj)];
+      return G.code(ki, kj) != cq ? -INFINITY : a * p.scale_log2 + Tq[-T::b(ki, k)];
     };
     float mx = -INFINITY;
 #pragma unroll 1
@@ -724,7 +699,7 @@ __global__ __launch_bounds__(W == 7 ? 64 : 192) void window_probs_f32_kernel(
 
 template <int W>
 constexpr size_t wp_f32_lds() {
-  constexpr int N = W * W, TW = 2 * W - 1;
+  constexpr int N = WinTraits<W>::N, TW = WinTraits<W>::TW;
   return (size_t)(N * 33 + TW * TW + N * (N % 2 ? N : N + 1)) * sizeof(float);
 }
 

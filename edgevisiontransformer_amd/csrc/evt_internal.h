@@ -333,15 +333,14 @@ hipError_t merge_launch(int dtype, const void* x, int64_t ldx, int B, int R, int
 size_t rpb_table_floats(int H, int w, int shift);
 hipError_t rpb_dense_launch(const float* table, int H, int w, int shift, float* dense,
                             hipStream_t s);
-hipError_t window_attn_launch(int dtype, const SwinAttnParams& p, hipStream_t s);    // w = 7
-hipError_t window12_attn_launch(int dtype, const SwinAttnParams& p, hipStream_t s);  // w = 12
+hipError_t window_attn_launch(int dtype, int w, const SwinAttnParams& p, hipStream_t s);  // w 7 / 12
 // The compact per-head relative-position table among the tables rpb_dense_launch wrote for
 // (H, w, shift): *row floats per head, entry r = table[r][h] * log2(e) for r < (2w - 1)^2
 const float* rpb_compact_table(const float* tables, int H, int w, int shift, int* row);
 // Window attention maps (attn_maps.hip; include/evt_window_attention.h): out[b][win][h][q][k] =
 // softmax_k(q_q . k_k 32^-0.5 + rpb[rel(q, k)][h] + mask(win, q, k)) as fp32, contiguous
 // [B][(R/w)^2][H][w*w][w*w], exactly 0 where q and k lie in different SW-MSA regions. p as
-// window_attn_launch / window12_attn_launch (out and ldo unused, bias = the block's
+// window_attn_launch (out and ldo unused, bias = the block's
 // rpb_dense_launch tables); w 7 or 12, out 16-byte aligned (hipErrorInvalidValue otherwise).
 hipError_t window_probs_launch(int dtype, int w, const SwinAttnParams& p, float* out,
                                hipStream_t s);

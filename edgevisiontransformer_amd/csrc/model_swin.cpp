@@ -271,7 +271,7 @@ int swin_run(evt_model* m, ForwardCall& call) {
         {
           ProfScope ps(m, EVT_PROF_ATTENTION, s);
           prof_work(m, 4.0 * rows * st.w * st.w * C, 4.0 * rows * C * es);  // w^2 keys per query
-          EVT_HIP(st.w == 12 ? window12_attn_launch(dt, ap, s) : window_attn_launch(dt, ap, s),
+          EVT_HIP(window_attn_launch(dt, st.w, ap, s),
                   "window attention");
         }
         EVT_RC(window_attn_map(m, call, block, st.w, ap));  // ws.qkv still holds the block

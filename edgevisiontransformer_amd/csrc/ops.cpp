@@ -350,7 +350,7 @@ int evt_window_attention(int dtype, const void* qkv, int64_t ldq, void* out, int
   EVT_HIP(rpb_dense_launch(rpb, H, 7, shift, dense_bias, s), "relative position bias");
   SwinAttnParams ap{qkv, ldq, out, ldo, dense_bias, B, R, R / 7, C, H, shift,
                     0.17677669529663687f * 1.4426950408889634f};
-  const hipError_t e = window_attn_launch(dtype, ap, s);
+  const hipError_t e = window_attn_launch(dtype, 7, ap, s);
   (void)hipFreeAsync(dense_bias, s);
   EVT_HIP(e, "window attention");
   return EVT_OK;

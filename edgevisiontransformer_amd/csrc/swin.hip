@@ -14,18 +14,25 @@
 //   merge_kernel         PatchMerging gather x[0::2,0::2] | x[1::2,0::2] | x[0::2,1::2] |
 //                        x[1::2,1::2] -> [B*(R/2)^2][4C] + row statistics (its LayerNorm is folded
 //                        into the reduction GEMM)
-//   window_attn_bf16     one wave per (window, head): S^T = K Q^T and O^T = V^T P^T on
-//                        v_mfma_f32_16x16x32_bf16 (head size 32 = one MFMA k-step), + relative
-//                        position bias + SW-MSA mask (one precomputed table per window type),
-//                        exact softmax
-//   window_attn_f32      the exact fp32 parity path (VALU dot products, K / V in LDS)
-//   window12_attn_bf16 / _f32   the same for 12 x 12 windows (the 384 px configurations): block =
-//                        3 waves = one (image, window, head); the window-7 kernels are 7-specific
+//   window_attn_bf16<W>  S^T = K Q^T and O^T = V^T P^T on v_mfma_f32_16x16x32_bf16 (head size 32 =
+//                        one MFMA k-step), + relative position bias from the head's compact table
+//                        + SW-MSA region mask, exact softmax; one template, two entries:
+//                        window_attn_bf16_kernel (w = 7: a wave per (image, window, head), four
+//                        per block) and window12_attn_bf16_kernel (w = 12, the 384 px
+//                        configurations: block = 3 waves = one (image, window, head))
+//   window_attn_f32 / window12_attn_f32   the exact fp32 parity paths (VALU dot products, K / V in
+//                        LDS; w = 7 reads the dense bias + mask table, w = 12 the compact one)
+//   swin_attn96_kernel   the fused attention sublayer of a C = 96 stage (phase P2 = the same core)
 //   ln_pool_kernel       final LayerNorm + mean over tokens (AdaptiveAvgPool1d) -> [B][Cst]
+//
+// The window geometry (shifted rows, window type, region codes), the per-W constants, the key
+// tables, the score step, the softmax statistics and P . V live once in window_scores.h; this file
+// holds what is each kernel's own: loads, LDS layout, stores and the launchers.
 #include <algorithm>
 
 #include "common.h"
 #include "evt_internal.h"
+#include "window_scores.h"
 
 namespace evt {
 
@@ -271,7 +278,7 @@ __global__ void rpb_dense_kernel(const float* __restrict__ table, int H, int w, 
 
 // Compact relative-position table per head (the bf16 window kernel's bias source): RPB_CROW
 // floats per head, entries 0 .. 168 = table[r][h] * log2(e), stored after the dense tables.
-constexpr int RPB_CROW = 192;
+constexpr int RPB_CROW = WinTraits<7>::CROW;  // 192
 __host__ __device__ __forceinline__ const float* rpb_compact(const float* dense, int H, int shift) {
   return dense + (size_t)(shift ? 4 : 1) * H * 49 * 64;
 }
@@ -280,50 +287,6 @@ __global__ void rpb_compact_kernel(const float* __restrict__ table, int H, float
   if (e >= H * RPB_CROW) return;
   const int h = e / RPB_CROW, r = e - h * RPB_CROW;
   out[e] = r < 169 ? table[r * H + h] * kLog2e : 0.f;
-}
-
-// Row of window-local token t (t < 49) of window `win` of image b, with the cyclic shift; and
-// the bias / mask table type of the window.
-struct WinGeom {
-  int R, s;
-  int y0, x0;       // shifted-frame origin of the window (wy * 7 + s, wx * 7 + s)
-  int64_t base;     // first token row of the image
-  int wtype;        // bias / mask table type (rpb_dense_kernel): last window row / column
-  __device__ __forceinline__ WinGeom(int R_, int nwx, int s_, int b, int win) : R(R_), s(s_) {
-    const int wy = win / nwx, wx = win - wy * nwx;
-    y0 = wy * 7 + s;
-    x0 = wx * 7 + s;
-    base = (int64_t)b * R * R;
-    wtype = s ? (wy == nwx - 1 ? 2 : 0) + (wx == nwx - 1 ? 1 : 0) : 0;
-  }
-  __device__ __forceinline__ int64_t row(int t) const {
-    const int i = t / 7, j = t - i * 7;
-    int y = y0 + i, x = x0 + j;
-    if (y >= R) y -= R;
-    if (x >= R) x -= R;
-    return base + (y * R + x);
-  }
-  __device__ __forceinline__ int type() const { return wtype; }
-};
-
-// Butterfly max / sum over lanes l ^ 16 and l ^ 32 on the VALU: v_permlane16_swap / 32_swap of a
-// value with itself leave the two halves of each row pair (of the wave) in the two results, so one
-// max / add gives every lane the reduction (no LDS round trip as with ds_bpermute).
-__device__ __forceinline__ float bfly_max_16_32(float x) {
-  unsigned u = __builtin_bit_cast(unsigned, x);
-  const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  x = fmaxf(__builtin_bit_cast(float, (unsigned)a[0]), __builtin_bit_cast(float, (unsigned)a[1]));
-  u = __builtin_bit_cast(unsigned, x);
-  const auto c = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return fmaxf(__builtin_bit_cast(float, (unsigned)c[0]), __builtin_bit_cast(float, (unsigned)c[1]));
-}
-__device__ __forceinline__ float bfly_sum_16_32(float x) {
-  unsigned u = __builtin_bit_cast(unsigned, x);
-  const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  x = __builtin_bit_cast(float, (unsigned)a[0]) + __builtin_bit_cast(float, (unsigned)a[1]);
-  u = __builtin_bit_cast(unsigned, x);
-  const auto c = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __builtin_bit_cast(float, (unsigned)c[0]) + __builtin_bit_cast(float, (unsigned)c[1]);
 }
 
 // bf16 window attention. 4 waves per block, wave = one (image, window, head); head size 32,
@@ -340,169 +303,119 @@ __device__ __forceinline__ float bfly_sum_16_32(float x) {
 // texture-address unit was busy 75 % of the kernel, half of that stalled on the L1, and the
 // kernel without its dense-table bias reads (16 x 16 B per lane per wave, L2 hits) ran 25 %
 // faster: those reads are gone; the VALU butterflies and v_rcp_f32 cut its VALU count by 29 %.
-__global__ __launch_bounds__(256) void window_attn_bf16_kernel(SwinAttnParams p) {
-  __shared__ __attribute__((aligned(16))) char smem[4 * 64 * 64 + 4 * 768];
+//
+// One body for both window sizes (the w = 12 kernel's own account is at its entry below); what
+// differs is a compile-time property of W: PW waves share one (image, window, head) and split its
+// query tiles, a block holds PB of them, and only a shared V tile / table needs the block barrier.
+template <int W>
+struct WinFwd {
+  static constexpr int PW = W == 7 ? 1 : 3;  // waves per (image, window, head)
+  static constexpr int PB = W == 7 ? 4 : 1;  // (image, window, head) per block
+  static constexpr int QTW = WinTraits<W>::NKT / PW;  // query tiles per wave
+  static constexpr int VT = WinTraits<W>::VROWS / 16;  // 16-row LDS-DMA instructions of a V tile
+  static constexpr int TC = WinTraits<W>::CROW / 64;   // 64-float ones of a table
+  static constexpr int LDS = PB * (WinTraits<W>::VROWS * 64 + WinTraits<W>::CROW * 4);
+  static_assert((PW == 1 || PB == 1) && WinTraits<W>::NKT % PW == 0 && TC % PW == 0, "geometry");
+};
+
+template <int W>
+__device__ __forceinline__ void window_attn_bf16(const SwinAttnParams& p) {
+  using T = WinTraits<W>;
+  using F = WinFwd<W>;
+  constexpr int N = T::N, NKT = T::NKT;
+  __shared__ __attribute__((aligned(16))) char smem[F::LDS];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // uniform: scalar index math
-  const int pair = blockIdx.x * 4 + wave;  // (B * windows * H < 2^31: checked at launch)
+  const int pb = F::PW == 1 ? wave : 0, pw = F::PW == 1 ? 0 : wave;
+  const int pair = blockIdx.x * F::PB + pb;  // (B * windows * H < 2^31: checked at launch)
   const int nw = p.nwx * p.nwx;
-  if (pair >= p.B * nw * p.H) return;
+  if constexpr (F::PB > 1)
+    if (pair >= p.B * nw * p.H) return;  // wave-uniform; no block barrier in this form
   const int h = pair % p.H;
   const int bw = pair / p.H;
   const int win = bw % nw, b = bw / nw;
-  const int R = p.R, s0 = p.shift;
-  const int wy = win / p.nwx, wx = win - wy * p.nwx;
-  const int y0 = wy * 7 + s0, x0 = wx * 7 + s0;
-  const int wtype = s0 ? (wy == p.nwx - 1 ? 2 : 0) + (wx == p.nwx - 1 ? 1 : 0) : 0;
-  // image-local raster row of window token t (with the cyclic shift)
-  auto lrow = [&](int t) {
-    const int i = (t * 37) >> 8, j = t - 7 * i;  // t / 7 for t < 64
-    int y = y0 + i, x = x0 + j;
-    if (y >= R) y -= R;
-    if (x >= R) x -= R;
-    return y * R + x;
-  };
+  const int R = p.R;
+  const WinGeom<W> G(R, p.nwx, p.shift, win);
   const int ldq2 = (int)p.ldq * 2, ldo2 = (int)p.ldo * 2;
   const int64_t img0 = (int64_t)b * R * R;
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
       (char*)const_cast<void*>(p.qkv) + img0 * ldq2, 0, R * R * ldq2, 0x00020000);
   const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
       (char*)p.out + img0 * ldo2, 0, R * R * ldo2, 0x00020000);
+  const float* tables = W == 7 ? rpb_compact(p.bias, p.H, p.shift) : p.bias;
   const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(rpb_compact(p.bias, p.H, s0)) + h * RPB_CROW, 0, RPB_CROW * 4, 0x00020000);
+      const_cast<float*>(tables) + h * T::CROW, 0, T::CROW * 4, 0x00020000);
   const int g = lane >> 4, c16 = lane & 15;
-  EVT_LDS char* Vs = (EVT_LDS char*)smem + wave * 4096;
-  EVT_LDS char* Ts = (EVT_LDS char*)smem + 4 * 4096 + wave * 768;
+  EVT_LDS char* Vs = (EVT_LDS char*)smem + pb * (T::VROWS * 64);
+  EVT_LDS char* Ts = (EVT_LDS char*)smem + F::PB * (T::VROWS * 64) + pb * (T::CROW * 4);
   const int C2 = p.C * 2;
 
-  // the head's compact bias table -> LDS (3 x 64 lanes x 4 B)
+  // the head's compact bias table -> LDS (64 lanes x 4 B per instruction, shared out over PW)
 #pragma unroll
-  for (int i = 0; i < 3; ++i)
+  for (int n = 0; n < F::TC / F::PW; ++n) {
+    const int i = pw + F::PW * n;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rt, Ts + i * 256, 4, lane * 4, i * 256, 0, 0);
-  // V rows (keys) -> LDS: instruction i covers rows 16 i + (lane >> 2), 16-B chunk lane & 3
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = 16 * i + (lane >> 2), ch = (lane & 3) ^ ((r >> 2) & 3);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, Vs + i * 1024, 16,
-                                             lrow(min(r, 48)) * ldq2 + (h * 32 + ch * 8) * 2,
-                                             2 * C2, 0, 0);
   }
-  // Q and K fragments: tile i, lane (token 16 i + c16, d 8 g .. 8 g + 7)
-  u32x4 qf[4], kf[4];
-  int qoff[4];
+  // V rows (keys) -> LDS: instruction i covers rows 16 i + (lane >> 2), 16-B chunk lane & 3; rows
+  // past N - 1 (P = 0 or masked there) repeat key N - 1 so that the products are 0, not NaN
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int t = min(16 * i + c16, 48);
-    const int lr = lrow(t);
-    qoff[i] = lr * ldo2 + (h * 32 + 4 * g) * 2;  // query token t's output row, this lane's columns
-    const int vo = lr * ldq2 + (h * 32 + 8 * g) * 2;
-    qf[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, 0, 0));
+  for (int n = 0; n < (F::VT + F::PW - 1) / F::PW; ++n) {
+    const int i = pw + F::PW * n;
+    if (i < F::VT) {
+      const int r = 16 * i + (lane >> 2), ch = (lane & 3) ^ ((r >> 2) & 3);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, Vs + i * 1024, 16,
+                                               G.row(min(r, N - 1)) * ldq2 + (h * 32 + ch * 8) * 2,
+                                               2 * C2, 0, 0);
+    }
+  }
+  // K fragments of every tile, Q fragments of this wave's: tile i, lane (token 16 i + c16,
+  // d 8 g .. 8 g + 7) (each of PW waves loads all K tiles: the repeats hit the L1 / L2)
+  u32x4 qf[F::QTW], kf[NKT];
+  int qoff[F::QTW];
+#pragma unroll
+  for (int i = 0; i < NKT; ++i) {
+    const int vo = G.row(T::clamp(16 * i + c16)) * ldq2 + (h * 32 + 8 * g) * 2;
     kf[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, C2, 0));
   }
-  // per-lane table offsets b(k) of its 16 keys k = 16 kt + 4 g + j (keys past 48 read key 48's:
-  // masked below) and, for SW-MSA windows, their region codes (bit 0: lower part of the last
-  // window row, bit 1: right part of the last window column), one byte per j
-  int kofs[4][4];
-  unsigned kc[4] = {0u, 0u, 0u, 0u};
-  const int cut = 7 - s0;
-  const bool lr_ = wtype & 2, lc_ = wtype & 1;
 #pragma unroll
-  for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int k = min(16 * kt + 4 * g + j, 48), ki = (k * 37) >> 8, kj = k - 7 * ki;
-      kofs[kt][j] = (6 * ki + k) * 4;
-      kc[kt] |= (unsigned)((lr_ && ki >= cut ? 1 : 0) | (lc_ && kj >= cut ? 2 : 0)) << (8 * j);
-    }
-  wait_vmcnt0();
+  for (int n = 0; n < F::QTW; ++n) {
+    const int lr = G.row(T::clamp(16 * (pw * F::QTW + n) + c16));
+    qoff[n] = lr * ldo2 + (h * 32 + 4 * g) * 2;  // the query's output row, this lane's columns
+    qf[n] = __builtin_bit_cast(
+        u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lr * ldq2 + (h * 32 + 8 * g) * 2, 0, 0));
+  }
+  int kofs[NKT][4];
+  unsigned kc[NKT];
+  key_tables<W>(G, g, kofs, kc);
+  wait_vmcnt0();  // this wave's LDS-DMA has landed ...
+  if constexpr (F::PW > 1) __syncthreads();  // ... and so has the other waves'
 
-  const int tq = (lane >> 2) & 3, tp = lane & 3;
-  const float NEG = -INFINITY;
 #pragma unroll
-  for (int qt = 0; qt < 4; ++qt) {
-    const int q = 16 * qt + c16;
-    const int qq = min(q, 48), qi = (qq * 37) >> 8, qj = qq - 7 * qi;
-    const EVT_LDS char* Tq = Ts + (6 * qi + qq + 84) * 4;
-    const unsigned cq = ((lr_ && qi >= cut ? 1u : 0u) | (lc_ && qj >= cut ? 2u : 0u)) * 0x01010101u;
-    f32x4 s[4];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf[kt]),
-                                                      __builtin_bit_cast(bf16x8, qf[qt]), acc, 0,
-                                                      0, 0);
-    }
-    // s[kt][j] = S^T[key 16 kt + 4 g + j][query q]: scores in the log2 domain + bias on packed
-    // pairs, then the masks
-    const f32x2 sc2 = {p.scale_log2, p.scale_log2};
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-      f32x4 bv;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bv[j] = *(const EVT_LDS float*)(Tq - kofs[kt][j]);
-      const f32x2 lo = f32x2{s[kt][0], s[kt][1]} * sc2 + f32x2{bv[0], bv[1]};
-      const f32x2 hi = f32x2{s[kt][2], s[kt][3]} * sc2 + f32x2{bv[2], bv[3]};
-      s[kt] = f32x4{lo[0], lo[1], hi[0], hi[1]};
-      if (wtype) {  // SW-MSA window on the last row / column: keys of another region
-        const unsigned x = kc[kt] ^ cq;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if ((x >> (8 * j)) & 3u) s[kt][j] = NEG;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)  // keys 49 .. 63 (the padding of tile 3: all but key 48)
-      if (4 * g + j > 0) s[3][j] = NEG;
-    float m4[4];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) m4[kt] = fmaxf(fmaxf(s[kt][0], s[kt][1]), fmaxf(s[kt][2], s[kt][3]));
-    const float mx = bfly_max_16_32(fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3])));
-    float p4[4];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s[kt][j] = __builtin_amdgcn_exp2f(s[kt][j] - mx);
-      p4[kt] = (s[kt][0] + s[kt][1]) + (s[kt][2] + s[kt][3]);
-    }
-    const float sum = bfly_sum_16_32((p4[0] + p4[1]) + (p4[2] + p4[3]));
-
+  for (int n = 0; n < F::QTW; ++n) {
+    const int q = 16 * (pw * F::QTW + n) + c16;
+    f32x4 s[NKT];
+    score_tile<W>(G, kf, qf[n], T::clamp(q), g, Ts, p.scale_log2, kofs, kc, s);
+    const float sum = softmax_exp<W>(s);
     f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 pf;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        pf[j] = (bf16)s[2 * ks][j];
-        pf[4 + j] = (bf16)s[2 * ks + 1][j];
-      }
-      const int key0 = ks * 32 + 4 * g + tq;  // and key0 + 16: same (row >> 2) & 3 swizzle
-      const int sw = (key0 >> 2) & 3;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        const int chunk = 2 * dt + (tp >> 1);
-        const int off = ((chunk ^ sw) * 16) + (tp & 1) * 8;
-        const i16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((EVT_LDS i16x4*)(Vs + key0 * 64 + off));
-        const i16x4 v1 =
-            __builtin_amdgcn_ds_read_tr16_b64_v4i16((EVT_LDS i16x4*)(Vs + (key0 + 16) * 64 + off));
-        const i16x8 vv = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vv), pf, o[dt],
-                                                        0, 0, 0);
-      }
-    }
+    pv_accumulate<W, 64, true>(s, Vs, lane, o);
     // o[dt][j] = O^T[d = 16 dt + 4 g + j][query q]
-    if (q < 49) {
+    if (N % 16 == 0 || q < N) {
       const float inv = __builtin_amdgcn_rcpf(sum);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
         const f32x4 v = o[dt] * inv;
         const bf16x4 ob = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-        buffer_store_b64<0>(__builtin_bit_cast(u32x2, ob), ro, qoff[qt], 32 * dt);
+        buffer_store_b64<0>(__builtin_bit_cast(u32x2, ob), ro, qoff[n], 32 * dt);
       }
       if (h == 0)  // pad columns [C, ldo) of the attention output (the proj GEMM's K padding)
         for (int c = p.C + 4 * g; c < p.ldo; c += 16)
-          buffer_store_b64<0>(u32x2{0u, 0u}, ro, qoff[qt] + (c - 4 * g) * 2, 0);
+          buffer_store_b64<0>(u32x2{0u, 0u}, ro, qoff[n] + (c - 4 * g) * 2, 0);
     }
   }
+}
+
+__global__ __launch_bounds__(256) void window_attn_bf16_kernel(SwinAttnParams p) {
+  window_attn_bf16<7>(p);
 }
 
 // fp32 window attention (parity path): wave = (image, window, head), lane = query (49 of 64).
@@ -515,24 +428,25 @@ __global__ __launch_bounds__(256) void window_attn_f32_kernel(SwinAttnParams p) 
   const int h = (int)(pair % p.H);
   const int64_t bw = pair / p.H;
   const int win = (int)(bw % nw), b = (int)(bw / nw);
-  const WinGeom G(p.R, p.nwx, p.shift, b, win);
+  const WinGeom<7> G(p.R, p.nwx, p.shift, win);
+  const int64_t base = (int64_t)b * p.R * p.R;
   const float* qkv = (const float*)p.qkv;
   float(*Ks)[33] = smem[wave][0];
   float(*Vs)[33] = smem[wave][1];
   for (int e = lane; e < 49 * 32; e += 64) {
     const int t = e >> 5, d = e & 31;
-    const float* rp = qkv + G.row(t) * p.ldq + h * 32 + d;
+    const float* rp = qkv + (base + G.row(t)) * p.ldq + h * 32 + d;
     Ks[t][d] = rp[p.C];
     Vs[t][d] = rp[2 * p.C];
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // wave-private LDS: no barrier
   __builtin_amdgcn_wave_barrier();
   const int t = min(lane, 48);
-  const int64_t qrow = G.row(t);
+  const int64_t qrow = base + G.row(t);
   float q[32];
 #pragma unroll
   for (int d = 0; d < 32; ++d) q[d] = qkv[qrow * p.ldq + h * 32 + d];
-  const float* br = p.bias + (((int64_t)G.type() * p.H + h) * 49 + t) * 64;
+  const float* br = p.bias + (((int64_t)G.wtype * p.H + h) * 49 + t) * 64;
   float sc[49];
   float mx = -INFINITY;
 #pragma unroll
@@ -572,21 +486,13 @@ __global__ __launch_bounds__(256) void window_attn_f32_kernel(SwinAttnParams p) 
 // RPB12_CROW floats per head, entries 0 .. 528 = table[r][h] * log2(e), 0 after. Both w = 12
 // kernels work the SW-MSA regions out themselves, so no dense [q][k] table exists for w = 12 and
 // the w = 7 tables (and rpb_compact's offset into them) are what they were.
-constexpr int RPB12_CROW = 576;  // 9 x 64 floats
+constexpr int RPB12_CROW = WinTraits<12>::CROW;  // 576 = 9 x 64 floats
 __global__ void rpb12_kernel(const float* __restrict__ table, int H, float* __restrict__ out) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= H * RPB12_CROW) return;
   const int h = e / RPB12_CROW, r = e - h * RPB12_CROW;
   out[e] = r < 529 ? table[r * H + h] * kLog2e : 0.f;
 }
-
-constexpr int div12(int t) { return (t * 171) >> 11; }  // t / 12 for t < 160
-constexpr bool div12_exact() {
-  for (int t = 0; t < 160; ++t)
-    if (div12(t) != t / 12) return false;
-  return true;
-}
-static_assert(div12_exact(), "div12 must equal t / 12 over the padded window");
 
 // bf16 window attention for 12 x 12 windows: 144 tokens = 9 full tiles of 16, no key padding in
 // the scores. Block = 3 waves = one (image, window, head); the waves share the V tile (160 key
@@ -609,178 +515,8 @@ static_assert(div12_exact(), "div12 must equal t / 12 over the padded window");
 // the w = 7 kernel's 53 % / 104 TFLOP/s in the same run: three times the MFMA work per byte, and
 // neither HBM nor the MFMA binds - the per-score VALU / LDS work (bias read, scale, mask, exp2:
 // 144 scores per query) at 3 waves per SIMD does.
-constexpr int W12_VROWS = 160;
 __global__ __launch_bounds__(192) void window12_attn_bf16_kernel(SwinAttnParams p) {
-  __shared__ __attribute__((aligned(16))) char smem[W12_VROWS * 64 + RPB12_CROW * 4];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // uniform: scalar index math
-  const int pair = blockIdx.x;  // (B * windows * H < 2^31: checked at launch)
-  const int nw = p.nwx * p.nwx;
-  const int h = pair % p.H;
-  const int bw = pair / p.H;
-  const int win = bw % nw, b = bw / nw;
-  const int R = p.R, s0 = p.shift;
-  const int wy = win / p.nwx, wx = win - wy * p.nwx;
-  const int y0 = wy * 12 + s0, x0 = wx * 12 + s0;
-  const int wtype = s0 ? (wy == p.nwx - 1 ? 2 : 0) + (wx == p.nwx - 1 ? 1 : 0) : 0;
-  // image-local raster row of window token t (with the cyclic shift)
-  auto lrow = [&](int t) {
-    const int i = div12(t), j = t - 12 * i;
-    int y = y0 + i, x = x0 + j;
-    if (y >= R) y -= R;
-    if (x >= R) x -= R;
-    return y * R + x;
-  };
-  const int ldq2 = (int)p.ldq * 2, ldo2 = (int)p.ldo * 2;
-  const int64_t img0 = (int64_t)b * R * R;
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-      (char*)const_cast<void*>(p.qkv) + img0 * ldq2, 0, R * R * ldq2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-      (char*)p.out + img0 * ldo2, 0, R * R * ldo2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(p.bias) + h * RPB12_CROW, 0, RPB12_CROW * 4, 0x00020000);
-  const int g = lane >> 4, c16 = lane & 15;
-  EVT_LDS char* Vs = (EVT_LDS char*)smem;
-  EVT_LDS char* Ts = (EVT_LDS char*)smem + W12_VROWS * 64;
-  const int C2 = p.C * 2;
-
-  // the head's compact bias table -> LDS (9 x 64 lanes x 4 B, three per wave)
-#pragma unroll
-  for (int n = 0; n < 3; ++n) {
-    const int i = wave + 3 * n;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rt, Ts + i * 256, 4, lane * 4, i * 256, 0, 0);
-  }
-  // V rows (keys) -> LDS: instruction i covers rows 16 i + (lane >> 2), 16-B chunk lane & 3;
-  // i = 9 (rows 144 .. 159, P = 0 there) repeats key 143 so that the products are 0, not NaN
-#pragma unroll
-  for (int n = 0; n < 4; ++n) {
-    const int i = wave + 3 * n;
-    if (i < W12_VROWS / 16) {
-      const int r = 16 * i + (lane >> 2), ch = (lane & 3) ^ ((r >> 2) & 3);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, Vs + i * 1024, 16,
-                                               lrow(min(r, 143)) * ldq2 + (h * 32 + ch * 8) * 2,
-                                               2 * C2, 0, 0);
-    }
-  }
-  // K fragments of all nine tiles, Q fragments of this wave's three: tile i, lane (token
-  // 16 i + c16, d 8 g .. 8 g + 7)
-  u32x4 qf[3], kf[9];
-  int qoff[3];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    const int vo = lrow(16 * i + c16) * ldq2 + (h * 32 + 8 * g) * 2;
-    kf[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, C2, 0));
-  }
-#pragma unroll
-  for (int n = 0; n < 3; ++n) {
-    const int lr = lrow(16 * (3 * wave + n) + c16);
-    qoff[n] = lr * ldo2 + (h * 32 + 4 * g) * 2;  // the query's output row, this lane's columns
-    qf[n] = __builtin_bit_cast(
-        u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lr * ldq2 + (h * 32 + 8 * g) * 2, 0, 0));
-  }
-  // per-lane table offsets b(k) of its 36 keys k = 16 kt + 4 g + j and, for SW-MSA windows, their
-  // region codes (bit 0: lower part of the last window row, bit 1: right part of the last window
-  // column), one byte per j
-  int kofs[9][4];
-  unsigned kc[9];
-  const int cut = 12 - s0;
-  const bool lr_ = wtype & 2, lc_ = wtype & 1;
-#pragma unroll
-  for (int kt = 0; kt < 9; ++kt) {
-    kc[kt] = 0u;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int k = 16 * kt + 4 * g + j, ki = div12(k), kj = k - 12 * ki;
-      kofs[kt][j] = (11 * ki + k) * 4;
-      kc[kt] |= (unsigned)((lr_ && ki >= cut ? 1 : 0) | (lc_ && kj >= cut ? 2 : 0)) << (8 * j);
-    }
-  }
-  wait_vmcnt0();    // this wave's LDS-DMA has landed ...
-  __syncthreads();  // ... and so has the other two waves'
-
-  const int tq = (lane >> 2) & 3, tp = lane & 3;
-  const float NEG = -INFINITY;
-#pragma unroll
-  for (int n = 0; n < 3; ++n) {
-    const int q = 16 * (3 * wave + n) + c16;
-    const int qi = div12(q), qj = q - 12 * qi;
-    const EVT_LDS char* Tq = Ts + (11 * qi + q + 264) * 4;
-    const unsigned cq = ((lr_ && qi >= cut ? 1u : 0u) | (lc_ && qj >= cut ? 2u : 0u)) * 0x01010101u;
-    f32x4 s[9];
-#pragma unroll
-    for (int kt = 0; kt < 9; ++kt) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf[kt]),
-                                                      __builtin_bit_cast(bf16x8, qf[n]), acc, 0,
-                                                      0, 0);
-    }
-    // s[kt][j] = S^T[key 16 kt + 4 g + j][query q]: scores in the log2 domain + bias on packed
-    // pairs, then the region mask
-    const f32x2 sc2 = {p.scale_log2, p.scale_log2};
-#pragma unroll
-    for (int kt = 0; kt < 9; ++kt) {
-      f32x4 bv;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bv[j] = *(const EVT_LDS float*)(Tq - kofs[kt][j]);
-      const f32x2 lo = f32x2{s[kt][0], s[kt][1]} * sc2 + f32x2{bv[0], bv[1]};
-      const f32x2 hi = f32x2{s[kt][2], s[kt][3]} * sc2 + f32x2{bv[2], bv[3]};
-      s[kt] = f32x4{lo[0], lo[1], hi[0], hi[1]};
-      if (wtype) {  // SW-MSA window on the last row / column: keys of another region
-        const unsigned x = kc[kt] ^ cq;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if ((x >> (8 * j)) & 3u) s[kt][j] = NEG;
-      }
-    }
-    float mx = NEG;
-#pragma unroll
-    for (int kt = 0; kt < 9; ++kt)
-      mx = fmaxf(mx, fmaxf(fmaxf(s[kt][0], s[kt][1]), fmaxf(s[kt][2], s[kt][3])));
-    mx = bfly_max_16_32(mx);
-    float sum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 9; ++kt) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s[kt][j] = __builtin_amdgcn_exp2f(s[kt][j] - mx);
-      sum += (s[kt][0] + s[kt][1]) + (s[kt][2] + s[kt][3]);
-    }
-    sum = bfly_sum_16_32(sum);
-
-    f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-    for (int ks = 0; ks < 5; ++ks) {
-      bf16x8 pf;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        pf[j] = (bf16)s[2 * ks][j];
-        pf[4 + j] = ks < 4 ? (bf16)s[(2 * ks + 1) % 9][j] : (bf16)0.f;  // keys 144 .. 159: P = 0
-      }
-      const int key0 = ks * 32 + 4 * g + tq;  // and key0 + 16: same (row >> 2) & 3 swizzle
-      const int sw = (key0 >> 2) & 3;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        const int chunk = 2 * dt + (tp >> 1);
-        const int off = ((chunk ^ sw) * 16) + (tp & 1) * 8;
-        const i16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((EVT_LDS i16x4*)(Vs + key0 * 64 + off));
-        const i16x4 v1 =
-            __builtin_amdgcn_ds_read_tr16_b64_v4i16((EVT_LDS i16x4*)(Vs + (key0 + 16) * 64 + off));
-        const i16x8 vv = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vv), pf, o[dt],
-                                                        0, 0, 0);
-      }
-    }
-    // o[dt][j] = O^T[d = 16 dt + 4 g + j][query q]
-    const float inv = __builtin_amdgcn_rcpf(sum);
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt) {
-      const f32x4 v = o[dt] * inv;
-      const bf16x4 ob = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-      buffer_store_b64<0>(__builtin_bit_cast(u32x2, ob), ro, qoff[n], 32 * dt);
-    }
-    if (h == 0)  // pad columns [C, ldo) of the attention output (the proj GEMM's K padding)
-      for (int c = p.C + 4 * g; c < p.ldo; c += 16)
-        buffer_store_b64<0>(u32x2{0u, 0u}, ro, qoff[n] + (c - 4 * g) * 2, 0);
-  }
+  window_attn_bf16<12>(p);
 }
 
 // fp32 window attention for 12 x 12 windows (parity path): block = 3 waves = one (image, window,
@@ -798,21 +534,13 @@ __global__ __launch_bounds__(192) void window12_attn_f32_kernel(SwinAttnParams p
   const int h = (int)(pair % p.H);
   const int64_t bw = pair / p.H;
   const int win = (int)(bw % nw), b = (int)(bw / nw);
-  const int R = p.R, s0 = p.shift;
-  const int wy = win / p.nwx, wx = win - wy * p.nwx;
-  const int wtype = s0 ? (wy == p.nwx - 1 ? 2 : 0) + (wx == p.nwx - 1 ? 1 : 0) : 0;
-  const int64_t base = (int64_t)b * R * R;
-  auto row = [&](int t) {
-    const int i = t / 12, j = t - 12 * i;
-    int y = wy * 12 + s0 + i, x = wx * 12 + s0 + j;
-    if (y >= R) y -= R;
-    if (x >= R) x -= R;
-    return base + (y * R + x);
-  };
+  using T = WinTraits<12>;
+  const WinGeom<12> G(p.R, p.nwx, p.shift, win);
+  const int64_t base = (int64_t)b * p.R * p.R;
   const float* qkv = (const float*)p.qkv;
   for (int e = tid; e < 144 * 32; e += 192) {
     const int t = e >> 5, d = e & 31;
-    const float* rp = qkv + row(t) * p.ldq + h * 32 + d;
+    const float* rp = qkv + (base + G.row(t)) * p.ldq + h * 32 + d;
     Ks[t][d] = rp[p.C];
     Vs[t][d] = rp[2 * p.C];
   }
@@ -820,21 +548,18 @@ __global__ __launch_bounds__(192) void window12_attn_f32_kernel(SwinAttnParams p
   __syncthreads();
   if (tid >= 144) return;
   const int t = tid, qi = t / 12, qj = t - 12 * qi;
-  const int64_t qrow = row(t);
+  const int64_t qrow = base + G.row(t);
   float q[32];
 #pragma unroll
   for (int d = 0; d < 32; ++d) q[d] = qkv[qrow * p.ldq + h * 32 + d];
-  const int cut = 12 - s0;
-  const bool lr_ = wtype & 2, lc_ = wtype & 1;
-  const int cq = (lr_ && qi >= cut ? 1 : 0) | (lc_ && qj >= cut ? 2 : 0);
-  const float* Tq = Ts + (11 * qi + t + 264);
+  const unsigned cq = G.code(qi, qj);
+  const float* Tq = Ts + T::a(qi, t);
   auto score = [&](int k, int ki, int kj) {
     float a = 0.f;
 #pragma unroll
     for (int d = 0; d < 32; ++d) a += q[d] * Ks[k][d];
-    float v = a * p.scale_log2 + Tq[-(11 * ki + k)];
-    const int ck = (lr_ && ki >= cut ? 1 : 0) | (lc_ && kj >= cut ? 2 : 0);
-    if (ck != cq) v += -100.0f * kLog2e;
+    float v = a * p.scale_log2 + Tq[-T::b(ki, k)];
+    if (G.code(ki, kj) != cq) v += -100.0f * kLog2e;
     return v;
   };
   float mx = -INFINITY;
@@ -1152,17 +877,6 @@ __global__ __launch_bounds__(256, 2) void swin_attn96_kernel(SwinAttnBlockParams
     const float* cb = rpb_compact(p.bias, 3, p.shift);
     for (int e = tid; e < 3 * RPB_CROW; e += 256) ((EVT_LDS float*)(L + AT96_TB))[e] = cb[e];
   }
-  // per-lane table offsets b(k) of the 16 keys k = 16 kt + 4 g + j (past 48: key 48's, masked)
-  int kofs[4][4], kij[4][4];
-#pragma unroll
-  for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int k = min(16 * kt + 4 * g + j, 48), ki = (k * 37) >> 8;
-      kofs[kt][j] = (6 * ki + k) * 4;
-      kij[kt][j] = ki * 8 + (k - 7 * ki);  // row, column in the window
-    }
-  const int cut = 7 - p.shift;
   const int ft0 = wave * 5 - (wave > 2 ? 1 : 0), nft = wave < 2 ? 5 : 4;  // 0 / 5 / 10 / 14
   u32x4 wq[5][3];
 #pragma unroll
@@ -1181,14 +895,15 @@ __global__ __launch_bounds__(256, 2) void swin_attn96_kernel(SwinAttnBlockParams
   f32x4 sc[3];
   auto prefetch = [&](int wgn) {
     const int bn = wgn / nw, wn = wgn - bn * nw;
-    const WinGeom Gn(p.R, nwx, p.shift, bn, wn);
+    const WinGeom<7> Gn(p.R, nwx, p.shift, wn);
+    const int64_t basen = (int64_t)bn * p.R * p.R;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       const int e = tid + 256 * k, t = e / 12, j = e - t * 12;
       xc[k] = u32x4{0u, 0u, 0u, 0u};
       sc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (t < 49) {
-        const int64_t row = Gn.row(t);
+        const int64_t row = basen + Gn.row(t);
         xc[k] = *(const u32x4*)(x + row * 96 + j * 8);
         const float* st = p.stats_in + row * 2 * p.nslots;
         sc[k] = f32x4{st[0], st[1], p.nslots > 1 ? st[2] : 0.f, p.nslots > 1 ? st[3] : 0.f};
@@ -1196,10 +911,10 @@ __global__ __launch_bounds__(256, 2) void swin_attn96_kernel(SwinAttnBlockParams
     }
   };
   if (blockIdx.x < nwin) prefetch(blockIdx.x);
-  const int tq = (lane >> 2) & 3, tp = lane & 3;
   for (int wg = blockIdx.x; wg < nwin; wg += gridDim.x) {
     const int b = wg / nw, win = wg - b * nw;
-    const WinGeom G(p.R, nwx, p.shift, b, win);
+    const WinGeom<7> G(p.R, nwx, p.shift, win);
+    const int64_t base = (int64_t)b * p.R * p.R;
     __syncthreads();  // the previous window's qkv / XO readers are done
     // ---- P0: Xn = LN1(x) of the window tokens ((x - mu) r; gamma is in Wq, beta in cqkv) ----
 #pragma unroll
@@ -1254,81 +969,27 @@ __global__ __launch_bounds__(256, 2) void swin_attn96_kernel(SwinAttnBlockParams
     }
     __syncthreads();
     // ---- P2: attention units (h, query tile `wave`), h = 0..2 ----
-    // the bias from the LDS tables as in window_attn_bf16_kernel (T[a(q) - b(k)], the SW-MSA
-    // region mask and the keys past 48 as -inf); the next window's x prefetch lands during P2 / P3
+    // window_scores.h's score step, softmax and P . V as in window_attn_bf16, with Q / K / V from
+    // the LDS qkv tile (unswizzled rows); the next window's x prefetch lands during P2 / P3
     const int qt = wave;
     if (wg + (int)gridDim.x < nwin) prefetch(wg + gridDim.x);
-    const int wtype = G.type();
-    const bool lr_ = wtype & 2, lc_ = wtype & 1;
-    const int qq = min(16 * qt + c16, 48), qi = (qq * 37) >> 8, qj = qq - 7 * qi;
-    const int toff = AT96_TB + (6 * qi + qq + 84) * 4;
-    const unsigned cq = (lr_ && qi >= cut ? 1u : 0u) | (lc_ && qj >= cut ? 2u : 0u);
+    int kofs[4][4];
+    unsigned kc[4];
+    key_tables<7>(G, g, kofs, kc);
     const EVT_LDS char* Q = L + AT96_QKV;
 #pragma unroll
     for (int h = 0; h < 3; ++h) {
       const u32x4 qf = *(const EVT_LDS u32x4*)(Q + (16 * qt + c16) * AT96_QROW + (32 * h + 8 * g) * 2);
-      f32x4 sv[4];
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt) {
-        const u32x4 kf = *(const EVT_LDS u32x4*)(Q + (16 * kt + c16) * AT96_QROW + (96 + 32 * h + 8 * g) * 2);
-        sv[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf),
-                                                         __builtin_bit_cast(bf16x8, qf),
-                                                         f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-      }
-      const f32x2 sc2 = {scale_log2, scale_log2};
-      const EVT_LDS char* Tq = L + toff + h * RPB_CROW * 4;
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt) {
-        f32x4 bv;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bv[j] = *(const EVT_LDS float*)(Tq - kofs[kt][j]);
-        const f32x2 lo = f32x2{sv[kt][0], sv[kt][1]} * sc2 + f32x2{bv[0], bv[1]};
-        const f32x2 hi = f32x2{sv[kt][2], sv[kt][3]} * sc2 + f32x2{bv[2], bv[3]};
-        sv[kt] = f32x4{lo[0], lo[1], hi[0], hi[1]};
-        if (wtype) {  // SW-MSA window on the last row / column: keys of another region
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int ki = kij[kt][j] >> 3, kj = kij[kt][j] & 7;
-            const unsigned ck = (lr_ && ki >= cut ? 1u : 0u) | (lc_ && kj >= cut ? 2u : 0u);
-            if (ck != cq) sv[kt][j] = -INFINITY;
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j)  // keys 49 .. 63
-        if (4 * g + j > 0) sv[3][j] = -INFINITY;
-      float m4[4];
+      u32x4 kf[4];
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt)
-        m4[kt] = fmaxf(fmaxf(sv[kt][0], sv[kt][1]), fmaxf(sv[kt][2], sv[kt][3]));
-      const float mx = bfly_max_16_32(fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3])));
-      float p4[4];
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) sv[kt][j] = __builtin_amdgcn_exp2f(sv[kt][j] - mx);
-        p4[kt] = (sv[kt][0] + sv[kt][1]) + (sv[kt][2] + sv[kt][3]);
-      }
-      const float sum = bfly_sum_16_32((p4[0] + p4[1]) + (p4[2] + p4[3]));
+        kf[kt] = *(const EVT_LDS u32x4*)(Q + (16 * kt + c16) * AT96_QROW + (96 + 32 * h + 8 * g) * 2);
+      f32x4 sv[4];
+      score_tile<7>(G, kf, qf, WinTraits<7>::clamp(16 * qt + c16), g, L + AT96_TB + h * RPB_CROW * 4,
+                    scale_log2, kofs, kc, sv);
+      const float sum = softmax_exp<7>(sv);
       f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        bf16x8 pf;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          pf[j] = (bf16)sv[2 * ks][j];
-          pf[4 + j] = (bf16)sv[2 * ks + 1][j];
-        }
-        const int key0 = ks * 32 + 4 * g + tq;
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-          const int col = (192 + 32 * h + 16 * dt + 4 * tp) * 2;
-          const i16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((EVT_LDS i16x4*)(Q + key0 * AT96_QROW + col));
-          const i16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((EVT_LDS i16x4*)(Q + (key0 + 16) * AT96_QROW + col));
-          const i16x8 vv = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-          o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vv), pf, o[dt], 0, 0, 0);
-        }
-      }
+      pv_accumulate<7, AT96_QROW, false>(sv, Q + (192 + 32 * h) * 2, lane, o);
       // o[dt][j] = O^T[d = 16 dt + 4 g + j][query 16 qt + c16]
       const float inv = __builtin_amdgcn_rcpf(sum);
 #pragma unroll
@@ -1344,7 +1005,7 @@ __global__ __launch_bounds__(256, 2) void swin_attn96_kernel(SwinAttnBlockParams
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's O rows are in LDS
     {
       const int t = 16 * qt + c16;
-      const int64_t row = G.row(min(t, 48));
+      const int64_t row = base + G.row(min(t, 48));
       bf16x4 xr[6];  // residual rows (L2-resident: read by this window's prefetch)
 #pragma unroll
       for (int f = 0; f < 6; ++f) xr[f] = *(const bf16x4*)(x + row * 96 + 16 * f + 4 * g);
@@ -1388,7 +1049,7 @@ __global__ __launch_bounds__(256, 2) void swin_attn96_kernel(SwinAttnBlockParams
         const int idx = 64 * i + lane, r = idx / 12, j = idx - r * 12, tr = 16 * qt + r;
         if (tr < 49) {
           const u32x4 v = *(const EVT_LDS u32x4*)(L + AT96_XO + tr * AT96_ROW + j * 16);
-          store_b128((bf16*)p.xm + G.row(tr) * 96 + 8 * j, v);
+          store_b128((bf16*)p.xm + (base + G.row(tr)) * 96 + 8 * j, v);
         }
       }
       if (g == 0 && t < 49) {
@@ -1677,38 +1338,26 @@ const float* rpb_compact_table(const float* tables, int H, int w, int shift, int
   return w == 12 ? tables : rpb_compact(tables, H, shift);
 }
 
-hipError_t window_attn_launch(int dtype, const SwinAttnParams& p, hipStream_t s) {
+hipError_t window_attn_launch(int dtype, int w, const SwinAttnParams& p, hipStream_t s) {
   if (p.B <= 0) return hipSuccess;
-  if (p.R % 7 || p.nwx * 7 != p.R || p.C != p.H * 32 || p.ldo < p.C || p.shift < 0 ||
-      p.shift >= 7 || (p.ldq % 8) || (p.ldo % 4))
+  if ((w != 7 && w != 12) || p.R % w || p.nwx * w != p.R || p.C != p.H * 32 || p.ldo < p.C ||
+      p.shift < 0 || p.shift >= w || (p.ldq % 8) || (p.ldo % 4))
     return hipErrorInvalidValue;
+  // w = 7: 4 (image, window, head) per block, w = 12: one. The bf16 kernels hold a 32-bit (image,
+  // window, head) index and per-image 32-bit buffer offsets
   const int64_t pairs = (int64_t)p.B * p.nwx * p.nwx * p.H;
-  const dim3 grid((unsigned)((pairs + 3) / 4));
-  // bf16 kernel: 32-bit (image, window, head) index and per-image 32-bit buffer offsets
-  if (dtype == DT_BF16 && (pairs + 4 >= (int64_t)1 << 31 ||
-                           (int64_t)p.R * p.R * std::max(p.ldq, p.ldo) * 2 >= (int64_t)1 << 31))
-    return hipErrorInvalidValue;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(window_attn_bf16_kernel, grid, dim3(256), 0, s, p);
-  else
-    hipLaunchKernelGGL(window_attn_f32_kernel, grid, dim3(256), 0, s, p);
-  return hipGetLastError();
-}
-
-hipError_t window12_attn_launch(int dtype, const SwinAttnParams& p, hipStream_t s) {
-  if (p.B <= 0) return hipSuccess;
-  if (p.R % 12 || p.nwx * 12 != p.R || p.C != p.H * 32 || p.ldo < p.C || p.shift < 0 ||
-      p.shift >= 12 || (p.ldq % 8) || (p.ldo % 4))
-    return hipErrorInvalidValue;
-  // one block per (image, window, head); the bf16 kernel forms 32-bit byte offsets per image
-  const int64_t pairs = (int64_t)p.B * p.nwx * p.nwx * p.H;
-  if (pairs >= (int64_t)1 << 31 ||
+  if (pairs + 4 >= (int64_t)1 << 31 ||
       (dtype == DT_BF16 && (int64_t)p.R * p.R * std::max(p.ldq, p.ldo) * 2 >= (int64_t)1 << 31))
     return hipErrorInvalidValue;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(window12_attn_bf16_kernel, dim3((unsigned)pairs), dim3(192), 0, s, p);
+  const dim3 grid((unsigned)(w == 7 ? (pairs + 3) / 4 : pairs)), block(w == 7 ? 256 : 192);
+  if (w == 7 && dtype == DT_BF16)
+    hipLaunchKernelGGL(window_attn_bf16_kernel, grid, block, 0, s, p);
+  else if (w == 7)
+    hipLaunchKernelGGL(window_attn_f32_kernel, grid, block, 0, s, p);
+  else if (dtype == DT_BF16)
+    hipLaunchKernelGGL(window12_attn_bf16_kernel, grid, block, 0, s, p);
   else
-    hipLaunchKernelGGL(window12_attn_f32_kernel, dim3((unsigned)pairs), dim3(192), 0, s, p);
+    hipLaunchKernelGGL(window12_attn_f32_kernel, grid, block, 0, s, p);
   return hipGetLastError();
 }
 

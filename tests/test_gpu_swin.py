@@ -107,7 +107,8 @@ def _oracle_core(qkv, R, H, s, rpb):
 
 @pytest.mark.parametrize("dtype,tol", [("f32", 2e-5), ("bf16", 3e-2)])
 @pytest.mark.parametrize("R,H,shift,B", [(14, 3, 0, 2), (14, 3, 3, 2), (28, 6, 3, 1),
-                                         (7, 24, 0, 3), (21, 4, 3, 1)])
+                                         (7, 24, 0, 3), (21, 4, 3, 1),
+                                         (7, 3, 0, 1), (7, 3, 3, 1)])  # 3 pairs: a partial block
 def test_window_attention_kernel(gpu, dtype, tol, R, H, shift, B):
     out, ref, C, ldo = _window_case(dtype, R, H, shift, B, gpu)
     assert np.abs(out[:, :C] - ref).max() <= tol
