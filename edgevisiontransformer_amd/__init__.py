@@ -12,5 +12,5 @@ __version__ = "0.4.0"
 
 from .images import (IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD, EvalTransform,  # noqa: E402,F401
                      Uint8Images)
-from .evaluate import (collect_ffn_stats, collect_head_stats, evaluate,  # noqa: E402,F401
-                       head_ablation, sublayer_ablation)
+from .evaluate import (collect_ffn_stats, collect_grams, collect_head_stats,  # noqa: E402,F401
+                       evaluate, head_ablation, sublayer_ablation)

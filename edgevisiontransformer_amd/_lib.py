@@ -254,6 +254,26 @@ FFN_STATS_SIGNATURES = {
 }
 
 
+class evt_gram_args(ctypes.Structure):
+    _fields_ = [("n_blocks", ctypes.c_int32), ("blocks", ctypes.POINTER(ctypes.c_int32)),
+                ("which", ctypes.c_int32), ("grams", ctypes.POINTER(ctypes.c_void_p)),
+                ("sums", ctypes.POINTER(ctypes.c_void_p)), ("scratch", ctypes.c_void_p),
+                ("scratch_bytes", ctypes.c_size_t)]
+
+
+# include/evt_gram.h constants
+GRAM_FFN, GRAM_ATTN, GRAM_MAX_WIDTH = 0, 1, 6144
+# the entry points of include/evt_gram.h (evt.h includes it; bound like SIGNATURES)
+GRAM_SIGNATURES = {
+    "evt_gram_scratch_bytes": (_I, [_I64, _I, ctypes.POINTER(ctypes.c_size_t)]),
+    "evt_gram": (_I, [_I, _P, _I64, _I64, _I, _P, _P, _P, ctypes.c_size_t, _P]),
+    "evt_gram_shape": (_I, [_P, _I, _I, _PI, _PI]),
+    "evt_forward_grams": (_I, [_P, ctypes.POINTER(evt_image_args), _I,
+                               ctypes.POINTER(evt_features_args),
+                               ctypes.POINTER(evt_gram_args), _P]),
+}
+
+
 class evt_rollout_args(ctypes.Structure):
     _fields_ = [("start", ctypes.c_int32), ("mode", ctypes.c_int32), ("out", ctypes.c_void_p),
                 ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t)]
@@ -397,7 +417,8 @@ def load_library() -> ctypes.CDLL:
                                       **ROLLOUT_SIGNATURES, **FFN_STATS_SIGNATURES,
                                       **CLASSIFY_SIGNATURES, **WORKSPACE_SIGNATURES,
                                       **PERFORMER_SIGNATURES, **TOKEN_PRUNING_SIGNATURES,
-                                      **GATES_SIGNATURES, **DEPTH_SIGNATURES}.items():
+                                      **GATES_SIGNATURES, **DEPTH_SIGNATURES,
+                                      **GRAM_SIGNATURES}.items():
                 if lenient and not hasattr(lib, name):
                     continue
                 fn = getattr(lib, name)

@@ -16,7 +16,7 @@ LIB = os.path.join(HERE, "libevt_hip.so")
 OBJ = os.path.join(HERE, "build_obj")
 SOURCES = ["gemm.hip", "attention.hip", "norm.hip", "t2t.hip", "swin.hip", "mx8.hip",
            "features.hip", "preprocess.hip", "attn_maps.hip", "rollout.hip", "ffn_stats.hip",
-           "token_pruning.hip", "gates.hip", "depth_stats.hip",
+           "token_pruning.hip", "gates.hip", "depth_stats.hip", "gram.hip",
            "model.cpp", "encoder.cpp", "model_vit.cpp", "model_t2t.cpp", "model_swin.cpp",
            "ops.cpp", "resize_plan.cpp"]
 # the GEMM kernels, one header per kernel, all included by gemm.hip (one translation unit)
@@ -32,6 +32,7 @@ HEADERS = GEMM_HEADERS + [
            os.path.join("..", "..", "include", "evt_attention_maps.h"),
            os.path.join("..", "..", "include", "evt_head_stats.h"),
            os.path.join("..", "..", "include", "evt_ffn_stats.h"),
+           os.path.join("..", "..", "include", "evt_gram.h"),
            os.path.join("..", "..", "include", "evt_rollout.h"),
            os.path.join("..", "..", "include", "evt_token_pruning.h"),
            os.path.join("..", "..", "include", "evt_gates.h"),

@@ -173,14 +173,14 @@ int run_encoder(evt_model* m, ForwardCall& call) {
     // out-proj, FC1 and FC2 run on the B CLS rows (the CLS tail, below) and its attention on query
     // tile 0. A call that exports the last block's token map (tokens, or a tap on it or on a
     // skipped block after it) runs the full-row block as well; the CLS rows it exports, and the
-    // head reads, are still the tail's. The last block's FFN and stream statistics are those of the
-    // full-row launches (evt_ffn_stats.h, evt_depth.h).
+    // head reads, are still the tail's. The last block's FFN and stream statistics and its Grams are
+    // those of the full-row launches (evt_ffn_stats.h, evt_depth.h, evt_gram.h).
     const bool last = block == last_block;
     // the call asks for this block's stream statistics (read here: the cursor moves on at the
     // block's FFN sublayer)
     const bool bs = call.bstats.wants(block);
     const bool full = !last || (call.feat && call.feat->tokens) || call.taps.reaches(block) ||
-                      call.fstats.last_is(block) || bs;
+                      call.fstats.last_is(block) || call.grams.last_is(block) || bs;
     if (last) m->tail_mode = full ? 3 : 1;
     // The CLS tail's form of a launch: row b is row b T of the stream and statistics buffers, in
     // place (the head, and `pooled`, read them where they always did), the FFN hidden rows compact
@@ -248,6 +248,7 @@ int run_encoder(evt_model* m, ForwardCall& call) {
       EVT_RC(attn_map(m, call, block, ap));
       EVT_RC(head_stats(m, call, block, ap));
       EVT_RC(rollout_step(m, call, block, ap));
+      if (full) EVT_RC(gram_hook(m, call, block, EVT_GRAM_ATTN, m->ws.o, L.inner, rows, L.inner));
       // out-proj + bias + LN1(x) residual -> xm (+ stats); STANDARD: + x
       DenseCall co;
       co.flags = resid_flags;
@@ -294,6 +295,7 @@ int run_encoder(evt_model* m, ForwardCall& call) {
         if (last) EVT_RC(dense(m, L.fc1, tail(c1), s));
       }
       if (full) EVT_RC(ffn_stats(m, call, block, L, rows));
+      if (full) EVT_RC(gram_hook(m, call, block, EVT_GRAM_FFN, m->ws.hbuf, L.ffn_st, rows, L.ffn));
       {
         ProfScope ps(m, EVT_PROF_FC2, s);
         if (full) EVT_RC(dense(m, L.fc2, c2, s));

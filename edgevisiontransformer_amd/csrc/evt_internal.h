@@ -192,6 +192,42 @@ constexpr int FFN_STATS_MAX_TOKENS = 4096;  // EVT_FFN_STATS_MAX_TOKENS of the h
 hipError_t ffn_stats_launch(int dtype, const void* h, int64_t ld, int B, int T, int F, float* out,
                             hipStream_t s);
 
+// Activation Grams (gram.hip; include/evt_gram.h): gram[i][j] = sum_r a[r][i] a[r][j] ([F][F], both
+// triangles) and sums[j] = sum_r a[r][j] of the row-major matrix a (`rows` rows, pitch ld elements,
+// dtype bf16 or f32), fp32, written not accumulated. gram_plan is the work split, a function of
+// (rows, F) alone: 128 x 128 tiles of the upper triangle, and, while those are fewer than
+// GRAM_MIN_BLOCKS, row chunks (whole multiples of GRAM_ROW_QUANTUM rows, at least
+// GRAM_MIN_CHUNK_ROWS of them in the matrix per chunk) up to about GRAM_TARGET_BLOCKS workgroups;
+// with more than one chunk the fp32 partial tiles and column sums go through `scratch`
+// (scratch_bytes of the plan, 16-byte aligned) and a second launch adds them in chunk order.
+// 1 <= F <= GRAM_MAX_WIDTH, ld >= F and a multiple of the 16-byte vector (8 bf16, 4 f32), rows >= 1,
+// a / gram / sums 16-byte aligned (hipErrorInvalidValue otherwise). Columns [F, ld) may be loaded
+// and never reach a stored element.
+constexpr int GRAM_TILE = 128, GRAM_MAX_WIDTH = 6144;  // EVT_GRAM_MAX_WIDTH of the header
+constexpr int GRAM_ROW_QUANTUM = 64, GRAM_MIN_CHUNK_ROWS = 256;
+constexpr int GRAM_MIN_BLOCKS = 256, GRAM_TARGET_BLOCKS = 512;
+struct GramPlan {
+  int nt = 0, tiles = 0, chunks = 1, rows_per_chunk = 0;
+  size_t scratch_bytes = 0;
+};
+inline GramPlan gram_plan(int rows, int F) {
+  GramPlan p;
+  p.nt = (F + GRAM_TILE - 1) / GRAM_TILE;
+  p.tiles = p.nt * (p.nt + 1) / 2;
+  const int want = p.tiles >= GRAM_MIN_BLOCKS ? 1 : (GRAM_TARGET_BLOCKS + p.tiles - 1) / p.tiles;
+  const int fit = rows / GRAM_MIN_CHUNK_ROWS > 1 ? rows / GRAM_MIN_CHUNK_ROWS : 1;
+  const int chunks = want < fit ? want : fit;
+  const int per = (rows + chunks - 1) / chunks;
+  p.rows_per_chunk = (per + GRAM_ROW_QUANTUM - 1) / GRAM_ROW_QUANTUM * GRAM_ROW_QUANTUM;
+  p.chunks = (rows + p.rows_per_chunk - 1) / p.rows_per_chunk;
+  if (p.chunks > 1)
+    p.scratch_bytes = (size_t)p.chunks * ((size_t)p.tiles * GRAM_TILE * GRAM_TILE +
+                                          (size_t)p.nt * GRAM_TILE) * sizeof(float);
+  return p;
+}
+hipError_t gram_launch(int dtype, const void* a, int64_t ld, int rows, int F, float* gram,
+                       float* sums, void* scratch, size_t scratch_bytes, hipStream_t s);
+
 // Stream-delta statistics (depth_stats.hip; include/evt_depth.h): out[b ldo + 0..3] = (cosine,
 // rel_update, norm_ratio, cls_cosine) of the rows b T .. b T + T - 1 of a against those of b (B T
 // rows of D elements, pitches lda / ldb, dtype bf16 or f32). One launch for T <= STREAM_DELTA_CHUNK;

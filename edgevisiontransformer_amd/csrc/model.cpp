@@ -266,6 +266,23 @@ int ffn_stats(evt_model* m, ForwardCall& call, int block, const Layer& L, int ro
   return EVT_OK;
 }
 
+// At the same point of an evt_forward_grams call for EVT_GRAM_FFN, and right after the attention
+// kernel (ws.o) for EVT_GRAM_ATTN: the block's Gram and column sums, if they were asked for
+// (gram.hip: one launch, or two through the call's scratch; counted under EVT_PROF_HEAD)
+int gram_hook(evt_model* m, ForwardCall& call, int block, int which, const void* a, int64_t ld,
+              int rows, int width) {
+  if (!call.gram || call.gram->which != which || !call.grams.wants(block)) return EVT_OK;
+  float* sums = call.gram->sums[call.grams.next];
+  float* out = call.grams.take(block);
+  ProfScope ps(m, EVT_PROF_HEAD, call.s);
+  prof_work(m, 2.0 * rows * (double)width * width,
+            (double)rows * width * elem_size(m->dtype) + 4.0 * width * (width + 1.0));
+  EVT_HIP(gram_launch(m->dtype, a, ld, rows, width, out, sums, call.gram->scratch,
+                      call.gram->scratch_bytes, call.s),
+          "activation gram");
+  return EVT_OK;
+}
+
 // At both sublayer ends of an evt_forward_block_stats call, while the sublayer's input rows `a`
 // and output rows `b` are both resident (run_encoder): its four stream statistics, if the block
 // is the next one asked for (depth_stats.hip; counted under EVT_PROF_HEAD). The per-chunk partials
@@ -972,6 +989,73 @@ int evt_forward_ffn_stats(evt_model* m, const evt_image_args* in, int B,
   EVT_RC(check_blocks(stats, model_blocks(m), nullptr, nullptr));
   EVT_RC(no_skipped(m, stats, EVT_SKIP_FFN));
   call.fstats = stats.cursor();
+  return forward(m, call, false);
+}
+
+// ---- activation Grams (include/evt_gram.h) --------------------------------------------------
+
+// the users of run_encoder, for the reasons of ffn_stats_family
+static int gram_family(const evt_model* m) {
+  if (m->family == FAM_SWIN)
+    return fail(EVT_EINVAL, "activation gram: Swin's fused MLP and window attention do not store "
+                            "the rows a Gram is formed of");
+  if (m->mx8)
+    return fail(EVT_EINVAL, "activation gram: not available on an EVT_DTYPE_MX8 model (its hidden "
+                            "and attention rows are kept quantised)");
+  return EVT_OK;
+}
+
+static int gram_which(int which) {
+  if (which != EVT_GRAM_FFN && which != EVT_GRAM_ATTN)
+    return fail(EVT_EINVAL, "activation gram: which must be EVT_GRAM_FFN or EVT_GRAM_ATTN");
+  return EVT_OK;
+}
+
+static int gram_width(const Layer& L, int which) { return which == EVT_GRAM_FFN ? L.ffn : L.inner; }
+
+int evt_gram_shape(const evt_model* m, int block, int which, int* width, int* tokens) {
+  if (!m || !width || !tokens) return fail(EVT_EINVAL, "activation gram: null argument");
+  EVT_RC(gram_family(m));
+  EVT_RC(gram_which(which));
+  if (block < 0 || block >= (int)m->layers.size())
+    return fail(EVT_EINVAL, "block must be in [0, " + std::to_string(m->layers.size()) + ")");
+  *width = gram_width(m->layers[block], which);
+  *tokens = m->sh.T;
+  return EVT_OK;
+}
+
+int evt_forward_grams(evt_model* m, const evt_image_args* in, int B,
+                      const evt_features_args* feat, const evt_gram_args* a, void* stream) {
+  if (!m || !in || !a) return fail(EVT_EINVAL, "model, image descriptor and ga must be non-null");
+  const BlockList grams = {a->n_blocks, a->blocks, a->grams, "n_blocks", "blocks, grams and sums",
+                           "gram block", "gram blocks", "gram pointer", "activation gram outputs"};
+  ForwardCall call;
+  EVT_RC(analysis_call(m, in, B, feat, stream, gram_family, "evt_forward_grams", &grams, &call));
+  EVT_RC(gram_which(a->which));
+  if (a->n_blocks > 0 && !a->sums)
+    return fail(EVT_EINVAL, "n_blocks > 0 needs the blocks, grams and sums arrays");
+  EVT_RC(check_blocks(grams, model_blocks(m), nullptr, nullptr));
+  EVT_RC(no_skipped(m, grams, a->which == EVT_GRAM_FFN ? EVT_SKIP_FFN : EVT_SKIP_ATTN));
+  if ((uintptr_t)a->scratch & 15)
+    return fail(EVT_EINVAL, "activation gram outputs: scratch must be 16-byte aligned");
+  for (int i = 0; i < a->n_blocks; ++i) {
+    if (!a->sums[i]) return fail(EVT_EINVAL, "gram sums pointer " + std::to_string(i) + " is NULL");
+    if ((uintptr_t)a->sums[i] & 15)
+      return fail(EVT_EINVAL, "activation gram outputs must be 16-byte aligned");
+    const int width = gram_width(m->layers[a->blocks[i]], a->which);
+    if (width > EVT_GRAM_MAX_WIDTH)
+      return fail(EVT_EINVAL, "gram block " + std::to_string(a->blocks[i]) + ": its width " +
+                                  std::to_string(width) + " is above " +
+                                  std::to_string(EVT_GRAM_MAX_WIDTH));
+    const size_t need = gram_plan(B * m->sh.T, width).scratch_bytes;
+    if (need && (!a->scratch || a->scratch_bytes < need))
+      return fail(EVT_EINVAL, "activation gram: scratch_bytes is " +
+                                  std::to_string(a->scratch ? a->scratch_bytes : 0) + ", block " +
+                                  std::to_string(a->blocks[i]) + " needs " + std::to_string(need) +
+                                  " (evt_gram_scratch_bytes)");
+  }
+  call.grams = grams.cursor();
+  call.gram = a;
   return forward(m, call, false);
 }
 

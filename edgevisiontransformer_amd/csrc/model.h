@@ -280,6 +280,8 @@ struct ForwardCall {
   BlockCursor hstats;             // evt_forward_head_stats blocks
   BlockCursor fstats;             // evt_forward_ffn_stats blocks
   BlockCursor bstats;             // evt_forward_block_stats blocks
+  BlockCursor grams;              // evt_forward_grams blocks (out: the Grams), with
+  const evt_gram_args* gram = nullptr;  // their `which`, column-sum pointers and scratch
   void set_feat(const evt_features_args* a) {
     feat = a;
     if (a) taps = BlockCursor{a->tap_blocks, a->taps, a->n_taps};
@@ -426,6 +428,11 @@ int head_stats(evt_model* m, ForwardCall& call, int block, const AttnParams& ap)
 // evt_forward_ffn_stats: block's neuron statistics of the `rows` hidden rows the full-row FC1 left in
 // ws.hbuf, if the call asks for them next (between FC1 and FC2)
 int ffn_stats(evt_model* m, ForwardCall& call, int block, const Layer& L, int rows);
+// evt_forward_grams: the Gram and column sums of the `rows` rows of `a` (pitch ld, `width` columns:
+// ws.hbuf after the full-row FC1 for `which` EVT_GRAM_FFN, ws.o after the attention kernel for
+// EVT_GRAM_ATTN), if the call asks for Grams of that kind and for the block next
+int gram_hook(evt_model* m, ForwardCall& call, int block, int which, const void* a, int64_t ld,
+              int rows, int width);
 // evt_forward_block_stats: sublayer `sub` (0 attention, 1 FFN) of block `block`, if the call asks
 // for the block next: the statistics of the stream rows b against a (T tokens per image), or with
 // a == nullptr the identity values of a skipped sublayer. sub == 1 moves the cursor on.

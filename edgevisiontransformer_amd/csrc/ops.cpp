@@ -453,6 +453,46 @@ int evt_ffn_neuron_stats(int dtype, const void* h, int64_t ld, int B, int T, int
   return EVT_OK;
 }
 
+// include/evt_gram.h
+int evt_gram_scratch_bytes(int64_t rows, int width, size_t* bytes) {
+  static_assert(EVT_GRAM_MAX_WIDTH == GRAM_MAX_WIDTH, "header and kernel agree");
+  if (!bytes) return fail(EVT_EINVAL, "gram scratch: bytes is NULL");
+  if (rows < 1 || rows > INT32_MAX)
+    return fail(EVT_EINVAL, "gram scratch: rows must be in [1, 2^31 - 1]");
+  if (width < 1 || width > EVT_GRAM_MAX_WIDTH)
+    return fail(EVT_EINVAL, "gram scratch: width must be in [1, " +
+                                std::to_string(EVT_GRAM_MAX_WIDTH) + "]");
+  *bytes = gram_plan((int)rows, width).scratch_bytes;
+  return EVT_OK;
+}
+
+int evt_gram(int dtype, const void* a, int64_t ld, int64_t rows, int width, float* gram,
+             float* sums, void* scratch, size_t scratch_bytes, void* stream) {
+  if (dtype != EVT_DTYPE_F32 && dtype != EVT_DTYPE_BF16)
+    return fail(EVT_EINVAL, "gram: dtype must be EVT_DTYPE_F32 or EVT_DTYPE_BF16");
+  if (!a || !gram || !sums) return fail(EVT_EINVAL, "gram: a, gram and sums must be non-null");
+  const int vec = dtype == DT_BF16 ? 8 : 4;
+  if (width < vec || width % vec || width > EVT_GRAM_MAX_WIDTH)
+    return fail(EVT_EINVAL, "gram: width must be a multiple of " + std::to_string(vec) +
+                                " in [" + std::to_string(vec) + ", " +
+                                std::to_string(EVT_GRAM_MAX_WIDTH) + "]");
+  if (ld < width || ld % vec)
+    return fail(EVT_EINVAL, "gram: ld must be at least width and the row pitch a multiple of 16 "
+                            "bytes");
+  if (rows < 1 || rows > INT32_MAX) return fail(EVT_EINVAL, "gram: rows must be in [1, 2^31 - 1]");
+  if (((uintptr_t)a | (uintptr_t)gram | (uintptr_t)sums | (uintptr_t)scratch) & 15)
+    return fail(EVT_EINVAL, "gram: a, gram, sums and scratch must be 16-byte aligned");
+  const size_t need = gram_plan((int)rows, width).scratch_bytes;
+  if (need && (!scratch || scratch_bytes < need))
+    return fail(EVT_EINVAL, "gram: scratch_bytes is " + std::to_string(scratch ? scratch_bytes : 0) +
+                                ", this call needs " + std::to_string(need) +
+                                " (evt_gram_scratch_bytes)");
+  EVT_HIP(gram_launch(dtype, a, ld, (int)rows, width, gram, sums, scratch, scratch_bytes,
+                      (hipStream_t)stream),
+          "gram");
+  return EVT_OK;
+}
+
 // include/evt_depth.h: the stream-delta kernel on caller buffers; the per-chunk partials of an
 // image of more than 16 tokens come from, and go back to, the stream's memory pool
 int evt_stream_delta_stats(int dtype, const void* a, int64_t lda, const void* b, int64_t ldb,

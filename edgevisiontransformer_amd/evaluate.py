@@ -243,3 +243,43 @@ def collect_ffn_stats(model, loader: Iterable, transform=None, blocks=None):
     if not seen:
         raise ValueError("collect_ffn_stats: the loader gave no images")
     return [torch.cat([s / seen, top[:, None]], dim=1).cpu().numpy() for s, top in zip(sums, tops)]
+
+
+def collect_grams(model, loader: Iterable, what="ffn", blocks=None, transform=None):
+    """Dataset Grams of the activations a pruned layer's consumer reads (modeling/models/grams.py):
+    {"gram": [one fp64 [F_i, F_i] per block], "sum": [one fp64 [F_i] per block], "rows": the token
+    rows seen}, numpy, for `pruning.reconstruct_vit_params`. `what`: "ffn" (the FC1 output, for
+    FC2) or "attn" (the attention context, for the out-projection); `blocks=None`: every block
+    (negative indices and any order as `activation_grams`).
+
+    `loader` yields what `evaluate` takes: (images, target) tuples, of which the target is not
+    read, or the images alone. Each batch's fp32 Gram and column sums are added into per-block
+    fp64 device tensors that live for the whole loop, as do the fp32 buffers of a call; the host
+    reads once, at the end. Every token row weighs the same, whatever its batch's size."""
+    import torch
+
+    from .modeling.models.features import resolve_taps
+    device = model.device
+    on_device = torch.cuda.device(device) if device.type == "cuda" else contextlib.nullcontext()
+    nb = model.num_blocks
+    idx = resolve_taps(range(nb) if blocks is None else blocks, nb)
+    geo = [model.gram_shape(i, what) for i in idx]
+    grams = [torch.zeros((f, f), dtype=torch.float64, device=device) for f, _ in geo]
+    sums = [torch.zeros((f,), dtype=torch.float64, device=device) for f, _ in geo]
+    gbuf = [torch.empty((f, f), dtype=torch.float32, device=device) for f, _ in geo]
+    sbuf = [torch.empty((f,), dtype=torch.float32, device=device) for f, _ in geo]
+    rows = 0
+    for item in loader:
+        images = item[0] if isinstance(item, tuple) else item
+        x = _device_batch(model, images, transform)
+        with on_device:
+            model.activation_grams_into(x, blocks=idx, what=what, gram_tensors=gbuf,
+                                        sum_tensors=sbuf)
+            for g, s, gb, sb in zip(grams, sums, gbuf, sbuf):
+                g += gb
+                s += sb
+        rows += x.shape[0] * geo[0][1] if geo else 0
+    if not rows:
+        raise ValueError("collect_grams: the loader gave no images (or no block was asked for)")
+    return {"gram": [g.cpu().numpy() for g in grams], "sum": [s.cpu().numpy() for s in sums],
+            "rows": rows}

@@ -24,7 +24,7 @@ import torch
 
 from ... import _lib
 from .features import outputs_to_numpy
-from .ffn_stats import FFNStats
+from .grams import ActivationGrams
 
 VALUES = {"prob": _lib.CLASSIFY_PROB, "logit": _lib.CLASSIFY_LOGIT}
 MAX_CLASSES = 1 << 20
@@ -84,7 +84,7 @@ def classify_reference(logits, k: int, labels=None) -> Dict[str, np.ndarray]:
     return out
 
 
-class Classification(FFNStats):
+class Classification(ActivationGrams):
     """What ViT, T2T_ViT and SwinTransformer derive from: the classification outputs on top of the
     FFN statistics, attention rollout, head statistics, attention maps and feature outputs. Needs nothing of the
     model class but `cfg.num_classes`."""

@@ -245,6 +245,9 @@ class DepthAxis(StructuredGates):
     def ffn_stats_into(self, *a, **kw):
         return self._skip_refused(super().ffn_stats_into, *a, **kw)
 
+    def activation_grams_into(self, *a, **kw):
+        return self._skip_refused(super().activation_grams_into, *a, **kw)
+
 
 def collect_block_stats(model, loader) -> List[np.ndarray]:
     """Dataset means of `model.block_stats` over `loader` (batches of images, or (images, labels)

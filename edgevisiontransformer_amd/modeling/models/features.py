@@ -131,19 +131,22 @@ class FeatureOutputs(ModelHandle):
             self._ptr(), ctypes.byref(image), b, ctypes.byref(feat[0]) if feat[1] else None,
             ctypes.byref(args), self._stream()))
 
-    def _block_outputs(self, img, key: str, blocks: Sequence[int], shape, into,
+    def _block_outputs(self, img, key, blocks: Sequence[int], shape, into,
                        **want: bool) -> Dict[str, object]:
         """What the allocating wrappers share: {key: [one fp32 tensor of `shape(b, block)` per block
         of `blocks`]} plus the "logits" / "pooled" / "tokens" asked for in `want`, filled by
-        `into(x, tensors, logits=..., ...)` on the model's device. numpy in, numpy out."""
+        `into(x, tensors, logits=..., ...)` on the model's device. numpy in, numpy out. With a tuple
+        of keys and as many shape functions there is one list per key, and `into` gets the lists in
+        that order: `into(x, tensors_0, tensors_1, ..., logits=..., ...)`."""
+        keys, shapes_of = ((key,), (shape,)) if isinstance(key, str) else (tuple(key), tuple(shape))
         x, was_numpy = self._checked_image(img)
         b = x.shape[0]
         new = lambda shape: torch.empty(shape, dtype=torch.float32, device=self.device)  # noqa: E731
-        out: Dict[str, object] = {key: [new(shape(b, i)) for i in blocks]}
+        out: Dict[str, object] = {k: [new(f(b, i)) for i in blocks] for k, f in zip(keys, shapes_of)}
         shapes = self._feat_shapes(b)
         out.update({k: new(shapes[k]) for k, wanted in want.items() if wanted})
         with torch.cuda.device(self.device):
-            into(x, out[key], **{k: out.get(k) for k in want})
+            into(x, *[out[k] for k in keys], **{k: out.get(k) for k in want})
         return outputs_to_numpy(out) if was_numpy else out
 
     def features_into(self, img: torch.Tensor, *, pooled: torch.Tensor = None,

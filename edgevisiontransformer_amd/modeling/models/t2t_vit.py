@@ -91,6 +91,11 @@ class T2T_ViT(DepthAxis):
         c = self.cfg
         return [(c.mlp_dim, c.tokens)] * c.depth
 
+    # -- activation Grams (grams.py): the encoder blocks' attention context is `dim` wide --------
+    def _attn_context_geometry(self):
+        c = self.cfg
+        return [(c.dim, c.tokens)] * c.depth
+
 
 def get_t2t_vit_7(**kw) -> T2T_ViT:
     return T2T_ViT(hidden_size=256, depth=7, num_heads=4, mlp_ratio=2, **kw)

@@ -207,6 +207,9 @@ class TokenPruning(Classification):
     def ffn_stats_into(self, *a, **kw):
         return self._refused(super().ffn_stats_into, *a, **kw)
 
+    def activation_grams_into(self, *a, **kw):
+        return self._refused(super().activation_grams_into, *a, **kw)
+
     # -- the scheduled forward with its exports -------------------------------------------------
     def _int32_tensor(self, name: str, t, shape) -> int:
         if t is None:

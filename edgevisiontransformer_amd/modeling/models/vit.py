@@ -145,6 +145,12 @@ class ViT(DepthAxis):
         c = self.cfg
         return [(int(f), c.tokens) for f in list(c.ffn)[:c.depth]]
 
+    # -- activation Grams (grams.py): the attention context is heads * head_dim wide -------------
+    def _attn_context_geometry(self):
+        c = self.cfg
+        return [(int(h) * int(d), c.tokens)
+                for h, d in zip(list(c.heads)[:c.depth], list(c.head_dim)[:c.depth])]
+
 
 class ViT_Pruned(ViT):
     """Head/FFN-pruned ViT (reference `ViT_Pruned`, vit.py:58-75)."""

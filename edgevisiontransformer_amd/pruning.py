@@ -363,6 +363,125 @@ def prune_vit_params(params: Dict[str, np.ndarray], cfg: ViTConfig, kept_heads: 
     return out, new_cfg
 
 
+# Default ridge of reconstruct_linear, relative to the mean eigenvalue of C_SS. The Grams come from
+# fp32 sums over R = 10^5 .. 10^6 token rows: their entries carry a relative error of the order of
+# sqrt(R) 2^-24 (2e-5 .. 6e-5), and forming C = G / R - mu mu^T cancels part of the leading digits.
+# Directions of C_SS whose eigenvalue is below about 1e-4 of the mean are therefore noise, and an
+# unregularised solve would divide by them; 1e-4 damps exactly those and changes a well-conditioned
+# solve by a relative 1e-4, well under the bf16 rounding (2^-9) of the weights it produces. The
+# value follows from that error estimate; it was not tuned on a dataset.
+DEFAULT_RIDGE = 1e-4
+
+
+def _checked_keep(keep, n: int, what: str) -> np.ndarray:
+    k = np.asarray(list(keep), dtype=np.int64).reshape(-1)
+    if k.size == 0:
+        raise ValueError(f"{what}: keep is empty")
+    if k.min() < 0 or k.max() >= n:
+        raise ValueError(f"{what}: keep has an index outside [0, {n})")
+    if np.unique(k).size != k.size:
+        raise ValueError(f"{what}: keep has a repeated index")
+    return k
+
+
+def reconstruct_linear(W, b, keep, gram, sums, rows, ridge: float = DEFAULT_RIDGE
+                       ) -> Tuple[np.ndarray, np.ndarray]:
+    """Least-squares repair of a linear layer y = h W + b (W [F, D], b [D]) whose input is cut to
+    the columns `keep` of h, from the second moments of h over a calibration set: `gram` = H^T H
+    [F, F], `sums` = the column sums [F], `rows` = the rows of H (`collect_grams`). With
+
+        mu = sums / rows          C = gram / rows - mu mu^T       S = keep
+
+    the weights that minimise E |h W + b - (h_S W'_S + b')|^2 over the calibration rows are
+
+        W'_S = (C_SS + lambda I)^-1 C_S,: W        b' = b + mu^T W - mu_S^T W'_S
+
+    with lambda = ridge * trace(C_SS) / |S| (`ridge` = 0: the plain least-squares solution; the
+    default is DEFAULT_RIDGE, see there). Returns (W', b') in fp64, W' full size [F, D] with the
+    rows outside `keep` zero, so that `prune_vit_params` slices it like the dense weights. All of
+    the dropped columns' mean and of what the kept columns predict of them moves into W'_S and b';
+    keep = all returns W and b. Pure numpy fp64: a Cholesky solve, `lstsq` when C_SS + lambda I is
+    not positive definite."""
+    W = np.asarray(W, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    G = np.asarray(gram, dtype=np.float64)
+    sm = np.asarray(sums, dtype=np.float64)
+    if W.ndim != 2:
+        raise ValueError(f"W must be [F, D], got {W.shape}")
+    F, D = W.shape
+    if b.shape != (D,):
+        raise ValueError(f"b must be [{D}], got {b.shape}")
+    if G.shape != (F, F) or sm.shape != (F,):
+        raise ValueError(f"gram must be [{F}, {F}] and sums [{F}], got {G.shape} and {sm.shape}")
+    if not rows >= 1:
+        raise ValueError("rows must be at least 1")
+    if ridge < 0:
+        raise ValueError("ridge must be non-negative")
+    S = _checked_keep(keep, F, "reconstruct_linear")
+    if S.size == F and np.array_equal(np.sort(S), np.arange(F)):
+        return W.copy(), b.copy()
+    mu = sm / float(rows)
+    C = G / float(rows) - np.outer(mu, mu)
+    css = C[np.ix_(S, S)]
+    rhs = C[S, :] @ W
+    lam = float(ridge) * float(np.trace(css)) / S.size
+    A = css + lam * np.eye(S.size)
+    try:
+        L = np.linalg.cholesky(A)
+        ws = np.linalg.solve(L.T, np.linalg.solve(L, rhs))
+    except np.linalg.LinAlgError:
+        ws = np.linalg.lstsq(A, rhs, rcond=None)[0]
+    Wn = np.zeros_like(W)
+    Wn[S] = ws
+    bn = b + mu @ W - mu[S] @ ws
+    return Wn, bn
+
+
+def _block_grams(grams, depth: int, what: str):
+    if not isinstance(grams, dict) or not {"gram", "sum", "rows"} <= set(grams):
+        raise ValueError(f"{what} must be the {{'gram', 'sum', 'rows'}} dict of collect_grams")
+    if len(grams["gram"]) != depth or len(grams["sum"]) != depth:
+        raise ValueError(f"{what} must hold one Gram and one sum per layer ({depth})")
+    return grams["gram"], grams["sum"], grams["rows"]
+
+
+def reconstruct_vit_params(params: Dict[str, np.ndarray], cfg: ViTConfig,
+                           kept_heads: Optional[List[List[int]]] = None,
+                           kept_ffn: Optional[List[List[int]]] = None, ffn_grams=None,
+                           attn_grams=None, ridge: float = DEFAULT_RIDGE) -> Dict[str, np.ndarray]:
+    """A copy of the FULL-SIZE parameter dict whose FC2 (`l{i}.fc2_w` / `fc2_b`, for `kept_ffn`)
+    and out-projection (`l{i}.out_w` / `out_b`, for `kept_heads`; a kept head is its head_dim rows
+    of out_w) are repaired by `reconstruct_linear` for the cut the kept lists describe, from the
+    Grams of every block of the unpruned model: `ffn_grams` = collect_grams(model, loader, "ffn"),
+    `attn_grams` = collect_grams(model, loader, "attn"). The rows of the dropped neurons / heads
+    are zero, so the result feeds `prune_vit_params` / `build_pruned_vit` with the same kept lists
+    unchanged. Calibration is one pass on the unpruned model: block i's repair does not see the
+    repairs of the blocks before it. Entries keep the dtype of `params`."""
+    depth = cfg.depth
+    out = {k: np.array(v, copy=True) for k, v in params.items()}
+    jobs = []
+    if kept_ffn is not None:
+        if len(kept_ffn) != depth:
+            raise ValueError("one kept list per layer")
+        g, s, r = _block_grams(ffn_grams, depth, "ffn_grams")
+        jobs += [(f"l{i}.fc2_w", f"l{i}.fc2_b", list(kept_ffn[i]), g[i], s[i], r)
+                 for i in range(depth)]
+    if kept_heads is not None:
+        if len(kept_heads) != depth:
+            raise ValueError("one kept list per layer")
+        g, s, r = _block_grams(attn_grams, depth, "attn_grams")
+        for i in range(depth):
+            hd = int(cfg.head_dim[i])
+            kh = _checked_keep(kept_heads[i], int(cfg.heads[i]), f"layer {i} heads")
+            rows_kept = (kh[:, None] * hd + np.arange(hd)[None, :]).reshape(-1)
+            jobs.append((f"l{i}.out_w", f"l{i}.out_b", rows_kept, g[i], s[i], r))
+    for wn, bn, keep, g, s, r in jobs:
+        w, b = reconstruct_linear(params[wn], params[bn], keep, g, s, r, ridge)
+        out[wn] = w.astype(np.asarray(params[wn]).dtype)
+        out[bn] = b.astype(np.asarray(params[bn]).dtype)
+    return out
+
+
 def build_pruned_vit(params: Dict[str, np.ndarray], cfg: ViTConfig, kept_heads: List[List[int]],
                      kept_ffn: Optional[List[List[int]]] = None, **kw):
     """The MI355X ViT of a pruned checkpoint (exact per-layer shapes; needs the GPU)."""

@@ -519,6 +519,7 @@ int evt_model_qkv_layout(const evt_model* m, int* headmajor_layers);
 #include "evt_attention_maps.h"  /* evt_forward_attention, evt_attn_map_shape, evt_attention_probs */
 #include "evt_head_stats.h"  /* evt_forward_head_stats, evt_head_stats_shape, evt_attention_head_stats */
 #include "evt_ffn_stats.h"  /* evt_forward_ffn_stats, evt_ffn_stats_shape, evt_ffn_neuron_stats */
+#include "evt_gram.h"  /* evt_forward_grams, evt_gram_shape, evt_gram, evt_gram_scratch_bytes */
 #include "evt_rollout.h"  /* evt_forward_rollout, evt_rollout_shape, evt_rollout_scratch_bytes, evt_attention_rollout_step */
 #include "evt_token_pruning.h"  /* evt_model_set_token_schedule, evt_forward_token_pruning, evt_token_scores / _select / _gather */
 #include "evt_gates.h"  /* evt_model_set_head_gates / _ffn_gates, evt_model_clear_gates, evt_model_get_*_gates, evt_gate_weights */
